@@ -12,11 +12,21 @@ the headline is the metric BASELINE names and the N = 2/4/8 runs exercise the co
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...` (one rank per GPU, RCCL); started by torchrun it
 reads RANK / LOCAL_RANK / WORLD_SIZE.  It refuses to print a line when fewer than N ranks / GPUs are available.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+A plain run (`python bench.py --gpus N --steps K --warmup W`) measures the headline only: set-up, W warm-up steps, K timed
+steps (one repetition unless --reps says otherwise; a --full run keeps the median of 3 repetitions of K steps), then the line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (one timed step, in ms), `final_loss`, `config` and the derived `roofline_e2e` [+ `rccl` when N > 1].
+`--dump-outputs DIR` then writes what the last timed step computed as DIR/<name>.npy (float32): `loss`, `params` (every
+parameter after the optimizer, flattened and concatenated in named_parameters() order), `grads` (their gradients, same
+order) and `bn_stats` (the BatchNorm running statistics) - at most 64 MB in all, larger arrays cut to a fixed, seeded sample
+of their elements (`dump_outputs`).  Inputs, weights and labels are seeded, and with --dump-outputs the last timed step
+starts from the run's seeded start state, reset off the clock (`train_bench`): the same arguments give the same inputs and outputs every run.
+
+`--full` adds every other measurement, each as an extra object of the same line (the `--no-*` options drop single legs):
   roofline       the kernel with the largest share of the timed step: algorithmic HBM bytes (or flops) per launch / its
                  mean launch duration (HIP events on the launch stream) against the 8 TB/s HBM3E (or MFMA) peak;
                  `traffic` = measured HBM bytes per launch from the committed PMC passes (profiles/pmc_traffic_*.json)
-  roofline_e2e   the whole training step at SURVEY 8(d)'s 285.8 MB algorithmic bytes per clip
+  roofline_e2e   the whole training step at SURVEY 8(d)'s 285.8 MB algorithmic bytes per clip (in a plain run too);
+                 --full adds the bytes the step's launches move (`moved_bytes_per_step`, `pmc_bytes_per_step`)
   forward        BASELINE configs[1]: log-mel + mn10 eval forward, batch 256, hipGraph replay: clips/s, ms, fraction of the
                  HBM roofline at the 96.37 MB/clip contract bytes AND at the bytes the launch plan actually moves
                  (sum of every kernel's own input + output), `fp32_exact` = every 1x1 conv on the exact fp32 MFMA
@@ -73,11 +83,15 @@ def _fan_in_init(model, head_scale=None):
             model.classifier[5].weight.mul_(head_scale)   # keep |logits| O(1) so the parity probe reads like 1e-3 abs
 
 
-def build_model(dev):
+def build_model(dev, eval_model=True):
+    """(log-mel front-end, mn10 eval model); the model is None when `eval_model` is False (a plain bench run needs the
+    front-end only: the train step builds its own network)."""
     from efficientat_amd.mn import get_model
     from efficientat_amd.preprocess import AugmentMelSTFT
     torch.manual_seed(0)
     mel = quiet(AugmentMelSTFT, freqm=0, timem=0).to(dev).eval()
+    if not eval_model:
+        return mel, None
     model = quiet(get_model, width_mult=1.0)
     _fan_in_init(model, head_scale=0.05)
     return mel, model.to(dev).eval()
@@ -908,6 +922,29 @@ def make_train_model(name, dev, precision=None):
     return model.to(dev)
 
 
+DUMP_BUDGET = 60_000_000       # bytes of array data written by --dump-outputs (64 MB in all with the .npy headers, at most)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET):
+    """{name: tensor} -> out_dir/<name>.npy, float32 (float64 stays float64).  When the whole exceeds `budget` bytes, every
+    tensor of more than 4096 elements is cut to the same fraction of its flattened elements, chosen by a generator seeded
+    with the tensor's name (sorted indices: two runs with the same arguments write the same elements)."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[k] = (v.double() if v.dtype == torch.float64 else v.float()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    small = sum(a.nbytes for a in host.values() if a.size <= 4096)
+    frac = 1.0 if total <= budget else 0.99 * (budget - small) / (total - small)
+    for k, a in host.items():
+        if frac < 1.0 and a.size > 4096:
+            rng = np.random.default_rng(zlib.crc32(k.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, max(1, int(a.size * frac)), replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _adam(params, capturable):
     """The optimizer of the timed steps (ex_audioset.py:86-91: Adam, lr 8e-4): the library's one-launch multi-tensor Adam
     (`efficientat_amd.optim.FusedAdam`, eat_adam_multi) - EAT_ADAM=torch selects torch.optim.Adam(fused=True) for A/B."""
@@ -919,11 +956,31 @@ def _adam(params, capturable):
     return FusedAdam(params, lr=8e-4, capturable=capturable)
 
 
-def train_bench(name, batch, steps, warmup, args, mel, wave, ranks, precision=None):
+def reset_train_state(model, opt, start):
+    """Back to the state a run starts from, in place (a captured step keeps its addresses): parameters and BatchNorm
+    buffers <- `start` (a copy of model.state_dict() values), Adam moments and step counter <- 0.  Stream-ordered
+    multi-tensor copy / zero launches, no synchronisation."""
+    with torch.no_grad():
+        torch._foreach_copy_(list(model.state_dict().values()), start)
+        torch._foreach_zero_([v for st in opt.state.values() for v in st.values() if torch.is_tensor(v)]
+                             + list(getattr(opt, "_counters", {}).values()))
+    cache = getattr(model, "_cache", None)
+    if cache is not None:
+        cache.invalidate()
+
+
+def train_bench(name, batch, steps, warmup, args, mel, wave, ranks, precision=None, dump_dir=None):
     """Full training step per GPU: log-mel (train mode) -> forward (batch-stat BN) -> BCE-with-logits ->
     hand-written backward -> [bucketed RCCL all-reduce of the gradient, overlapped with backward] -> fused Adam.
     Mirrors ex_audioset.py:139-199 without data loading / wandb / KD teacher.  The step (incl. the collectives when
-    N > 1) is captured into one hipGraph and replayed; the log-mel stays outside (host RNG draws per step)."""
+    N > 1) is captured into one hipGraph and replayed; the log-mel stays outside (host RNG draws per step).
+    `dump_dir`: after the timed steps, the last step's loss, gradients, updated parameters and BatchNorm statistics
+    are written there (`dump_outputs`).  The kernels add floats with atomics in places, so a step is reproducible to
+    rounding only and N + W Adam steps carry that spread much further; the last timed step therefore starts from the
+    seeded state the run started from (parameters, BatchNorm statistics, zero Adam moments and step counter:
+    `reset_train_state`, between the timed intervals of steps 1..N-1 and step N), which makes its outputs the same from
+    run to run.  That step is Adam's first from the initial weights: the dump shows one step's loss, gradients and
+    update, not moments or running statistics accumulated over many steps."""
     import torch.nn.functional as F
     from efficientat_amd.dp import enable_data_parallel
     dev = ranks.dev
@@ -936,6 +993,7 @@ def train_bench(name, batch, steps, warmup, args, mel, wave, ranks, precision=No
     if use_dp:
         enable_data_parallel(model, force_buckets=ranks.world == 1)
     graphed = not args.no_graph
+    start = dump_dir is not None and [v.detach().clone() for v in model.state_dict().values()]
     model.train()
     mel.train()
     launch = "eager"
@@ -954,6 +1012,7 @@ def train_bench(name, batch, steps, warmup, args, mel, wave, ranks, precision=No
             print(f"[bench] train-step graph capture failed for {name} ({type(e).__name__}: {e}); eager", file=sys.stderr)
             graphed = False
             model = make_train_model(name, dev, precision)
+            start = start and [v.detach().clone() for v in model.state_dict().values()]
             if use_dp:
                 enable_data_parallel(model, force_buckets=ranks.world == 1)
             model.train()
@@ -986,8 +1045,31 @@ def train_bench(name, batch, steps, warmup, args, mel, wave, ranks, precision=No
     # median of `reps` repetitions; every repetition times EXACTLY `steps` steps between barrier +
     # synchronize pairs (max over ranks) - the reported value / ms_per_step are those of the median repetition
     reps = max(1, getattr(args, "reps", 1))
-    els = sorted(ranks.timed(lambda: out.__setitem__("loss", tstep()), steps) for _ in range(reps))
+
+    def timed_step():
+        out["loss"] = tstep()
+
+    def timed_rep(last):
+        if not (start and last):
+            return ranks.timed(timed_step, steps)
+        # --dump-outputs: the last timed step of the run starts from the run's seeded start state; the reset (~1.5 ms of
+        # copy / zero launches) runs between two timed intervals, off the clock, and the reported time is their sum
+        el = ranks.timed(timed_step, steps - 1) if steps > 1 else 0.0
+        reset_train_state(model, opt, start)
+        return el + ranks.timed(timed_step, 1)
+    els = sorted(timed_rep(r == reps - 1) for r in range(reps))
     el = els[len(els) // 2]
+    if dump_dir is not None and (ranks.dist is None or ranks.dist.get_rank() == 0):
+        # one array per kind, tensors flattened and concatenated in named_parameters() / named_buffers() order: a comparison
+        # then runs at the model's scale (as the gradient tests do), not at the scale of tensors whose exact gradient is zero
+        # (the BatchNorm shifts in front of a batch-statistics BatchNorm hold rounding noise of order 1e-11 only)
+        with torch.no_grad():
+            ps = [p for _, p in model.named_parameters()]
+            arrays = {"loss": out["loss"].reshape(1),
+                      "params": torch.cat([p.detach().float().reshape(-1) for p in ps]),
+                      "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).float().reshape(-1) for p in ps]),
+                      "bn_stats": torch.cat([b.float().reshape(-1) for _, b in model.named_buffers() if b.is_floating_point()])}
+        dump_outputs(dump_dir, arrays)
     if evs:
         gaps = [round(evs[i][0].elapsed_time(evs[i + 1][0]), 2) for i in range(len(evs) - 1)]
         host = [round((evs[i + 1][1] - evs[i][1]) * 1e3, 2) for i in range(len(evs) - 1)]
@@ -1146,7 +1228,9 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=3, help="repetitions of the timed region (each exactly --steps steps); the median is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the timed region (each exactly --steps steps); the median is reported "
+                         "(default: 1 in a plain run; 3 for every leg of a --full run, the headline included)")
     ap.add_argument("--batch", type=int, default=256, help="clips per GPU per step")
     ap.add_argument("--streams", type=int, default=2, help="sub-batches issued on concurrent HIP streams per step")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
@@ -1164,7 +1248,15 @@ def parse_args(argv=None):
                          "calibrate the counters of that pass (tools/pmc_traffic.py)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rank plumbing only (gloo, CPU, no kernels): used by the CPU test of the N-rank launch path")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other measurement: forward, exact-fp32 and KD steps, the other train "
+                         "configs, per-kernel profiles / roofline, parity against the CPU oracle, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MB)")
+    args = ap.parse_args(argv)
+    if not args.full and (args.kernel_table or args.calibrate_traffic):
+        ap.error("--kernel-table and --calibrate-traffic belong to the measurements of --full")
+    return args
 
 
 def _claim_stdout():
@@ -1228,7 +1320,7 @@ def main():
     ranks = Ranks(dist, world, dev)
 
     from efficientat_amd import mn as mn_mod
-    if args.calibrate_traffic and rank == 0:
+    if args.full and args.calibrate_traffic and rank == 0:
         from efficientat_amd import _lib
         n = 1 << 28                                             # 1 GiB per buffer: past the 256 MiB Infinity Cache
         src = torch.rand(n, device=dev)
@@ -1239,13 +1331,16 @@ def main():
         torch.cuda.synchronize()
         del src, dst
         torch.cuda.empty_cache()
-    mel, model = build_model(dev)
+    mel, model = build_model(dev, eval_model=args.full)      # the eval model serves the forward / parity legs of --full
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
     wave = (0.1 * torch.randn(args.batch, CLIP_SAMPLES, device=dev, generator=g)).clamp_(-1, 1)
 
     # ------------------------------------------------------------------ headline: the training step (fwd + bwd)
     train_name = args.train_model or "mn10"
-    head = train_bench(train_name, args.batch, args.steps, args.warmup, args, mel, wave, ranks)
+    head_args = argparse.Namespace(**{**vars(args), "reps": args.reps or (3 if args.full else 1)})
+    head = train_bench(train_name, args.batch, args.steps, args.warmup, head_args, mel, wave, ranks,
+                       dump_dir=args.dump_outputs)       # every rank starts its last step alike; rank 0 writes
+    args.reps = args.reps or 3                 # the legs of --full: median of 3 repetitions, as the headline there
     arithmetic = {
         "auto": "fp32 activations and accumulation; 1x1 convs and their gradients: exact fp32 MFMA for C_in < 40, "
                 "split-operand bf16x3 MFMA (x = hi + lo, 3 products, ~2^-16 rel. error) from C_in >= 40",
@@ -1277,8 +1372,9 @@ def main():
                                  "(SURVEY 8d: 3 x forward activations + 28 B per parameter / batch + mel)"},
     }
 
+    # ------------------------------------------------------------------ --full: everything besides the headline
     # ------------------------------------------------------------------ BASELINE configs[1]: forward only
-    if not args.no_forward:
+    if args.full and not args.no_forward:
         clips_per_s, ms_step, launch = forward_bench(args, mel, model, wave, ranks)
         fwd = {"value": round(clips_per_s, 1), "unit": "clips/s", "ms_per_step": round(ms_step, 4), "steps": args.steps,
                "warmup": args.warmup, "batch_per_gpu": args.batch, "launch": launch,
@@ -1301,7 +1397,7 @@ def main():
                 model._cache.invalidate()
         result["forward"] = fwd
 
-    if not args.no_fp32_exact and os.environ.get("EAT_TRAIN_PRECISION", "auto") != "fp32":
+    if args.full and not args.no_fp32_exact and os.environ.get("EAT_TRAIN_PRECISION", "auto") != "fp32":
         # the same training step with every GEMM on the exact fp32 MFMA (the reference CPU path's arithmetic)
         try:
             ex = train_bench(train_name, args.batch, max(5, args.steps // 3), 2, args, mel, wave, ranks, precision="fp32")
@@ -1315,14 +1411,14 @@ def main():
             result["train_step_fp32_exact"] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
 
-    if not args.no_kd and args.train_model is None:
+    if args.full and not args.no_kd and args.train_model is None:
         try:
             result["kd_train_step"] = kd_bench(args, mel, wave, ranks)
         except Exception as e:  # pragma: no cover - one failing leg must not lose the line
             result["kd_train_step"] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_train_configs and args.train_model is None:
+    if args.full and world == 1 and not args.no_train_configs and args.train_model is None:
         for key, name, bt, st, wu in [("train_step_mn40_bf16", "mn40_bf16", 128, 10, 2), ("train_step_dymn20", "dymn20", 128, 10, 2),
                                       ("train_step_dymn20_bf16", "dymn20_bf16", 128, 10, 2)]:
             try:
@@ -1344,10 +1440,11 @@ def main():
                 except Exception as e:  # pragma: no cover
                     result[key] = {"error": f"{type(e).__name__}: {e}", "model": name}
                 torch.cuda.empty_cache()
-    model.eval()
+    if model is not None:
+        model.eval()
     mel.eval()
 
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         # ---- dominant kernel of the timed step: one eager training step with a HIP event pair around every launch
         import torch.nn.functional as F
         tm = make_train_model(train_name, dev)
@@ -1424,13 +1521,14 @@ def main():
                           "buckets": red.get("buckets"), "bytes_per_step": red.get("bytes"),
                           "bucket_bytes": red.get("bucket_bytes"), "forced_single_rank": bool(force_dist and world == 1)}
     if rank == 0:
-        err, scale = parity_probe(mel, model, dev)
-        result["parity"] = {"logit_max_abs_err": err, "logit_abs_max": scale, "vs": "CPU oracle, 4 clips, same weights (eval forward)"}
-        try:
-            result["parity"]["train_grads"] = parity_grad_probe(dev)
-        except Exception as e:  # pragma: no cover
-            result["parity"]["train_grads"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            err, scale = parity_probe(mel, model, dev)
+            result["parity"] = {"logit_max_abs_err": err, "logit_abs_max": scale, "vs": "CPU oracle, 4 clips, same weights (eval forward)"}
+            try:
+                result["parity"]["train_grads"] = parity_grad_probe(dev)
+            except Exception as e:  # pragma: no cover
+                result["parity"]["train_grads"] = {"error": f"{type(e).__name__}: {e}"}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ref_root = os.environ.get("EAT_REFERENCE_ROOT")
             if ref_root and os.path.isfile(os.path.join(ref_root, "models", "mn", "model.py")):
                 try:

@@ -221,14 +221,17 @@ def test_pw_wgrad_wide_tile_random_shapes(B, Co, Ci, S, sc):
 
 # whole-network gradients at rel-L2 <= 1e-2 per tensor.  What stands in the way is not arithmetic but activation
 # kinks: ONE element crossing ReLU's 0 / Hardswish's +-3 between two evaluations moves every tensor upstream through the
-# BatchNorm mean terms (the reference in fp32 vs ITSELF in fp64 shows 1-2e-3 on every tensor upstream of features.12, SURVEY
-# 8c).  Measured on MI355X (round 6) on this pinned batch: exact fp32 leaves 6 of 159 tensors above 1e-2 (max 1.40e-2), the
-# default "auto" arithmetic 5 of 159 (max 1.18e-2) - every one of them a BatchNorm scale / shift or the conv in front of it in
-# the first 7 blocks, whose gradient is a sum over 10^6-10^7 positions through 2-3 activation layers (per-op backward tests on
-# the oracle's saved tensors sit at 2e-5).  That CLASS is named here, like _ATTENTION_HEAD for DyMN; a tensor outside it above
-# 1e-2, a member above 2e-2, or more than _MAX_ABOVE_1E2 members fails.
+# BatchNorm mean terms - a BatchNorm scale / shift or the conv in front of it in the first 7 blocks, whose gradient is a sum
+# over 10^6-10^7 positions through 2-3 activation layers (per-op backward tests on the oracle's saved tensors sit at 2e-5).
+# Whether such a flip happens depends on the rounding of the evaluation, so it is a matter of chance and of the machine:
+# the fp32 CPU evaluation of the oracle against its own fp64 evaluation shows no flip on one host (median 1e-5) and several
+# on another (median 6.7e-3, 7 tensors above 1e-2; SURVEY 8c saw 1-2e-3 upstream of features.12).  The gradients are
+# therefore compared with the fp64 evaluation, which has no flips to speak of.  Measured on MI355X against it, the same in
+# three evaluations: exact fp32 median 1.9e-5, max 9.6e-3, none above 1e-2; the default "auto" arithmetic (split-operand
+# bf16x3 products, ~2^-16) median 5.4e-3, max 1.09e-2, 4 above 1e-2, all in the class.  That CLASS is named here, like
+# _ATTENTION_HEAD for DyMN; a tensor outside it above 1e-2, a member above 2e-2, or more than _MAX_ABOVE_1E2 members fails.
 _KINK_CLASS = re.compile(r"^features\.[0-7]\.(block\.\d\.)?[01]\.(weight|bias)$")
-_MAX_ABOVE_1E2 = {"fp32": 8, "auto": 8}
+_MAX_ABOVE_1E2 = {"fp32": 2, "auto": 6}
 
 
 @pytest.mark.parametrize("precision", ["auto", "fp32"])
@@ -242,12 +245,12 @@ def test_mn10_train_step_matches_oracle(golden_dir, precision):
     y = torch.from_numpy(g["train_labels"])
     keep = torch.from_numpy(g["drop_keep"].astype(np.float32))
 
-    # oracle: torch-CPU autograd over the restatement (itself pinned to the reference's grads)
-    sdr = {k: (v.clone().requires_grad_(True) if v.dtype.is_floating_point and not k.endswith(
-        ("running_mean", "running_var")) else v.clone()) for k, v in sd.items()}
+    # oracle: torch-CPU autograd over the restatement (itself pinned to the reference's grads), evaluated in fp64
+    sdr = {k: (v.double().requires_grad_(True) if v.dtype.is_floating_point and not k.endswith(("running_mean", "running_var"))
+               else (v.double() if v.dtype.is_floating_point else v.clone())) for k, v in sd.items()}
     stats = {}
-    logits_ref, _ = O.mn_forward(sdr, x, train=True, stats=stats, drop_mask=keep)
-    loss_ref = F.binary_cross_entropy_with_logits(logits_ref, y)
+    logits_ref, _ = O.mn_forward(sdr, x.double(), train=True, stats=stats, drop_mask=keep.double())
+    loss_ref = F.binary_cross_entropy_with_logits(logits_ref, y.double())
     loss_ref.backward()
 
     model = _quiet(get_model, width_mult=1.0)
@@ -263,9 +266,7 @@ def test_mn10_train_step_matches_oracle(golden_dir, precision):
     assert float((logits.detach().cpu() - logits_ref.detach()).abs().max()) < 1e-3
     assert np.abs(logits.detach().cpu().numpy() - g["train_logits"]).max() < 1e-3
     gmax = max(float(v.grad.norm()) for k, v in sdr.items() if getattr(v, "grad", None) is not None)
-    # Measured on MI355X (a per-tensor diagnostic): vs an fp64 evaluation the CPU fp32 oracle itself is
-    # off by 0.45 % median / 1.0 % max per tensor (activation-kink flips), the HIP path by 0.65 % / 1.9 %
-    # - the same error class.  Hard bound: 3 % per tensor, 1 % median; SURVEY's 1e-2 with the named / counted exceedances.
+    # Hard bound against the fp64 oracle: 3 % per tensor, 1 % median; SURVEY's 1e-2 with the named / counted exceedances.
     bad, rels, above = [], [], []
     for name, p in model.named_parameters():
         ref = sdr[name].grad

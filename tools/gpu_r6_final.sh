@@ -4,10 +4,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 REF=$GRAFT_REPO_ROOT/.refstage/reference
 # 1. the bench line of record (reference staged: cpu_baseline kind "reference")
-EAT_REFERENCE_ROOT=$REF timeout -k 10 1500 python bench.py --kernel-table > $OUT/bench.json 2> $OUT/bench_table.log
+EAT_REFERENCE_ROOT=$REF timeout -k 10 1500 python bench.py --full --kernel-table > $OUT/bench.json 2> $OUT/bench_table.log
 tail -c 1500 $OUT/bench.json; echo
 # 2. rocprofv3 kernel statistics of the mn10 bench (graph-captured steps + forward replays)
-(cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/stats -o s --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-fp32-exact --no-train-configs --no-kd > $GRAFT_REPO_ROOT/$OUT/rocprof_bench.json 2> $GRAFT_REPO_ROOT/$OUT/rocprof.log)
+(cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/stats -o s --output-format csv -- python $OLDPWD/bench.py --full --no-cpu-baseline --no-fp32-exact --no-train-configs --no-kd > $OLDPWD/$OUT/rocprof_bench.json 2> $OLDPWD/$OUT/rocprof.log)
 find $OUT/stats -name "*kernel_stats.csv" -exec cp {} $OUT/r6_rocprof_kernel_stats.csv \; ; rm -rf $OUT/stats
 head -5 $OUT/r6_rocprof_kernel_stats.csv | cut -c1-160
 # 3. rocprofv3 kernel statistics of the dymn20 bf16 step

@@ -1,8 +1,8 @@
 """Turn rocprofv3 PMC passes into per-kernel HBM traffic of ONE training step / ONE forward for bench.py's `roofline.traffic`
 and `roofline_e2e.pmc_bytes_per_step`.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir_f> -o f --output-format csv -- python bench.py --calibrate-traffic ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d <dir_w> -o w --output-format csv -- python bench.py --calibrate-traffic ...
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir_f> -o f --output-format csv -- python bench.py --full --calibrate-traffic ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d <dir_w> -o w --output-format csv -- python bench.py --full --calibrate-traffic ...
     python tools/pmc_traffic.py <dir_f>/f_counter_collection.csv <dir_w>/w_counter_collection.csv profiles/pmc_traffic_r5.json
 
 FETCH_SIZE / WRITE_SIZE are in KiB.  The file keeps RAW counter sums; bench.py multiplies them by the calibration factors
