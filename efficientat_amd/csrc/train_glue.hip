@@ -285,7 +285,7 @@ extern "C" int eat_col_sum(const float* m, float* out, int R, int C, eat_stream_
 //   m = m + (1 - b1) (g' - m);  v = b2 v + (1 - b2) g'^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // - the order of operations of torch's fused kernel (aten/src/ATen/native/cuda/fused_adam_utils.cuh), bias corrections in fp64.
 namespace {
-struct AdamChunk { float* p; const float* g; float* m; float* v; int n; int pad; };
+struct AdamChunk { float* p; const float* g; float* m; float* v; int n; int pad; };   // pad: step offset (see below)
 static_assert(sizeof(AdamChunk) == 40, "host side builds the table as 40-byte records");
 
 __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamChunk* __restrict__ table, const float* __restrict__ lr_ptr,
@@ -293,7 +293,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamChunk* __rest
                                                          double b1, double b2, double eps, double wd, int decoupled,
                                                          double grad_scale) {
   const AdamChunk c = table[blockIdx.x];
-  const double t = (double)(step_ptr ? *step_ptr : step_val) + 1.0;
+  // c.pad: the parameter's step minus the launch's (eager parameters that skipped a step - torch's per-parameter `step`)
+  const double t = (double)(step_ptr ? *step_ptr : step_val) + (double)c.pad + 1.0;
   const double lr = lr_ptr ? (double)*lr_ptr : lr_val;
   const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
   const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);

@@ -258,24 +258,31 @@ class GraphedKDTrainer(KDTrainer):
 
 
 def _snapshot(model, opt):
+    """Copies of the model's state and of the optimizer's live state (`opt.state`, keyed by parameter: `state_dict()` may hand
+    out copies - FusedAdam's steps are) and of FusedAdam's per-group step counters."""
     sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    od = opt.state_dict()
-    ost = {k: {n: (t.detach().clone() if torch.is_tensor(t) else t) for n, t in st.items()} for k, st in od["state"].items()}
-    return sd, ost
+    ost = {p: {n: (t.detach().clone() if torch.is_tensor(t) else t) for n, t in st.items()} for p, st in opt.state.items()}
+    ctr = {gi: c.detach().clone() for gi, c in getattr(opt, "_counters", {}).items()}
+    return sd, ost, ctr
 
 
 def _restore(model, opt, state):
-    """In place (the captured graph holds the addresses of the parameters and of the optimizer's moment buffers)."""
-    sd, ost = state
+    """In place (the captured graph holds the addresses of the parameters, of the optimizer's moment buffers and of its step
+    counters)."""
+    sd, ost, ctr = state
     with torch.no_grad():
         for k, v in model.state_dict().items():
             v.copy_(sd[k])
-        cur = opt.state_dict()["state"]
-        for k, st in cur.items():
+        for p, st in opt.state.items():
             for n, t in st.items():
                 if not torch.is_tensor(t):
                     continue
-                if k in ost and n in ost[k]:
-                    t.copy_(ost[k][n])
+                if p in ost and n in ost[p]:
+                    t.copy_(ost[p][n])
                 else:
                     t.zero_()                            # state created by the warm-up (first use of the optimizer)
+        for gi, c in getattr(opt, "_counters", {}).items():
+            if gi in ctr:
+                c.copy_(ctr[gi])
+            else:
+                c.zero_()                                # FusedAdam's counter, created by the warm-up

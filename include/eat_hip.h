@@ -693,10 +693,11 @@ int eat_kd_loss_fwd_bwd(const float* logits, const float* y, const int* perm, co
 /* The optimizer step of the training loop (ex_audioset.py:86-91 `torch.optim.Adam` / `AdamW` over all parameters, :197-199
  * `optimizer.step()`) as ONE launch over every parameter: table = n_chunks records of 40 bytes
  * { float* p; const float* g; float* m; float* v; int n; int pad; } - a chunk is <= 4096 consecutive elements of one parameter
- * with its gradient and the two moment buffers (fp32, updated in place).
+ * with its gradient and the two moment buffers (fp32, updated in place); pad = that parameter's step minus `step` (0 unless some
+ * parameters skipped earlier steps: torch keeps one step per parameter).
  *   g' = g * grad_scale (+ weight_decay * p when decoupled == 0: Adam's L2 form);  decoupled != 0 (AdamW): p *= 1 - lr * weight_decay;
  *   m += (1 - beta1) (g' - m);  v = beta2 v + (1 - beta2) g'^2;  p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
- * with t = step + 1.  lr_ptr / step_ptr != NULL: the learning rate / step counter are read from the device (hipGraph replays,
+ * with t = step + pad + 1.  grad_scale MULTIPLIES the gradient (torch's fused-Adam kwarg of that name divides).  lr_ptr / step_ptr != NULL: the learning rate / step counter are read from the device (hipGraph replays,
  * schedulers that write a tensor) and *step_ptr is advanced by one after the update; NULL: the by-value arguments are used.
  * Hyper-parameters are doubles and the second-moment / update expressions are evaluated in fp64 where torch's fused kernel
  * evaluates them in fp64 (aten/src/ATen/native/cuda/fused_adam_utils.cuh: double hyper-parameters promote those lines). */

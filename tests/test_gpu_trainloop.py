@@ -473,3 +473,84 @@ def test_training_steps_read_no_uninitialised_memory(name):
             assert "non-finite grads 0 []; params 0 []" in ln, ln
         else:                                           # captured: "... non-finite params 0 []; grads []"
             assert "non-finite params 0 []; grads []" in ln, ln
+
+
+def _fused_adam(m):
+    from efficientat_amd.optim import FusedAdam
+    return FusedAdam(m.parameters(), lr=torch.tensor(1e-3, device=DEV), capturable=True)
+
+
+def _kd_trainer(tag, opt_for, tlogits, f2i, B, L):
+    from efficientat_amd.train_loop import GraphedKDTrainer
+    m = _kd_setup()
+    with contextlib.redirect_stdout(io.StringIO()):
+        mel = AugmentMelSTFT(freqm=0, timem=0).to(DEV).train()
+    opt = opt_for(m)
+    kw = dict(teacher_preds=tlogits, fname_to_index=f2i, kd_lambda=0.1, mixup_alpha=0.3)
+    return m, opt, (KDTrainer(m, mel, opt, **kw) if tag == "eager" else GraphedKDTrainer(m, mel, opt, B, L, **kw))
+
+
+def _kd_teacher():
+    g = torch.Generator().manual_seed(5)
+    return torch.randn(40, 527, generator=g) * 2 - 5, {"syn%07d" % i: i % 40 for i in range(0, 30, 2)}
+
+
+def _assert_trainers_agree(le, lg, pe, pg):
+    # the tolerances of test_graphed_kd_trainer_follows_the_eager_trainer
+    assert all(abs(a - b) < 2e-5 * max(1.0, abs(a)) for a, b in zip(le, lg)), (le, lg)
+    d = (pe - pg).abs()
+    frac = float((d > 1e-4).float().mean())
+    assert float(d.max()) <= 6.1e-3 and frac < 0.02, (float(d.max()), frac)
+
+
+def test_graphed_kd_trainer_with_fused_adam_follows_the_eager_trainer():
+    """train_dp's default: GraphedKDTrainer with FusedAdam(capturable=True, tensor lr) - the capture's warm-up steps create
+    the optimizer state and its step counter, which the trainer must put back to zero - against the eager KDTrainer."""
+    B, L = 6, 32000
+    tlogits, f2i = _kd_teacher()
+    res = {}
+    for tag in ("eager", "graph"):
+        m, opt, tr = _kd_trainer(tag, _fused_adam, tlogits, f2i, B, L)
+        torch.manual_seed(11); np.random.seed(11)
+        losses = [float(tr.step(*_kd_batch(s, B, L))) for s in range(3)]
+        torch.cuda.synchronize()
+        res[tag] = (losses, torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu(), tr.epoch_stats())
+        assert {float(opt.state[p]["step"]) for p in m.parameters()} == {3.0}, tag
+    _assert_trainers_agree(res["eager"][0], res["graph"][0], res["eager"][1], res["graph"][1])
+    se, sg = res["eager"][2], res["graph"][2]
+    assert all(abs(se[k] - sg[k]) < 2e-5 * max(1.0, abs(se[k])) for k in se), (se, sg)
+
+
+def test_graphed_kd_trainer_with_fused_adam_resumes_from_a_checkpoint():
+    """4 graphed steps with a checkpoint (model + optimizer state, torch.save) taken after the second; a new model, FusedAdam
+    and trainer (whose constructor has already captured its step) load it and take steps 3 and 4: the same losses and
+    parameters as the uninterrupted run.  (Both continue from the one checkpoint: two uninterrupted runs differ already, by
+    the round-off of the atomics in backward that Adam turns into +-lr moves, more than the trainer tolerance by step 4.)"""
+    B, L = 6, 32000
+    tlogits, f2i = _kd_teacher()
+    m, opt, tr = _kd_trainer("graph", _fused_adam, tlogits, f2i, B, L)
+    torch.manual_seed(11); np.random.seed(11)
+    full = [float(tr.step(*_kd_batch(s, B, L))) for s in range(2)]
+    buf = io.BytesIO()
+    torch.save(dict(model=m.state_dict(), opt=opt.state_dict()), buf)
+    rng = torch.get_rng_state(), np.random.get_state()
+    full += [float(tr.step(*_kd_batch(s, B, L))) for s in range(2, 4)]
+    torch.cuda.synchronize()
+    p_full = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu()
+    del m, opt, tr
+
+    m, opt, tr = _kd_trainer("graph", _fused_adam, tlogits, f2i, B, L)
+    buf.seek(0)
+    ck = torch.load(buf, weights_only=False)
+    m.load_state_dict(ck["model"])
+    opt.load_state_dict(ck["opt"])
+    for i, p in enumerate(m.parameters()):                # the captured step's own buffers now hold the checkpoint
+        for k in ("exp_avg", "exp_avg_sq"):
+            assert torch.equal(opt.state[p][k].cpu(), ck["opt"]["state"][i][k].cpu()), (i, k)
+        assert float(opt.state[p]["step"]) == 2.0
+    torch.set_rng_state(rng[0]); np.random.set_state(rng[1])
+    part = [float(tr.step(*_kd_batch(s, B, L))) for s in range(2, 4)]
+    torch.cuda.synchronize()
+    p_part = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu()
+    _assert_trainers_agree(full[2:], part, p_full, p_part)
+    assert {float(opt.state[p]["step"]) for p in m.parameters()} == {4.0}
