@@ -42,6 +42,28 @@ __global__ __launch_bounds__(256) void ctx_pool_kernel(const float* __restrict__
     out[(size_t)(F + t) * ls] = (s_col[t] + s_col[T + t] + s_col[2 * T + t] + s_col[3 * T + t]) / (float)F;
 }
 
+// the same without LDS, for planes whose [4][T] column partials do not fit it (T > 4096: block 0 of a clip longer than
+// ~82 s): the row means as above, then one thread per column walks the rows (a second, coalesced pass over the plane)
+__global__ __launch_bounds__(256) void ctx_pool_wide_kernel(const float* __restrict__ x, float* __restrict__ seq,
+                                                            int C, int F, int T, int cm, int B) {
+  const int plane = blockIdx.x, b = plane / C, c = plane % C;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float* xp = x + (size_t)plane * F * T;
+  float* out = cm ? seq + ((size_t)c * B + b) * (F + T) : seq + (size_t)b * (F + T) * C + c;
+  const size_t ls = cm ? 1 : (size_t)C;
+  for (int f = wv; f < F; f += 4) {
+    float rs = 0.0f;
+    for (int t = lane; t < T; t += 64) rs += xp[(size_t)f * T + t];
+    rs = eat::wave_sum(rs);
+    if (lane == 0) out[(size_t)f * ls] = rs / (float)T;
+  }
+  for (int t = threadIdx.x; t < T; t += 256) {
+    float cs = 0.0f;
+    for (int f = 0; f < F; ++f) cs += xp[(size_t)f * T + t];
+    out[(size_t)(F + t) * ls] = cs / (float)F;
+  }
+}
+
 // out[b, n] = gscale[n / group] * sum_k att[b,k] * bank[k, n]
 __global__ __launch_bounds__(256) void dyn_aggregate_kernel(const float* __restrict__ bank, const float* __restrict__ att,
                                                             const float* __restrict__ gscale, float* __restrict__ out,
@@ -214,18 +236,22 @@ __global__ __launch_bounds__(256) void dyn_pw_pack_bf16_kernel(const float* __re
 }
 
 // backward of ctx_pool: dx[b,c,f,t] = dseq[b,f,c]/T + dseq[b,F+t,c]/F  (+ add[b,c,f,t])
+// LDS: the (F + T) scaled gradients; LDS == false (they do not fit): read from dseq at every element
+template <bool LDS>
 __global__ __launch_bounds__(256) void ctx_pool_bwd_kernel(const float* __restrict__ dseq, const float* __restrict__ add,
                                                            float* __restrict__ dx, int C, int F, int T, int cm, int B) {
   extern __shared__ float s_g[];                         // [F + T]
   const int plane = blockIdx.x, b = plane / C, c = plane % C;
   const float* g = cm ? dseq + ((size_t)c * B + b) * (F + T) : dseq + (size_t)b * (F + T) * C + c;
   const size_t ls = cm ? 1 : (size_t)C;
-  for (int i = threadIdx.x; i < F + T; i += 256) s_g[i] = g[(size_t)i * ls] / (float)(i < F ? T : F);
-  __syncthreads();
+  if constexpr (LDS) {
+    for (int i = threadIdx.x; i < F + T; i += 256) s_g[i] = g[(size_t)i * ls] / (float)(i < F ? T : F);
+    __syncthreads();
+  }
   const size_t base = (size_t)plane * F * T;
   for (int e = threadIdx.x; e < F * T; e += 256) {
     const int f = e / T, t = e - f * T;
-    float v = s_g[f] + s_g[F + t];
+    float v = LDS ? s_g[f] + s_g[F + t] : g[(size_t)f * ls] / (float)T + g[(size_t)(F + t) * ls] / (float)F;
     if (add) v += add[base + e];
     dx[base + e] = v;
   }
@@ -260,11 +286,13 @@ __global__ __launch_bounds__(256) void dyrelu_ca_bwd_kernel(const float* __restr
                                                             const float* __restrict__ coef, const float* __restrict__ gf,
                                                             const float* __restrict__ gt, float* __restrict__ dv,
                                                             float* __restrict__ dcoef, float* __restrict__ dgf,
-                                                            float* __restrict__ dgt, int C, int Fo, int To) {
-  extern __shared__ float s_m[];                         // [Fo + To] sigmoids, [4][To] column partials, [16] coef partials
+                                                            float* __restrict__ dgt, int C, int Fo, int To, int ncol) {
+  // [Fo + To] sigmoids, [ncol][To] column partials, [16] coef partials.  ncol = 4: one row of partials per wave; ncol = 1
+  // (wide planes, where four rows would not fit LDS): one row shared by the four waves, accumulated with LDS atomics
+  extern __shared__ float s_m[];
   float* s_g = s_m;
   float* s_col = s_m + Fo + To;
-  float* s_cf = s_col + 4 * To;
+  float* s_cf = s_col + ncol * To;
   const int plane = blockIdx.x, bb = plane / C, c = plane % C;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float av = a ? a[c] : 1.0f, bv = a ? b[c] : 0.0f;
@@ -273,11 +301,11 @@ __global__ __launch_bounds__(256) void dyrelu_ca_bwd_kernel(const float* __restr
     const float g = i < Fo ? gf[((size_t)bb * Fo + i) * C + c] : gt[((size_t)bb * To + (i - Fo)) * C + c];
     s_g[i] = 1.0f / (1.0f + expf(-g));
   }
-  for (int i = threadIdx.x; i < 4 * To; i += 256) s_col[i] = 0.0f;
+  for (int i = threadIdx.x; i < ncol * To; i += 256) s_col[i] = 0.0f;
   __syncthreads();
   const size_t base = (size_t)plane * Fo * To;
   float da1 = 0.f, da2 = 0.f, db1 = 0.f, db2 = 0.f;
-  float* mycol = s_col + wv * To;
+  float* mycol = s_col + (ncol == 4 ? wv * To : 0);
   for (int f = wv; f < Fo; f += 4) {
     const float af = s_g[f];
     float rs = 0.0f;
@@ -293,7 +321,8 @@ __global__ __launch_bounds__(256) void dyrelu_ca_bwd_kernel(const float* __restr
       dv[e] = dm * (sel ? cf.x : cf.y);
       if (sel) { da1 = fmaf(dm, v, da1); db1 += dm; } else { da2 = fmaf(dm, v, da2); db2 += dm; }
       rs = fmaf(d * m, at, rs);                 // d out / d af summed over t
-      mycol[t] = fmaf(d * m, af, mycol[t]);     // d out / d at summed over this wave's rows
+      if (ncol == 4) mycol[t] = fmaf(d * m, af, mycol[t]);     // d out / d at summed over this wave's rows
+      else atomicAdd(mycol + t, d * m * af);
     }
     rs = eat::wave_sum(rs);
     if (lane == 0) dgf[((size_t)bb * Fo + f) * C + c] = rs * af * (1.0f - af);
@@ -303,7 +332,8 @@ __global__ __launch_bounds__(256) void dyrelu_ca_bwd_kernel(const float* __restr
   __syncthreads();
   for (int t = threadIdx.x; t < To; t += 256) {
     const float at = s_g[Fo + t];
-    dgt[((size_t)bb * To + t) * C + c] = (s_col[t] + s_col[To + t] + s_col[2 * To + t] + s_col[3 * To + t]) * at * (1.0f - at);
+    const float cs = ncol == 4 ? s_col[t] + s_col[To + t] + s_col[2 * To + t] + s_col[3 * To + t] : s_col[t];
+    dgt[((size_t)bb * To + t) * C + c] = cs * at * (1.0f - at);
   }
   if (threadIdx.x < 4)
     dcoef[(size_t)plane * 4 + threadIdx.x] = s_cf[threadIdx.x] + s_cf[4 + threadIdx.x] + s_cf[8 + threadIdx.x] + s_cf[12 + threadIdx.x];
@@ -505,16 +535,23 @@ __device__ __forceinline__ float group_sum(float v) {
 // A bf16 row of odd width starts on a 2-byte boundary on every other row: the slot access is ONE dword at a 2-byte aligned
 // address (gfx9 global memory handles it); the last slot of an odd-width row owns one column only - its load is moved back by
 // one element and takes the high half (so that it never reaches past the tensor), its store is a 2-byte store.
+// one_col (To == 1, uniform over the launch): every row is one column and the element before a row may lie before the
+// tensor itself (row 0 of plane 0), so the load is a 2-byte load instead.
 template <typename ST> struct DyIo;
 template <> struct DyIo<float> {
   static constexpr int CW = 1;
-  static __device__ __forceinline__ void ld(const float* p, bool, float (&v)[1]) { v[0] = *p; }
+  static __device__ __forceinline__ void ld(const float* p, bool, bool, float (&v)[1]) { v[0] = *p; }
   static __device__ __forceinline__ void st(float* p, bool, bool ok0, const float (&v)[1]) { if (ok0) *p = v[0]; }
 };
 template <> struct DyIo<eat::bf16_t> {
   static constexpr int CW = 2;
   // p: address of the slot's first column; part: the second column does not exist
-  static __device__ __forceinline__ void ld(const eat::bf16_t* p, bool part, float (&v)[2]) {
+  static __device__ __forceinline__ void ld(const eat::bf16_t* p, bool part, bool one_col, float (&v)[2]) {
+    if (one_col) {
+      v[0] = (float)*p;
+      v[1] = 0.0f;
+      return;
+    }
     const unsigned w = *reinterpret_cast<const unsigned*>(part ? p - 1 : p);
     v[0] = part ? eat::bf_hi(w) : eat::bf_lo(w);
     v[1] = part ? 0.0f : eat::bf_hi(w);
@@ -567,7 +604,7 @@ __global__ __launch_bounds__(256) void dyrelu_ca_fwd2_kernel(const ST* __restric
       const int f = f0 + r < Fo ? f0 + r : Fo - 1;
       af[r] = sigm(gfp[f]);
 #pragma unroll
-      for (int j = 0; j < NC; ++j) DyIo<ST>::ld(zp + (size_t)f * To + tc[j], part[j] && CW * (l + LPP * j) < To, v[r][j]);
+      for (int j = 0; j < NC; ++j) DyIo<ST>::ld(zp + (size_t)f * To + tc[j], part[j] && CW * (l + LPP * j) < To, To == 1, v[r][j]);
     }
 #pragma unroll
     for (int r = 0; r < RU; ++r) {
@@ -638,8 +675,8 @@ __global__ __launch_bounds__(256) void dyrelu_ca_bwd2_kernel(const ST* __restric
       for (int j = 0; j < NC; ++j) {
         const size_t e = base + (size_t)f * To + tc[j];
         const bool pt = part[j] && ok[j][0];
-        DyIo<ST>::ld(z + e, pt, zv[r][j]);
-        DyIo<ST>::ld(dout + e, pt, dd[r][j]);
+        DyIo<ST>::ld(z + e, pt, To == 1, zv[r][j]);
+        DyIo<ST>::ld(dout + e, pt, To == 1, dd[r][j]);
       }
     }
 #pragma unroll
@@ -724,21 +761,26 @@ __global__ __launch_bounds__(256) void dyn_bn_bwd_combine_kernel(const float* __
 
 }  // namespace
 
-extern "C" int eat_ctx_pool(const float* x, float* seq, int B, int C, int F, int T, eat_stream_t stream) {
+static constexpr size_t kLdsMax = 64 * 1024;           // LDS of one block without an opt-in
+
+static int ctx_pool_impl(const float* x, float* seq, int B, int C, int F, int T, int cm, eat_stream_t stream) {
   eat::clear_stale_error();
+  if (B < 1 || C < 1 || F < 1 || T < 1) return eat::fail(EAT_EINVAL, "eat_ctx_pool: bad shape");
   const size_t smem = (size_t)4 * T * sizeof(float);
-  if (smem > 64 * 1024) return eat::fail(EAT_EINVAL, "eat_ctx_pool: T=%d too wide", T);
-  hipLaunchKernelGGL(ctx_pool_kernel, dim3(B * C), dim3(256), smem, (hipStream_t)stream, x, seq, C, F, T, 0, B);
-  return eat::check_launch("eat_ctx_pool");
+  if (smem <= kLdsMax)
+    hipLaunchKernelGGL(ctx_pool_kernel, dim3(B * C), dim3(256), smem, (hipStream_t)stream, x, seq, C, F, T, cm, B);
+  else
+    hipLaunchKernelGGL(ctx_pool_wide_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, x, seq, C, F, T, cm, B);
+  return eat::check_launch(cm ? "eat_ctx_pool_cm" : "eat_ctx_pool");
+}
+
+extern "C" int eat_ctx_pool(const float* x, float* seq, int B, int C, int F, int T, eat_stream_t stream) {
+  return ctx_pool_impl(x, seq, B, C, F, T, 0, stream);
 }
 
 // channel-major form: seq (C, B, F+T) (see the kernel)
 extern "C" int eat_ctx_pool_cm(const float* x, float* seq, int B, int C, int F, int T, eat_stream_t stream) {
-  eat::clear_stale_error();
-  const size_t smem = (size_t)4 * T * sizeof(float);
-  if (smem > 64 * 1024) return eat::fail(EAT_EINVAL, "eat_ctx_pool_cm: T=%d too wide", T);
-  hipLaunchKernelGGL(ctx_pool_kernel, dim3(B * C), dim3(256), smem, (hipStream_t)stream, x, seq, C, F, T, 1, B);
-  return eat::check_launch("eat_ctx_pool_cm");
+  return ctx_pool_impl(x, seq, B, C, F, T, 1, stream);
 }
 
 extern "C" int eat_dyn_aggregate(const float* bank, const float* att, const float* gscale, float* out, int B, int K,
@@ -813,26 +855,35 @@ extern "C" int eat_dyn_pw_pack_b16(const float* bank, const float* att, void* wp
   return dyn_pw_pack_bf16_impl(bank, att, wp, B, K, Co, Ci, trans ? 1 : 0, stream, 1);
 }
 
+static int ctx_pool_bwd_impl(const float* dseq, const float* add, float* dx, int B, int C, int F, int T, int cm,
+                             eat_stream_t stream) {
+  eat::clear_stale_error();
+  if (B < 1 || C < 1 || F < 1 || T < 1) return eat::fail(EAT_EINVAL, "eat_ctx_pool_bwd: bad shape");
+  const size_t smem = (size_t)(F + T) * sizeof(float);
+  if (smem <= kLdsMax)
+    hipLaunchKernelGGL(ctx_pool_bwd_kernel<true>, dim3(B * C), dim3(256), smem, (hipStream_t)stream, dseq, add, dx, C, F, T, cm, B);
+  else
+    hipLaunchKernelGGL(ctx_pool_bwd_kernel<false>, dim3(B * C), dim3(256), 0, (hipStream_t)stream, dseq, add, dx, C, F, T, cm, B);
+  return eat::check_launch(cm ? "eat_ctx_pool_cm_bwd" : "eat_ctx_pool_bwd");
+}
+
 extern "C" int eat_ctx_pool_bwd(const float* dseq, const float* add, float* dx, int B, int C, int F, int T,
                                 eat_stream_t stream) {
-  eat::clear_stale_error();
-  hipLaunchKernelGGL(ctx_pool_bwd_kernel, dim3(B * C), dim3(256), (size_t)(F + T) * sizeof(float), (hipStream_t)stream,
-                     dseq, add, dx, C, F, T, 0, B);
-  return eat::check_launch("eat_ctx_pool_bwd");
+  return ctx_pool_bwd_impl(dseq, add, dx, B, C, F, T, 0, stream);
 }
 
 extern "C" int eat_ctx_pool_cm_bwd(const float* dseq, const float* add, float* dx, int B, int C, int F, int T,
                                    eat_stream_t stream) {
-  eat::clear_stale_error();
-  hipLaunchKernelGGL(ctx_pool_bwd_kernel, dim3(B * C), dim3(256), (size_t)(F + T) * sizeof(float), (hipStream_t)stream,
-                     dseq, add, dx, C, F, T, 1, B);
-  return eat::check_launch("eat_ctx_pool_cm_bwd");
+  return ctx_pool_bwd_impl(dseq, add, dx, B, C, F, T, 1, stream);
 }
 
 extern "C" int eat_dyrelu_ca_fwd(const float* z, const float* a, const float* b, const float* coef, const float* gate_f,
                                  const float* gate_t, float* out, int B, int C, int Fo, int To, eat_stream_t stream) {
   eat::clear_stale_error();
-  hipLaunchKernelGGL(dyrelu_ca_fwd_kernel, dim3(B * C), dim3(256), (size_t)(Fo + To) * sizeof(float),
+  if (B < 1 || C < 1 || Fo < 1 || To < 1) return eat::fail(EAT_EINVAL, "eat_dyrelu_ca_fwd: bad shape");
+  const size_t smem = (size_t)(Fo + To) * sizeof(float);
+  if (smem > kLdsMax) return eat::fail(EAT_EINVAL, "eat_dyrelu_ca_fwd: Fo + To = %d gates do not fit LDS", Fo + To);
+  hipLaunchKernelGGL(dyrelu_ca_fwd_kernel, dim3(B * C), dim3(256), smem,
                      (hipStream_t)stream, z, a, b, coef, gate_f, gate_t, out, C, Fo, To);
   return eat::check_launch("eat_dyrelu_ca_fwd");
 }
@@ -841,9 +892,13 @@ extern "C" int eat_dyrelu_ca_bwd(const float* dout, const float* z, const float*
                                  const float* gate_f, const float* gate_t, float* dv, float* dcoef, float* dgate_f,
                                  float* dgate_t, int B, int C, int Fo, int To, eat_stream_t stream) {
   eat::clear_stale_error();
-  const size_t smem = (size_t)(Fo + To + 4 * To + 16) * sizeof(float);
+  if (B < 1 || C < 1 || Fo < 1 || To < 1) return eat::fail(EAT_EINVAL, "eat_dyrelu_ca_bwd: bad shape");
+  int ncol = 4;                                          // column partials per wave; one shared row on wide planes
+  if ((size_t)(Fo + To + ncol * To + 16) * sizeof(float) > kLdsMax) ncol = 1;
+  const size_t smem = (size_t)(Fo + To + ncol * To + 16) * sizeof(float);
+  if (smem > kLdsMax) return eat::fail(EAT_EINVAL, "eat_dyrelu_ca_bwd: Fo=%d To=%d do not fit LDS", Fo, To);
   hipLaunchKernelGGL(dyrelu_ca_bwd_kernel, dim3(B * C), dim3(256), smem, (hipStream_t)stream, dout, z, a, b, coef, gate_f,
-                     gate_t, dv, dcoef, dgate_f, dgate_t, C, Fo, To);
+                     gate_t, dv, dcoef, dgate_f, dgate_t, C, Fo, To, ncol);
   return eat::check_launch("eat_dyrelu_ca_bwd");
 }
 

@@ -314,8 +314,9 @@ class DyMN(nn.Module):
                 if stride > 1:
                     h_cf, h_ct = _pool3(h_cf, stride), _pool3(h_ct, stride)
                 Fo, To = h_cf.shape[1], h_ct.shape[1]
-                g_cf = ops.linear(h_cf.reshape(B * Fo, H), cg.conv_f.weight.flatten(1), cg.conv_f.bias, ops.ACT_NONE)
-                g_ct = ops.linear(h_ct.reshape(B * To, H), cg.conv_t.weight.flatten(1), cg.conv_t.bias, ops.ACT_NONE)
+                # (contiguous: with one row or column the reshape of the slice is a view with the sequence's strides)
+                g_cf = ops.linear(h_cf.reshape(B * Fo, H).contiguous(), cg.conv_f.weight.flatten(1), cg.conv_f.bias, ops.ACT_NONE)
+                g_ct = ops.linear(h_ct.reshape(B * To, H).contiguous(), cg.conv_t.weight.flatten(1), cg.conv_t.bias, ops.ACT_NONE)
         # ---- expand (dynamic 1x1)
         if blk.has_expand:
             if blk.no_dyconv:

@@ -38,6 +38,55 @@ def test_ctx_pool(B, C, F_, T):
     assert _rel(ops.ctx_pool(x.to(DEV)), ref) < 2e-6
 
 
+# T = 1; T = 4096 (the last width whose [4][T] column partials fit LDS) and past it (block 0 of a clip longer than ~82 s);
+# F + T > 16384 (the backward's gradient table no longer fits LDS either)
+@pytest.mark.parametrize("B,C,F_,T", [(3, 5, 7, 1), (2, 3, 1, 9), (2, 3, 5, 4096), (2, 3, 5, 4097), (1, 4, 64, 4500),
+                                      (1, 2, 3, 16500)])
+def test_ctx_pools_and_their_backward_match_fp64(B, C, F_, T):
+    """ctx_pool / ctx_pool_cm and both backward forms (the channel-major one with the main path's dx added) against
+    fp64 autograd of the two means."""
+    from efficientat_amd.dymn_train import CtxPool
+    x = _rand(B, C, F_, T, seed=1)
+    xr = x.double().requires_grad_(True)
+    ref = torch.cat([xr.mean(dim=3), xr.mean(dim=2)], dim=2)                      # (B, C, F+T)
+    L = F_ + T
+    dseq = _rand(B, L, C, seed=2)
+    ref.backward(dseq.double().transpose(1, 2))
+    xd = x.to(DEV).requires_grad_(True)
+    seq = CtxPool.apply(xd)
+    assert seq.shape == (B, L, C) and _rel(seq, ref.detach().transpose(1, 2)) < 2e-6
+    seq.backward(dseq.to(DEV))
+    assert _rel(xd.grad, xr.grad) < 2e-6
+    cm = ops.ctx_pool_cm(x.to(DEV))
+    assert _rel(cm.view(C, B, L), ref.detach().permute(1, 0, 2)) < 2e-6
+    add = _rand(B, C, F_, T, seed=3)
+    dcm = dseq.permute(2, 0, 1).contiguous().view(1, C, B * L, 1)
+    dx = ops.ctx_pool_cm_bwd(dcm.to(DEV), (B, C, F_, T), add=add.to(DEV))
+    assert _rel(dx, xr.grad + add.double()) < 2e-6
+
+
+@pytest.mark.parametrize("H,B,F_,T,stride", [(5, 3, 7, 9, 2), (4, 2, 1, 1, 2), (3, 2, 5, 1, 1), (6, 3, 5, 125, 2),
+                                             (4, 3, 3, 63, 2), (3, 2, 8, 4097, 1), (2, 3, 64, 4500, 2)])
+def test_ctx_split_and_backward_match_fp64(H, B, F_, T, stride):
+    """ctx_split (AvgPool(3, stride 2, pad 1) of both halves for stride 2, odd lengths included; the mean h_c) and its
+    backward against fp64 autograd."""
+    L = F_ + T
+    g = _rand(H, B, L, seed=1)
+    gr = g.double().requires_grad_(True)
+    pool = (lambda r: r) if stride == 1 else (lambda r: F.avg_pool1d(r, 3, 2, 1, count_include_pad=True))
+    hcf, hct, hc = pool(gr[..., :F_]), pool(gr[..., F_:]), gr.mean(-1).t()
+    Fo, To = hcf.shape[-1], hct.shape[-1]
+    dcf, dct, dc = _rand(H, B, Fo, seed=2), _rand(H, B, To, seed=3), _rand(B, H, seed=4)
+    torch.autograd.backward([hcf, hct, hc], [dcf.double(), dct.double(), dc.double()])
+    gcf, gct, gc = ops.ctx_split(g.view(1, H, B * L, 1).to(DEV), B, F_, T, stride)
+    assert gcf.shape == (1, H, B * Fo, 1) and gct.shape == (1, H, B * To, 1)
+    assert _rel(gcf.view(H, B, Fo), hcf.detach()) < 1e-6 and _rel(gct.view(H, B, To), hct.detach()) < 1e-6
+    assert _rel(gc, hc.detach()) < 1e-6
+    dg = ops.ctx_split_bwd(dcf.reshape(1, H, B * Fo, 1).to(DEV), dct.reshape(1, H, B * To, 1).to(DEV), dc.to(DEV), H, B, F_, T,
+                           stride)
+    assert _rel(dg.view(H, B, L), gr.grad) < 1e-6
+
+
 def test_dyn_aggregate_and_pack():
     B, K, Co, Ci = 3, 4, 40, 24
     bank, att = _rand(K, Co * Ci, seed=1), torch.softmax(_rand(B, K, seed=2), dim=-1)
@@ -55,7 +104,10 @@ def test_dyn_aggregate_and_pack():
 
 
 @pytest.mark.parametrize("B,C,F_,T,k,s", [(2, 32, 64, 500, 3, 1), (2, 48, 32, 250, 5, 2), (3, 240, 16, 125, 3, 2),
-                                          (3, 96, 8, 63, 5, 1), (4, 160, 4, 32, 5, 1)])
+                                          (3, 96, 8, 63, 5, 1), (4, 160, 4, 32, 5, 1),
+                                          # planes off the 128-mel / 10 s grid: 0.3 s clips (4x1, 8x2), 40 and 64 mels, 11 s
+                                          (3, 16, 4, 1, 5, 1), (3, 24, 8, 2, 3, 1), (2, 24, 5, 125, 3, 1), (2, 24, 3, 63, 5, 1),
+                                          (2, 24, 2, 31, 5, 1), (2, 8, 64, 550, 3, 1)])
 def test_dw_conv_dyn(B, C, F_, T, k, s):
     x, w = _rand(B, C, F_, T, seed=1), _rand(B, C, k, k, seed=2, scale=0.3)
     bias, coef = _rand(C, seed=3, scale=0.1), _rand(B, C, 4, seed=4)
@@ -126,6 +178,83 @@ def test_dyrelu_coordatt_backward():
         assert _rel(a.grad, b.grad) < 2e-5
 
 
+def _dyrelu_ca_fp64(z, a, b, coef, gf, gt, dout):
+    """fp64 autograd of DyReLU-B * CoordAtt on v = a z + b: gates position-major (B, L, C).  -> out, (dv, dcoef, dgf, dgt)"""
+    C = z.shape[1]
+    cr, gfr, gtr = (t.double().clone().requires_grad_(True) for t in (coef, gf, gt))
+    v = (z.double() * a.double().view(1, C, 1, 1) + b.double().view(1, C, 1, 1)).requires_grad_(True)
+    c = cr[:, :, None, None, :]
+    ref = torch.maximum(v * c[..., 0] + c[..., 2], v * c[..., 1] + c[..., 3])
+    ref = ref * torch.sigmoid(gfr.permute(0, 2, 1))[:, :, :, None] * torch.sigmoid(gtr.permute(0, 2, 1))[:, :, None, :]
+    ref.backward(dout.double())
+    return ref.detach(), (v.grad, cr.grad, gfr.grad, gtr.grad)
+
+
+DYRELU2_WIDTHS = [1, 2, 3, 15, 16, 17, 31, 33, 64, 65, 255, 257, 511, 512]     # every cut of EAT_DYRELU2_DISPATCH and its odd edges
+
+
+@pytest.mark.parametrize("To", DYRELU2_WIDTHS)
+def test_dyrelu_ca2_edge_widths_match_fp64(To):
+    """eat_dyrelu_ca_fwd2 / _bwd2 (fp32 storage) at every lane layout of the dispatch, with Fo of 1, 2, 3 and 5 rows (the
+    clamped last row group of the RU-row unroll) and a plane count that leaves the last wave part-filled."""
+    B, C = 2, 37
+    for Fo in (1, 2, 3, 5):
+        z, coef = _rand(B, C, Fo, To, seed=1), _rand(B, C, 4, seed=2)
+        gf, gt, dout = _rand(B, Fo, C, seed=3), _rand(B, To, C, seed=4), _rand(B, C, Fo, To, seed=5)
+        a, b = _rand(C, seed=6).abs() + 0.5, _rand(C, seed=7)
+        ref, (gv, gc, ggf, ggt) = _dyrelu_ca_fp64(z, a, b, coef, gf, gt, dout)
+        zd, cd, ad, bd, dd = (t.to(DEV) for t in (z, coef, a, b, dout))
+        gfd, gtd = gf.permute(2, 0, 1).contiguous().to(DEV), gt.permute(2, 0, 1).contiguous().to(DEV)
+        out = ops.dyrelu_ca_fwd2(zd, ad, bd, cd, gfd, gtd)
+        assert _rel(out, ref) < 5e-6, Fo
+        dv, dcoef, dgf, dgt, bnpart = ops.dyrelu_ca_bwd2(dd, zd, ad, bd, cd, gfd, gtd)
+        assert _rel(dv, gv) < 2e-5 and _rel(dcoef, gc) < 2e-5, Fo
+        assert _rel(dgf, ggf.permute(2, 0, 1)) < 2e-5 and _rel(dgt, ggt.permute(2, 0, 1)) < 2e-5, Fo
+        assert _rel(bnpart[..., 0], gv.sum((2, 3))) < 2e-5 and _rel(bnpart[..., 1], (gv * z.double()).sum((2, 3))) < 2e-5, Fo
+
+
+def test_dyrelu_ca2_refuses_rows_wider_than_512():
+    from efficientat_amd._lib import EatHipError
+    z, coef = torch.zeros(1, 2, 3, 513, device=DEV), torch.zeros(1, 2, 4, device=DEV)
+    gf, gt = torch.zeros(2, 1, 3, device=DEV), torch.zeros(2, 1, 513, device=DEV)
+    with pytest.raises(EatHipError):
+        ops.dyrelu_ca_fwd2(z, None, None, coef, gf, gt)
+    with pytest.raises(EatHipError):
+        ops.dyrelu_ca_bwd2(z, z, None, None, coef, gf, gt)
+
+
+@pytest.mark.parametrize("Fo,To", [(2, 550), (3, 2250), (2, 4500), (1, 10000)])
+def test_dyrelu_coordatt_wide_rows(Fo, To):
+    """The plane-per-block kernels (eat_dyrelu_ca_fwd / _bwd) of the unfused path on the rows of long clips: 4500 columns
+    (block 0 of 90 s) no longer fit one row of column partials per wave in LDS.  Past what fits at all, a clean EatHipError."""
+    from efficientat_amd._lib import EatHipError
+    from efficientat_amd.dymn_train import DyReluCoordAtt
+    B, C = 2, 3
+    v, coef = _rand(B, C, Fo, To, seed=1), _rand(B, C, 4, seed=2)
+    gf, gt, dout = _rand(B, Fo, C, seed=3), _rand(B, To, C, seed=4), _rand(B, C, Fo, To, seed=5)
+    one, zero = torch.ones(C), torch.zeros(C)
+    ref, grads = _dyrelu_ca_fp64(v, one, zero, coef, gf, gt, dout)
+    td = [t.to(DEV).requires_grad_(True) for t in (v, coef, gf, gt)]
+    out = DyReluCoordAtt.apply(*td)
+    assert _rel(out, ref) < 5e-6
+    if To > 8000:                                  # (Fo + 2 To + 16) floats of LDS: more than 64 KB
+        with pytest.raises(EatHipError):
+            out.backward(dout.to(DEV))
+        return
+    out.backward(dout.to(DEV))
+    for t, g in zip(td, grads):
+        assert _rel(t.grad, g) < 2e-5
+
+
+def test_dyrelu_coordatt_refuses_gates_that_do_not_fit_lds():
+    from efficientat_amd._lib import EatHipError
+    from efficientat_amd.dymn_train import DyReluCoordAtt
+    v = torch.zeros(1, 1, 1, 17000, device=DEV)
+    with pytest.raises(EatHipError):
+        DyReluCoordAtt.apply(v, torch.zeros(1, 1, 4, device=DEV), torch.zeros(1, 1, 1, device=DEV),
+                             torch.zeros(1, 17000, 1, device=DEV))
+
+
 @pytest.mark.parametrize("B,C,Fo,To", [(3, 24, 8, 63), (3, 7, 4, 32), (2, 5, 16, 125), (2, 6, 32, 250), (1, 3, 64, 500), (2, 9, 5, 20)])
 def test_dyrelu_coordatt_wave_per_plane_forms(B, C, Fo, To):
     """Round-4 forms (channel-major pre-sigmoid gates, one wave per plane, BatchNorm affine on load, BatchNorm-backward sums
@@ -159,7 +288,10 @@ def test_dyrelu_coordatt_wave_per_plane_forms(B, C, Fo, To):
 
 @pytest.mark.parametrize("B,C,Fq,T,k,s,act", [(3, 8, 64, 500, 3, 1, 1), (2, 8, 64, 500, 3, 2, 1), (3, 12, 32, 250, 5, 2, 1),
                                               (5, 20, 16, 125, 5, 1, 2), (3, 24, 16, 125, 3, 2, 2), (5, 20, 8, 63, 3, 1, 2),
-                                              (3, 16, 8, 63, 5, 2, 2), (7, 12, 4, 32, 5, 1, 2), (2, 6, 6, 40, 3, 1, 0)])
+                                              (3, 16, 8, 63, 5, 2, 2), (7, 12, 4, 32, 5, 1, 2), (2, 6, 6, 40, 3, 1, 0),
+                                              # off the 128-mel / 10 s grid: 4x1, 8x2, 5x125, 3x63, 2x31 and 64x550 outputs
+                                              (3, 8, 4, 1, 3, 1, 2), (3, 8, 8, 2, 5, 1, 2), (3, 8, 10, 250, 3, 2, 2),
+                                              (3, 8, 6, 125, 3, 2, 1), (3, 8, 2, 31, 5, 1, 2), (2, 8, 64, 550, 3, 1, 1)])
 def test_dynamic_depthwise_train_kernels(B, C, Fq, T, k, s, act):
     """Round-4 train-mode passes of the dynamic depthwise conv (per-(b,c) taps): forward with the expand BatchNorm +
     activation on load and depth_norm's statistics in the epilogue; merged backward with depth_norm's backward on load -

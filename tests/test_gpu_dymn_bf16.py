@@ -107,7 +107,8 @@ def test_pw_conv_dyn_wgrad_b16(B, Co, Ci, Fq, T, wide_x):
 
 @pytest.mark.parametrize("B,C,Fq,T,k,s,x16", [(2, 8, 64, 500, 3, 1, False), (2, 8, 64, 500, 3, 2, True), (3, 12, 32, 250, 5, 2, True),
                                               (3, 16, 32, 250, 3, 1, True), (3, 24, 16, 125, 5, 1, True), (3, 24, 16, 125, 3, 2, True),
-                                              (4, 40, 8, 63, 3, 1, True), (4, 40, 8, 63, 5, 2, True), (5, 48, 4, 32, 5, 1, True)])
+                                              (4, 40, 8, 63, 3, 1, True), (4, 40, 8, 63, 5, 2, True), (5, 48, 4, 32, 5, 1, True),
+                                              (2, 8, 64, 550, 3, 1, True)])       # block 0 of an 11 s clip
 def test_dynamic_depthwise_train_kernels_b16(B, C, Fq, T, k, s, x16):
     """Dynamic depthwise conv (+ expand BatchNorm / activation on load, statistics) and its merged backward on bf16 storage
     against the fp32 kernels fed the same bf16-representable tensors: outputs equal after rounding, statistics those of the
@@ -180,6 +181,47 @@ def test_dyrelu_coordatt_b16(B, C, Fo, To):
     d = dv16.double()
     assert _rel(bn16[..., 0], d.sum(dim=(2, 3))) < 1e-5 and _rel(bn16[..., 1], (d * z.double()).sum(dim=(2, 3))) < 1e-4
     bn32
+
+
+@pytest.mark.parametrize("To", [1, 2, 3, 15, 16, 17, 31, 33, 64, 65, 255, 257, 511, 512])
+def test_dyrelu_ca2_b16_edge_widths_match_fp64(To):
+    """eat_dyrelu_ca_fwd2_b16 / _bwd2_b16 at every lane layout of the dispatch (a bf16 slot is two columns: odd widths end
+    on a one-column slot, To == 1 is nothing else) and Fo of 1, 2, 3 and 5 rows, against fp64 autograd on the bf16 inputs:
+    stored outputs are the rounding of the fp64 values (up to the fp32 round-off of the kernel's arithmetic, which shows
+    where max(a1 v + b1, a2 v + b2) cancels to near zero), fp32 sums within round-off."""
+    B, C = 2, 37
+    for Fo in (1, 2, 3, 5):
+        z, dout = _r16(_rand(B, C, Fo, To, seed=1)), _r16(_rand(B, C, Fo, To, seed=7))
+        a, b = torch.rand(C, generator=torch.Generator().manual_seed(2)) + 0.5, _rand(C, seed=3, scale=0.2)
+        coef = _rand(B, C, 4, seed=4, scale=0.5) + torch.tensor([1.0, 0.5, 0.0, 0.0])
+        gf, gt = _rand(C, B, Fo, seed=5), _rand(C, B, To, seed=6)                  # channel-major (C, B, L)
+        cr, gfr, gtr = (t.double().clone().requires_grad_(True) for t in (coef, gf, gt))
+        v = (z.double() * a.double().view(1, C, 1, 1) + b.double().view(1, C, 1, 1)).requires_grad_(True)
+        c = cr[:, :, None, None, :]
+        ref = torch.maximum(v * c[..., 0] + c[..., 2], v * c[..., 1] + c[..., 3])
+        ref = ref * torch.sigmoid(gfr.permute(1, 0, 2))[:, :, :, None] * torch.sigmoid(gtr.permute(1, 0, 2))[:, :, None, :]
+        ref.backward(dout.double())
+        zd, dd = z.to(BF).to(DEV), dout.to(BF).to(DEV)
+        args = (a.to(DEV), b.to(DEV), coef.to(DEV), gf.to(DEV), gt.to(DEV))
+        o16 = ops.dyrelu_ca_fwd2(zd, *args)
+        assert o16.dtype == BF
+        _same_after_rounding(o16.cpu(), ref.detach().float(), acc_noise=1e-6)
+        dv16, dc, dgf, dgt, bn = ops.dyrelu_ca_bwd2(dd, zd, *args)
+        assert dv16.dtype == BF
+        _same_after_rounding(dv16.cpu(), v.grad.float(), acc_noise=1e-6)
+        assert _rel(dc, cr.grad) < 2e-5 and _rel(dgf, gfr.grad) < 2e-5 and _rel(dgt, gtr.grad) < 2e-5, Fo
+        d = dv16.double().cpu()
+        assert _rel(bn[..., 0], d.sum(dim=(2, 3))) < 1e-5 and _rel(bn[..., 1], (d * z.double()).sum(dim=(2, 3))) < 1e-5, Fo
+
+
+def test_dyrelu_ca2_b16_refuses_rows_wider_than_512():
+    from efficientat_amd._lib import EatHipError
+    z, coef = torch.zeros(1, 2, 3, 513, device=DEV, dtype=BF), torch.zeros(1, 2, 4, device=DEV)
+    gf, gt = torch.zeros(2, 1, 3, device=DEV), torch.zeros(2, 1, 513, device=DEV)
+    with pytest.raises(EatHipError):
+        ops.dyrelu_ca_fwd2(z, None, None, coef, gf, gt)
+    with pytest.raises(EatHipError):
+        ops.dyrelu_ca_bwd2(z, z, None, None, coef, gf, gt)
 
 
 def test_bn_bwd_apply_b16():
