@@ -148,7 +148,12 @@ SIGNATURES = {
     "eat_adam_multi": [_P, _I, _P, _D, _P, _F, _D, _D, _D, _D, _I, _D, _P],
     "eat_pw_dyn_wgrad_b16_slices": [_I] * 5,
     "eat_pw_conv_dyn_wgrad_b16": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    # ranking metrics of the evaluation (metrics.py)
+    "eat_rank_metrics_ws_bytes": [_I, _I],
+    "eat_rank_metrics": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P],
 }
+
+RESTYPES = {"eat_rank_metrics_ws_bytes": ctypes.c_longlong}   # every other entry point returns int
 
 _lib = None
 
@@ -169,7 +174,7 @@ def lib():
         for name, argtypes in SIGNATURES.items():
             fn = getattr(h, name)
             fn.argtypes = argtypes
-            fn.restype = _I
+            fn.restype = RESTYPES.get(name, _I)
         h.eat_version.restype = _I
         h.eat_pw_stream_mode.argtypes = [_I]
         h.eat_pw_stream_mode.restype = _I

@@ -14,8 +14,13 @@ the epoch's sample list).
 Pipeline per rank: `datasets.audioset.get_full_training_set` (dropin/: the reference's tuple layout) -> DataLoader workers
 -> `DevicePrefetcher` (pinned double buffering, copies on their own stream; `--transport int16` halves the PCIe bytes)
 -> `GraphedKDTrainer` (the whole iteration incl. the bucketed RCCL all-reduce as ONE hipGraph replay; `--no_graph`: the
-eager `KDTrainer`) with `enable_data_parallel`.  Out of scope here: wandb logging, mAP evaluation and
-checkpoint rotation - rank 0 prints one line per epoch and saves `<out>/<model>_epoch_<e>.pt` when `--out` is given.
+eager `KDTrainer`) with `enable_data_parallel`.  Out of scope here: wandb logging and checkpoint rotation -
+rank 0 prints one line per epoch and saves `<out>/<model>_epoch_<e>.pt` when `--out` is given.
+
+Validation (`--eval_every E`): after every E-th epoch (and after the last one when `--max_steps` ends the run early) every
+rank evaluates its shard of the test set and rank 0 reports mAP / ROC / val_loss - the reference's per-epoch `_test`
+(ex_audioset.py:203-216) through `evaluation.evaluate` (metrics on the device, evaluation.py).  `--eval_only --checkpoint
+PATH` evaluates one state dict and prints the JSON line: the reference's `evaluate()` for one model.
 """
 import argparse
 import contextlib
@@ -98,6 +103,12 @@ def parse_args(argv=None):
                         "(precision=16): wide activations / gradients of every block in bf16 in HBM")
     p.add_argument("--out", default=None, help="directory for rank 0's per-epoch state dicts")
     p.add_argument("--json", action="store_true", help="rank 0 prints one JSON line with the run's throughput at the end")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="evaluate on the test set after every E-th epoch (and after the last one when --max_steps ends the run); 0 = never")
+    p.add_argument("--eval_batch_size", type=int, default=None, help="clips per GPU per eval batch (default: --batch_size)")
+    p.add_argument("--eval_dump", default=None, help="directory: rank 0 writes the last evaluation's logits.npy / targets.npy (test-set order)")
+    p.add_argument("--eval_only", action="store_true", help="evaluate --checkpoint once and print the JSON line; no training")
+    p.add_argument("--checkpoint", default=None, help="state dict to load (e.g. one written by --out)")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="process-group backend: nccl = RCCL, one GPU per rank (production); gloo = several ranks may share a GPU "
                         "(tests on a one-GPU box: collectives on device tensors through the host, eager trainer only)")
@@ -126,15 +137,29 @@ def build(args, dev):
     return model, mel
 
 
+def _evaluate(args, model, mel, test_set, rank, world, dev):
+    from .evaluation import evaluate
+    res = evaluate(model, mel, test_set, args.eval_batch_size or args.batch_size, rank, world, dev,
+                   num_workers=min(args.num_workers, 4), keep_outputs=bool(args.eval_dump))
+    logits, targets = res.pop("logits", None), res.pop("targets", None)
+    if args.eval_dump and rank == 0:
+        os.makedirs(args.eval_dump, exist_ok=True)
+        np.save(os.path.join(args.eval_dump, "logits.npy"), logits.cpu().numpy())
+        np.save(os.path.join(args.eval_dump, "targets.npy"), targets.cpu().numpy())
+    return res
+
+
 def main(argv=None):
     args = parse_args(argv)
+    if args.eval_only and not args.checkpoint:
+        raise SystemExit("--eval_only needs --checkpoint PATH")
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
     if not torch.cuda.is_available():
         raise SystemExit("efficientat_amd.train_dp needs a GPU per rank: the package has no CPU path")
     if args.backend == "gloo":
         local %= torch.cuda.device_count()                                    # ranks share the visible GPUs
-        if not args.no_graph and world > 1:
+        if not args.no_graph and world > 1 and not args.eval_only:
             raise SystemExit("--backend gloo cannot be captured into a hipGraph (host-side collectives): add --no_graph")
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -158,6 +183,23 @@ def main(argv=None):
     model, mel = build(args, dev)
     if world > 1:
         enable_data_parallel(model)                                           # ... and rank 0's broadcast anyway, like DDP
+    if args.checkpoint:
+        model.load_state_dict(torch.load(args.checkpoint, map_location=dev))
+    test_set = None
+    if args.eval_every or args.eval_only:
+        test_set = _quiet(audioset.get_test_set, resample_rate=32000)
+    if args.eval_only:
+        ev = _evaluate(args, model, mel, test_set, rank, world, dev)
+        if rank == 0:
+            print(f"[train_dp] eval: mAP {ev['mAP']:.5f}, ROC {ev['ROC']:.5f}, val_loss {ev['val_loss']:.5f} over "
+                  f"{ev['n_clips']} clips, {ev['clips_per_s']:.0f} clips/s", file=sys.stderr, flush=True)
+            if args.json:
+                print(json.dumps({"what": "efficientat_amd.train_dp", "mode": "eval_only", "model": args.model_name,
+                                  "n_gpus": world, "checkpoint": args.checkpoint, "eval": ev}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     torch.manual_seed(args.seed + 1000 * (rank + 1))                          # per-rank augmentation draws from here on
     np.random.seed(args.seed + 1000 * (rank + 1))
 
@@ -198,6 +240,7 @@ def main(argv=None):
                else KDTrainer(model, mel, opt, **common))
 
     steps_total, clips_total, t_train = 0, 0, 0.0
+    evals = []
     done = False
     for epoch in range(args.n_epochs):
         sampler.set_epoch(epoch)
@@ -222,10 +265,15 @@ def main(argv=None):
         dt = time.perf_counter() - t0
         t_train += dt
         steps_total += n_ep
+        ev_txt = ""
+        if args.eval_every and ((epoch + 1) % args.eval_every == 0 or done):
+            ev = _evaluate(args, model, mel, test_set, rank, world, dev)
+            evals.append({"epoch": epoch, **{k: ev[k] for k in ("mAP", "ROC", "val_loss", "n_clips", "eval_s")}})
+            ev_txt = f", mAP {ev['mAP']:.5f}, ROC {ev['ROC']:.5f}, val_loss {ev['val_loss']:.5f}"
         if rank == 0:
             print(f"[train_dp] epoch {epoch + 1}/{args.n_epochs}: {n_ep} steps, {n_ep * args.batch_size * world / dt:.0f} clips/s "
                   f"over {world} GPU(s), train_loss {stats['train_loss']:.5f} (label {stats['label_loss']:.5f}, "
-                  f"kd {stats['distillation_loss']:.5f}), lr {float(sched.get_last_lr()[0]):.2e}", file=sys.stderr, flush=True)
+                  f"kd {stats['distillation_loss']:.5f}), lr {float(sched.get_last_lr()[0]):.2e}{ev_txt}", file=sys.stderr, flush=True)
             if args.out:
                 os.makedirs(args.out, exist_ok=True)
                 torch.save(model.state_dict(), os.path.join(args.out, f"{args.model_name}_epoch_{epoch}.pt"))
@@ -243,11 +291,14 @@ def main(argv=None):
     else:
         spread = 0.0
     if rank == 0 and args.json:
-        print(json.dumps({"what": "efficientat_amd.train_dp", "model": args.model_name, "n_gpus": world, "steps": steps_total,
-                          "param_abs_sum": digest, "param_abs_sum_spread_over_ranks": spread, "backend": args.backend if world > 1 else None,
-                          "batch_per_gpu": args.batch_size, "clips_per_s": round(clips_total * world / max(t_train, 1e-9), 1),
-                          "launch": "hipGraph replay" if graphed else "eager", "transport": args.transport,
-                          "final": stats}), flush=True)
+        line = {"what": "efficientat_amd.train_dp", "model": args.model_name, "n_gpus": world, "steps": steps_total,
+                "param_abs_sum": digest, "param_abs_sum_spread_over_ranks": spread, "backend": args.backend if world > 1 else None,
+                "batch_per_gpu": args.batch_size, "clips_per_s": round(clips_total * world / max(t_train, 1e-9), 1),
+                "launch": "hipGraph replay" if graphed else "eager", "transport": args.transport,
+                "final": stats}
+        if args.eval_every:
+            line["eval"] = evals
+        print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

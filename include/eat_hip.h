@@ -859,6 +859,22 @@ int eat_pw_dyn_wgrad_b16_slices(int B, int Co, int Ci, int S, int x_b16);
 int eat_pw_conv_dyn_wgrad_b16(const void* dz, int dz_b16, const void* x, int x_b16, float* dW_b, int n_slices, int B, int Co,
                               int Ci, int S, eat_stream_t stream);
 
+/* ---- ranking metrics of the evaluation: ex_audioset.py:231-256 (_test), ex_pl_audioset.py:215-247 -------------------
+ * Per-class average precision and ROC AUC of sklearn 1.7 (metrics.average_precision_score / roc_auc_score with
+ * average=None) over scores (N, C) row-major, fp32 or bf16 (scores_b16 != 0), and targets (N, C) fp32.
+ *   ap (C) fp64     sum over distinct thresholds t, descending, of (R(t) - R(t_prev)) * P(t); tied scores form one
+ *                   threshold (equal as fp32, so -0.0 ties +0.0).  No positives: 0.0; only positives: 1.0.
+ *   auc (C) fp64    trapezoid area under the ROC curve (Mann-Whitney U, ties counted 1/2).  One class only: NaN.
+ *   n_pos (C) int32 positives per class.
+ *   status (1) int  0, or bit 1: a score is not finite, bit 2: a target is neither 0 nor 1 (the outputs are then
+ *                   undefined).  Written on the stream like the outputs.
+ * The sums are fp64 in a fixed order: repeated calls give bit-identical results.  1 <= N <= 2^22, 1 <= C <= 2^16,
+ * N * C <= 2^31 - 1, else EAT_EINVAL.  ws: eat_rank_metrics_ws_bytes(N, C) bytes (16 per element, so a long long;
+ * negative for an unsupported shape). */
+long long eat_rank_metrics_ws_bytes(int N, int C);
+int eat_rank_metrics(const void* scores, int scores_b16, const float* targets, int N, int C, void* ws, double* ap,
+                     double* auc, int* n_pos, int* status, eat_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
