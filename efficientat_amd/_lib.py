@@ -151,6 +151,9 @@ SIGNATURES = {
     # ranking metrics of the evaluation (metrics.py)
     "eat_rank_metrics_ws_bytes": [_I, _I],
     "eat_rank_metrics": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    # single-label fine-tuning (finetune.py)
+    "eat_softmax_ce_fwd_bwd": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "eat_wave_augment": [_P, _P, _P, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
 }
 
 RESTYPES = {"eat_rank_metrics_ws_bytes": ctypes.c_longlong}   # every other entry point returns int

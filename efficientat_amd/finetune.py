@@ -1,0 +1,306 @@
+"""Single-label fine-tuning (ex_esc50.py:95-178) as a device-resident engine: the clip bank lives in HBM, the augmentation and
+the loss are HIP kernels, and a captured step is one hipGraph replay.
+
+Per step the reference does: DataLoader workers decode, gain, pad, roll and wave-mix each clip on the host (datasets/esc50.py,
+datasets/helpers/audiodatasets.py) -> blocking copy -> mel -> log-mel mix-up -> model -> two F.cross_entropy terms weighted by
+the mix-up lambda -> a `.cpu()` read of the loss (a device sync) -> backward -> Adam.  Here:
+
+  * the batch is built on the device from the resident bank by `eat_wave_augment` (ops.wave_augment) from host draws made in
+    MixupDataset's order (esc50.draw_augment) - a few hundred bytes per step cross PCIe, no waveform does;
+  * `eat_softmax_ce_fwd_bwd` computes the soft-target cross-entropy of the mixed targets and d loss / d logits in one pass;
+    the loss is accumulated on the device and read once per epoch (`epoch_stats`);
+  * evaluation (`evaluate_accuracy`) takes argmax and per-row loss from the same kernel.
+
+Host RNG order of a step: the augmentation draws (torch, numpy), the mel's (fmin, fmax) draw, then `mixup` (torch.randperm,
+numpy beta) - the reference's order within the main process, with the DataLoader's draws moved in front of the step.
+"""
+import time
+
+import torch
+
+from . import ops
+from .esc50 import draw_augment
+from .train_loop import _HostRing, _restore, _snapshot, mixup
+
+
+class _CELoss(torch.autograd.Function):
+    """Loss scalar (device) whose backward hands the pre-computed d loss / d logits to the network's backward."""
+
+    @staticmethod
+    def forward(ctx, logits, y, perm, lam, sums):
+        logits = logits.contiguous()
+        # the step's loss goes to its own zeroed buffer; the epoch accumulator (fp64) is updated from it (as _KDLoss does)
+        step = torch.zeros(1, device=logits.device, dtype=torch.float32)
+        # (row_loss lets the kernel's second launch read the row losses instead of recomputing every row in one block)
+        row_loss = torch.empty(logits.shape[0], device=logits.device, dtype=torch.float32)
+        ctx.save_for_backward(ops.softmax_ce_fwd_bwd(logits, y, perm, lam, sums=step, row_loss=row_loss))
+        sums += step.to(sums.dtype)
+        return step[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g, None, None, None, None
+
+
+def ce_loss(logits, y, perm=None, lam=None, sums=None):
+    """mean_b [lam CE(z, y) + (1 - lam) CE(z, y[perm])] (ex_esc50.py:102-118) as a device scalar that supports .backward();
+    `sums` (1,) accumulates it across calls."""
+    if sums is None:
+        sums = torch.zeros(1, device=logits.device, dtype=torch.float64)
+    return _CELoss.apply(logits, y.contiguous().float(), perm, lam, sums)
+
+
+class CETrainer:
+    """step(batch) = one iteration of ex_esc50.py's training loop (:95-121) on the bank rows `batch` (host indices).
+
+    bank (N, L) fp32, bank_mean (N) fp64, bank_cls (N) int32: the resident training split (esc50.load_split); model / mel:
+    the HIP-backed modules; optimizer: e.g. optim.FusedAdam.  gain_augment / roll / wavmix: ex_esc50.py's --gain_augment,
+    not --no_roll, not --no_wavmix."""
+
+    def __init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, n_classes=50, mixup_alpha=0.3, gain_augment=12,
+                 roll=True, wavmix=True):
+        self.model, self.mel, self.opt = model, mel, optimizer
+        self.bank, self.bank_mean, self.bank_cls = bank, bank_mean, bank_cls.to(torch.int32).contiguous()
+        if bank.dim() != 2 or bank_mean.numel() != bank.shape[0] or self.bank_cls.numel() != bank.shape[0]:
+            raise ValueError("CETrainer: bank (N, L), bank_mean (N) and bank_cls (N) do not match")
+        self.n_classes, self.mixup_alpha = int(n_classes), mixup_alpha
+        self.gain_augment, self.roll, self.wavmix = int(gain_augment), bool(roll), bool(wavmix)
+        dev = next(model.parameters()).device
+        self.sums = torch.zeros(1, device=dev, dtype=torch.float64)
+        self.steps = 0
+
+    def draw(self, batch):
+        idx, shift, amp, mix = draw_augment(batch, self.bank.shape[0], self.gain_augment, self.roll, self.wavmix)
+        ops.check_augment_draws(idx, shift, self.bank.shape[0], self.bank.shape[1])
+        return idx, shift, amp, mix
+
+    def loss_and_backward(self, batch):
+        """augment -> mel -> log-mel mix-up -> model -> CE -> backward; leaves the gradients in `.grad`."""
+        dev = self.bank.device
+        draws = self.draw(batch)
+        x, y = ops.wave_augment(self.bank, self.bank_mean, self.bank_cls, *draws, self.n_classes)
+        bs = x.shape[0]
+        spec = self.mel(x).unsqueeze(1)                                       # _mel_forward, ex_esc50.py:143-148
+        perm = lam = None
+        if self.mixup_alpha:
+            rn, lm = mixup(bs, self.mixup_alpha)                              # host draws, reference order
+            perm, lam = rn.to(dev, torch.int32, non_blocking=True), lm.to(dev, non_blocking=True)
+            spec = ops.mixup_fwd(spec, perm, lam)
+        y_hat, _ = self.model(spec)
+        loss = ce_loss(y_hat, y, perm, lam, self.sums)
+        loss.backward()
+        return loss.detach()
+
+    def step(self, batch):
+        loss = self.loss_and_backward(batch)
+        self.opt.step()
+        self.opt.zero_grad()
+        self.steps += 1
+        return loss                                                           # device scalar: no sync
+
+    def epoch_stats(self):
+        """Mean train_loss since the last call: the ONE host sync of the epoch."""
+        s = float((self.sums / max(1, self.steps)).item())
+        self.sums.zero_()
+        self.steps = 0
+        return dict(train_loss=s)
+
+
+class GraphedCETrainer(CETrainer):
+    """`CETrainer` with the whole iteration - wave augmentation, log-mel, mix-up, forward, CE, backward, optimizer - captured
+    ONCE into a hipGraph and replayed with one host call per step.  What changes per step enters through static buffers:
+
+        idx / shift (2B) int32, amp (2B), mix (B)   the augmentation draws (validated on the host before staging);
+        perm (B) int32, lam (B)                     the log-mel mix-up draw;
+        the mel basis                               band table of the step's (fmin, fmax) jitter (`AugmentMelSTFT.static_tables`).
+
+    Host RNG order as `CETrainer.step`.  SpecAugment masks (freqm / timem != 0) are launch arguments of the mel kernel: the
+    augmentation and the mel then run eagerly in front of the graph.  The optimizer must be capturable (FusedAdam(...,
+    capturable=True) with a tensor lr, so that a scheduler needs no re-capture).  DyMN: call `recapture()` after
+    `model.update_params(epoch)` (the temperatures are launch constants).  A batch of another size (the last, partial batch
+    of an epoch) takes the eager step."""
+
+    def __init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, batch_size, n_classes=50, mixup_alpha=0.3,
+                 gain_augment=12, roll=True, wavmix=True, warmup=2):
+        super().__init__(model, mel, optimizer, bank, bank_mean, bank_cls, n_classes, mixup_alpha, gain_augment, roll, wavmix)
+        dev = bank.device
+        self.B, self.L = int(batch_size), int(bank.shape[1])
+        first = torch.full((2 * self.B,), -1, device=dev, dtype=torch.int32)
+        first[0::2] = 0                                                       # (bank row 0, no wave-mix: the warm-up batch)
+        self._idx = _HostRing(first)
+        self._shift = _HostRing(torch.zeros(2 * self.B, device=dev, dtype=torch.int32))
+        self._amp = _HostRing(torch.ones(2 * self.B, device=dev))
+        self._mix = _HostRing(torch.ones(self.B, device=dev))
+        self._perm = _HostRing(torch.arange(self.B, device=dev, dtype=torch.int32)) if mixup_alpha else None
+        self._lam = _HostRing(torch.ones(self.B, device=dev)) if mixup_alpha else None
+        self.wave = torch.zeros((self.B, self.L), device=dev)
+        self.y = torch.zeros((self.B, self.n_classes), device=dev)
+        self.mel_in_graph = not (mel.freqm or mel.timem)
+        T = 1 + (self.L - 1) // mel.hopsize
+        self.spec = torch.empty((self.B, 1, mel.n_mels, T), device=dev)
+        mel.static_tables(dev)
+        mel.stage_tables(mel.fmin, mel.fmax)
+        self.warmup = warmup
+        self.graph = None
+        self.loss = None
+        self.recapture()
+
+    def _front(self, fmask=(0, 0), tmask=(0, 0)):
+        ops.wave_augment(self.bank, self.bank_mean, self.bank_cls, self._idx.dev, self._shift.dev, self._amp.dev, self._mix.dev,
+                         self.n_classes, out=self.wave, y=self.y)
+        self.mel.forward_static(self.wave, out=self.spec, fmask=fmask, tmask=tmask)
+
+    # the captured sequence (everything reads / writes static buffers)
+    def _issue(self):
+        if self.mel_in_graph:
+            self._front()
+        spec = self.spec
+        perm = lam = None
+        if self._perm is not None:
+            perm, lam = self._perm.dev, self._lam.dev
+            spec = ops.mixup_fwd(spec, perm, lam)
+        y_hat, _ = self.model(spec)
+        loss = ce_loss(y_hat, self.y, perm, lam, self.sums)
+        loss.backward()
+        self.opt.step()
+        return loss.detach()
+
+    def recapture(self):
+        from .graphs import _capture_mode
+        if not self.mel_in_graph:
+            self._front()
+        keep = self.sums.clone()
+        state = _snapshot(self.model, self.opt)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(self.warmup):                 # (allocator / pack-plan warm-up on a side stream, as torch recommends)
+                self.opt.zero_grad(set_to_none=True)
+                self._issue()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        self.opt.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        with torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
+            self.loss = self._issue()
+        # the warm-up steps trained on the warm-up batch: put parameters, BatchNorm buffers, optimizer state and the sums back
+        _restore(self.model, self.opt, state)
+        self.sums.copy_(keep)
+        cache = getattr(self.model, "_cache", None)
+        if cache is not None:
+            cache.invalidate()
+
+    def step(self, batch):
+        if len(batch) != self.B:
+            return super().step(batch)                   # e.g. the last, partial batch of an epoch
+        idx, shift, amp, mix = self.draw(batch)          # host draws, reference order: augmentation, mel, mix-up
+        self._idx.put(idx)
+        self._shift.put(shift)
+        self._amp.put(amp)
+        self._mix.put(mix)
+        fmin, fmax, fmask, tmask = self.mel.draw(self.L)
+        self.mel.stage_tables(fmin, fmax)
+        if not self.mel_in_graph:
+            self._front(fmask, tmask)
+        if self._perm is not None:
+            rn, lm = mixup(self.B, self.mixup_alpha)
+            self._perm.put(rn.to(torch.int32))
+            self._lam.put(lm)
+        self.graph.replay()
+        cache = getattr(self.model, "_cache", None)
+        if cache is not None:            # a replay updates the weights without bumping their version counters
+            cache.invalidate()
+        self.steps += 1
+        return self.loss
+
+
+def evaluate_accuracy(model, mel, bank, bank_cls, batch_size, n_classes=None, keep_outputs=False):
+    """The reference's `_test` (ex_esc50.py:154-178) on a resident split -> {"accuracy", "val_loss", "n_clips", "eval_s",
+    "clips_per_s"} (+ "logits" / "targets" (N, C) device tensors with keep_outputs=True).
+
+    accuracy: argmax(logits) == class over every clip; val_loss: the MEAN OF THE PER-BATCH MEAN cross-entropies at
+    `batch_size` (the reference's `losses.mean()`; the last batch of a fold may be short, so this is not the clip mean).
+    Both come from `eat_softmax_ce_fwd_bwd` (row argmax, per-batch sums); one host sync at the end.  Runs in eval mode under
+    no_grad inside a forked torch RNG (the mel draws its jitter even in eval); both modules get their previous mode back."""
+    n = bank.shape[0]
+    if n == 0:
+        raise ValueError("evaluate_accuracy: the split is empty")
+    dev = bank.device
+    cls = bank_cls.to(device=dev, dtype=torch.int64)
+    n_batches = (n + batch_size - 1) // batch_size
+    was_training = (model.training, mel.training)
+    model.eval()
+    mel.eval()
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    try:
+        with torch.random.fork_rng(devices=[]), torch.no_grad():
+            amax = torch.empty(n, device=dev, dtype=torch.int32)
+            rloss = torch.empty(n, device=dev, dtype=torch.float32)
+            bsum = torch.zeros(n_batches, device=dev, dtype=torch.float32)
+            logits = targets = None
+            for k in range(n_batches):
+                s, e = k * batch_size, min(n, (k + 1) * batch_size)
+                y_hat, _ = model(mel(bank[s:e]).unsqueeze(1))                 # _mel_forward + model (ex_esc50.py:163-165)
+                y_hat = y_hat.reshape(e - s, -1).float().contiguous()
+                C = y_hat.shape[1]
+                y = torch.nn.functional.one_hot(cls[s:e], n_classes or C).float()
+                ops.softmax_ce_fwd_bwd(y_hat, y, sums=bsum[k:k + 1], grad=False, row_loss=rloss[s:e], row_argmax=amax[s:e])
+                if keep_outputs:
+                    if logits is None:
+                        logits = torch.empty((n, C), device=dev)
+                        targets = torch.empty((n, y.shape[1]), device=dev)
+                    logits[s:e].copy_(y_hat)
+                    targets[s:e].copy_(y)
+            res = torch.stack([(amax.long() == cls).double().mean(), bsum.double().mean()]).cpu().tolist()
+    finally:
+        model.train(was_training[0])
+        mel.train(was_training[1])
+    eval_s = time.perf_counter() - t0
+    out = {"accuracy": res[0], "val_loss": res[1], "n_clips": n, "eval_s": eval_s, "clips_per_s": n / max(eval_s, 1e-9)}
+    if keep_outputs:
+        out["logits"], out["targets"] = logits, targets
+    return out
+
+
+def _out_layer(model, sd):
+    """-> (keys of the output layer, classes of the checkpoint, classes of the model) for the heads the reference re-sizes
+    (models/mn/model.py:285-304), None for any other head."""
+    head = getattr(model, "head_type", None)
+    if head == "mlp":
+        return ["classifier.5.weight", "classifier.5.bias"], sd["classifier.5.bias"].shape[0], model.classifier[5].out_features
+    if head == "fully_convolutional":
+        keys = ["classifier.0.weight"] + [k for k in sd if k.startswith("classifier.1.")]
+        return keys, sd["classifier.1.bias"].shape[0], model.classifier[0].out_channels
+    return None
+
+
+def load_init_checkpoint(model, path):
+    """Initialise `model` from a local AudioSet state dict (e.g. one written by `train_dp --out`) - what the reference's
+    `pretrained_name` does from its download.  When the class count differs, the output layer is dropped (classifier.5.* for
+    the mlp head, classifier.0.weight + classifier.1.* for the fully-convolutional one) with the reference's note, and the
+    rest is loaded strictly; a mismatch on any other head raises ValueError.  -> the list of dropped keys."""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    msd = model.state_dict()
+    mismatch = sorted(k for k in sd if k in msd and tuple(sd[k].shape) != tuple(msd[k].shape))
+    out = _out_layer(model, sd) if mismatch else None
+    if mismatch and out is None:
+        raise ValueError(f"load_init_checkpoint: {path} does not fit head '{getattr(model, 'head_type', None)}' "
+                         f"(shape mismatch at {mismatch[:4]}); only the mlp and fully_convolutional heads can be re-sized")
+    dropped = []
+    if out is not None:
+        keys, n_ckpt, n_model = out
+        stray = [k for k in mismatch if k not in keys]
+        if n_ckpt == n_model or stray:
+            raise ValueError(f"load_init_checkpoint: {path} mismatches outside the output layer: {(stray or mismatch)[:4]}")
+        print(f"Number of classes defined: {n_model}, but try to load pre-trained layer with logits: {n_ckpt}\n"
+              "Dropping last layer.")
+        for k in keys:
+            sd.pop(k)
+        dropped = keys
+    res = model.load_state_dict(sd, strict=not dropped)
+    if dropped and (sorted(res.missing_keys) != sorted(dropped) or res.unexpected_keys):
+        raise ValueError(f"load_init_checkpoint: {path} does not hold the model's other tensors "
+                         f"(missing {res.missing_keys[:4]}, unexpected {res.unexpected_keys[:4]})")
+    return dropped

@@ -1562,3 +1562,75 @@ def kd_loss_fwd_bwd(logits, y, perm, lam, teacher, teacher_idx, kd_lambda, sums)
               None if teacher_idx is None else teacher_idx.data_ptr(), 0 if teacher is None else teacher.shape[0],
               float(kd_lambda), B, C, sums.data_ptr(), dlogits.data_ptr(), _stream())
     return dlogits
+
+
+# ------------------------------------------------------------------ single-label fine-tuning (ex_esc50.py:95-178)
+def _dev_int32(t, name, n):
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
+        raise _lib.EatHipError(f"{name} must be a contiguous int32 GPU tensor of {n} elements (got {t.dtype}, {tuple(t.shape)}, "
+                               f"on {t.device})")
+    return t.data_ptr()
+
+
+def softmax_ce_fwd_bwd(logits, y, perm=None, lam=None, sums=None, grad=True, row_loss=None, row_argmax=None):
+    """Soft-target cross-entropy of (B, C) logits against y (B, C), with the mix-up t = lam y + (1 - lam) y[perm] folded in
+    (include/eat_hip.h: eat_softmax_ce_fwd_bwd).  -> dlogits (B, C) (None with grad=False); `sums` (>= 1 fp32) += the batch
+    mean; `row_loss` (B) fp32 and `row_argmax` (B) int32 are filled when given."""
+    if logits.dim() != 2:
+        raise _lib.EatHipError(f"softmax_ce_fwd_bwd: logits must be (B, C), got {tuple(logits.shape)}")
+    B, C = logits.shape
+    if tuple(y.shape) != (B, C):
+        raise _lib.EatHipError(f"softmax_ce_fwd_bwd: y {tuple(y.shape)} does not match the logits {(B, C)}")
+    if (perm is None) != (lam is None):
+        raise _lib.EatHipError("softmax_ce_fwd_bwd: perm and lam go together")
+    if lam is not None and lam.numel() != B:
+        raise _lib.EatHipError("softmax_ce_fwd_bwd: lam must hold B values")
+    if row_loss is not None and row_loss.numel() != B:
+        raise _lib.EatHipError("softmax_ce_fwd_bwd: row_loss must hold B values")
+    if sums is not None and (sums.dtype != torch.float32 or sums.numel() < 1):
+        raise _lib.EatHipError("softmax_ce_fwd_bwd: sums must be a float32 tensor")
+    dlogits = torch.empty_like(logits) if grad else None
+    _lib.call("eat_softmax_ce_fwd_bwd", _dev(logits, "logits"), _dev(y, "y"), _dev_int32(perm, "perm", B), _opt(lam, "lam"),
+              B, C, _opt(sums, "sums"), _opt(dlogits, "dlogits"), _opt(row_loss, "row_loss"),
+              _dev_int32(row_argmax, "row_argmax", B), _stream())
+    return dlogits
+
+
+def check_augment_draws(idx, shift, n_bank, L):
+    """Host-side validation of the draw tables of `wave_augment` (CPU tensors of 2B values): primary rows in [0, n_bank),
+    partners in [-1, n_bank), shifts in (-L, L)."""
+    idx, shift = torch.as_tensor(idx), torch.as_tensor(shift)
+    if idx.numel() % 2 or idx.numel() != shift.numel() or idx.numel() == 0:
+        raise ValueError(f"wave_augment: idx / shift must hold 2B values each (got {idx.numel()}, {shift.numel()})")
+    prim, part = idx[0::2], idx[1::2]
+    if bool(((prim < 0) | (prim >= n_bank)).any()) or bool(((part < -1) | (part >= n_bank)).any()):
+        raise ValueError(f"wave_augment: a bank index lies outside [0, {n_bank}) (partners may be -1)")
+    if bool((shift.abs() >= L).any()):
+        raise ValueError(f"wave_augment: a shift lies outside (-{L}, {L})")
+
+
+def wave_augment(bank, bank_mean, bank_cls, idx, shift, amp, mix, n_classes, out=None, y=None):
+    """Gain + roll + wave-mix of a batch gathered from the resident bank (include/eat_hip.h: eat_wave_augment) -> (out (B, L),
+    y (B, n_classes)).  idx / shift (2B) int32, amp (2B) / mix (B) fp32: CPU tensors are validated here and uploaded; device
+    tensors (the static buffers of a captured step) must have been validated before they were staged."""
+    n_bank, L = bank.shape
+    B = torch.as_tensor(mix).numel()
+    dev = bank.device
+    if not idx.is_cuda:
+        check_augment_draws(idx, shift, n_bank, L)
+        idx, shift = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, shift))
+        amp, mix = (t.to(dev, torch.float32, non_blocking=True) for t in (amp, mix))
+    if bank_mean.dtype != torch.float64 or not bank_mean.is_cuda or bank_mean.numel() != n_bank:
+        raise _lib.EatHipError("wave_augment: bank_mean must be a float64 GPU tensor of one value per bank row")
+    if out is None:
+        out = torch.empty((B, L), device=dev, dtype=torch.float32)
+    if y is None:
+        y = torch.empty((B, n_classes), device=dev, dtype=torch.float32)
+    if out.numel() != B * L or y.numel() != B * n_classes or amp.numel() != 2 * B:
+        raise _lib.EatHipError("wave_augment: out / y / amp do not match the batch")
+    _lib.call("eat_wave_augment", _dev(bank, "bank"), bank_mean.data_ptr(), _dev_int32(bank_cls, "bank_cls", n_bank), n_bank, L,
+              n_classes, _dev_int32(idx, "idx", 2 * B), _dev_int32(shift, "shift", 2 * B), _dev(amp, "amp"), _dev(mix, "mix"),
+              _dev(out, "out"), _dev(y, "y"), B, _stream())
+    return out, y

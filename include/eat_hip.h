@@ -875,6 +875,40 @@ long long eat_rank_metrics_ws_bytes(int N, int C);
 int eat_rank_metrics(const void* scores, int scores_b16, const float* targets, int N, int C, void* ws, double* ap,
                      double* auc, int* n_pos, int* status, eat_stream_t stream);
 
+/* ---- single-label fine-tuning: ex_esc50.py:95-178 ---------------------------------------------------------------------
+ * Soft-target softmax cross-entropy with the mix-up of the targets folded in (F.cross_entropy with probability targets,
+ * ex_esc50.py:102-118), its gradient and the evaluation outputs (:154-178) in one pass over the (B, C) logits:
+ *   t_b   = lam[b] y_b + (1 - lam[b]) y_perm[b]       (perm / lam (B) int32 / fp32, both NULL: t_b = y_b)
+ *   S_b   = sum_c t_bc                                  (rows need not sum to 1; a zero row is legal)
+ *   CE_b  = sum_c t_bc (lse(z_b) - z_bc)                (= lam CE(z, y) + (1 - lam) CE(z, y[perm]): CE is linear in t)
+ *   sums (1)          += mean_b CE_b, reduced in a fixed order (no atomics): repeated calls are bit-identical
+ *   dlogits (B, C)     = (S_b softmax(z_b) - t_b) / B  (torch's gradient for probability targets; p - t only if S_b = 1)
+ *   row_loss (B)       = CE_b
+ *   row_argmax (B) int = first index of the largest logit (numpy argmax: all-equal -> 0, a NaN wins at its first position)
+ * Any of sums / dlogits / row_loss / row_argmax may be NULL.  Arithmetic in fp64 with the max subtracted before exp; a NaN
+ * logit makes its row's loss and gradient NaN.  At most two launches: the rows (one wave each), then one block for `sums`
+ * (it reads row_loss, or recomputes the rows when row_loss is NULL - slower: pass row_loss on a hot path).
+ * B >= 1, C >= 1, B * C < 2^31, perm and lam given together, else EAT_EINVAL. */
+int eat_softmax_ce_fwd_bwd(const float* logits, const float* y, const int* perm, const float* lam, int B, int C,
+                           float* sums, float* dlogits, float* row_loss, int* row_argmax, eat_stream_t stream);
+
+/* Training batch of the ESC-50 loop built on the device from a resident clip bank (datasets/esc50.py gain + pad,
+ * datasets/helpers/audiodatasets.py roll, MixupDataset wave-mix):
+ *   bank (n_bank, L) clips already padded / truncated to L; bank_mean (n_bank) fp64 mean of each row; bank_cls (n_bank) int
+ *   class ids.  Per sample b, slot 0 = the clip, slot 1 = its wave-mix partner: idx (2B) int32 bank rows, idx[2b+1] = -1 for
+ *   no wave-mix; shift (2B) int32; amp (2B) fp32 linear gains; mix (B) fp32 wave-mix weights.
+ *   x_k[n] = amp_k bank[idx_k, (n - shift_k) mod L]     (gain, then torch.roll(x, shift_k); any shift)
+ *   out[b] = x_0                                                          without wave-mix
+ *   out[b] = l (x_0 - amp_0 m_0) + (1 - l) (x_1 - amp_1 m_1)              with it, l = mix[b], m_k = bank_mean[idx_k]
+ *   y[b]   = l at bank_cls[idx_0] + (1 - l) at bank_cls[idx_1] (a one-hot row without wave-mix); y (B, C) may be NULL
+ * The reference's final `x - x.mean()` of a mixed clip removes a mean that is already zero up to fp32 rounding: omitted.
+ * Offsets are 64-bit (n_bank * L may pass 2^31); any L; out rows are written with 16-byte stores where aligned.  The caller
+ * validates idx (0 <= idx_0 < n_bank, -1 <= idx_1 < n_bank) and bank_cls (in [0, C)) on the host; a row whose idx is out of
+ * range is written as NaN and no bank row outside the bank is read.  out must not alias bank.  B <= 65535. */
+int eat_wave_augment(const float* bank, const double* bank_mean, const int* bank_cls, long long n_bank, int L, int C,
+                     const int* idx, const int* shift, const float* amp, const float* mix, float* out, float* y, int B,
+                     eat_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
