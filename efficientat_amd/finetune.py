@@ -20,27 +20,8 @@ import torch
 
 from . import ops
 from .esc50 import draw_augment
-from .train_loop import _HostRing, _restore, _snapshot, mixup
-
-
-class _CELoss(torch.autograd.Function):
-    """Loss scalar (device) whose backward hands the pre-computed d loss / d logits to the network's backward."""
-
-    @staticmethod
-    def forward(ctx, logits, y, perm, lam, sums):
-        logits = logits.contiguous()
-        # the step's loss goes to its own zeroed buffer; the epoch accumulator (fp64) is updated from it (as _KDLoss does)
-        step = torch.zeros(1, device=logits.device, dtype=torch.float32)
-        # (row_loss lets the kernel's second launch read the row losses instead of recomputing every row in one block)
-        row_loss = torch.empty(logits.shape[0], device=logits.device, dtype=torch.float32)
-        ctx.save_for_backward(ops.softmax_ce_fwd_bwd(logits, y, perm, lam, sums=step, row_loss=row_loss))
-        sums += step.to(sums.dtype)
-        return step[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dlogits,) = ctx.saved_tensors
-        return dlogits * g, None, None, None, None
+from .graphs import HostRing
+from .train_loop import FusedLoss, GraphedTrainer, Trainer
 
 
 def ce_loss(logits, y, perm=None, lam=None, sums=None):
@@ -48,15 +29,20 @@ def ce_loss(logits, y, perm=None, lam=None, sums=None):
     `sums` (1,) accumulates it across calls."""
     if sums is None:
         sums = torch.zeros(1, device=logits.device, dtype=torch.float64)
-    return _CELoss.apply(logits, y.contiguous().float(), perm, lam, sums)
+    y = y.contiguous().float()
+    # (row_loss lets the kernel's second launch read the row losses instead of recomputing every row in one block)
+    return FusedLoss.apply(logits, sums, 1, lambda z, step: ops.softmax_ce_fwd_bwd(
+        z, y, perm, lam, sums=step, row_loss=torch.empty(z.shape[0], device=z.device, dtype=torch.float32)))
 
 
-class CETrainer:
+class CETrainer(Trainer):
     """step(batch) = one iteration of ex_esc50.py's training loop (:95-121) on the bank rows `batch` (host indices).
 
     bank (N, L) fp32, bank_mean (N) fp64, bank_cls (N) int32: the resident training split (esc50.load_split); model / mel:
     the HIP-backed modules; optimizer: e.g. optim.FusedAdam.  gain_augment / roll / wavmix: ex_esc50.py's --gain_augment,
     not --no_roll, not --no_wavmix."""
+
+    STATS = ("train_loss",)
 
     def __init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, n_classes=50, mixup_alpha=0.3, gain_augment=12,
                  roll=True, wavmix=True):
@@ -77,37 +63,17 @@ class CETrainer:
 
     def loss_and_backward(self, batch):
         """augment -> mel -> log-mel mix-up -> model -> CE -> backward; leaves the gradients in `.grad`."""
-        dev = self.bank.device
         draws = self.draw(batch)
         x, y = ops.wave_augment(self.bank, self.bank_mean, self.bank_cls, *draws, self.n_classes)
-        bs = x.shape[0]
         spec = self.mel(x).unsqueeze(1)                                       # _mel_forward, ex_esc50.py:143-148
-        perm = lam = None
-        if self.mixup_alpha:
-            rn, lm = mixup(bs, self.mixup_alpha)                              # host draws, reference order
-            perm, lam = rn.to(dev, torch.int32, non_blocking=True), lm.to(dev, non_blocking=True)
-            spec = ops.mixup_fwd(spec, perm, lam)
+        spec, perm, lam = self._mixup(spec)                                   # host draws, reference order
         y_hat, _ = self.model(spec)
         loss = ce_loss(y_hat, y, perm, lam, self.sums)
         loss.backward()
         return loss.detach()
 
-    def step(self, batch):
-        loss = self.loss_and_backward(batch)
-        self.opt.step()
-        self.opt.zero_grad()
-        self.steps += 1
-        return loss                                                           # device scalar: no sync
 
-    def epoch_stats(self):
-        """Mean train_loss since the last call: the ONE host sync of the epoch."""
-        s = float((self.sums / max(1, self.steps)).item())
-        self.sums.zero_()
-        self.steps = 0
-        return dict(train_loss=s)
-
-
-class GraphedCETrainer(CETrainer):
+class GraphedCETrainer(GraphedTrainer, CETrainer):
     """`CETrainer` with the whole iteration - wave augmentation, log-mel, mix-up, forward, CE, backward, optimizer - captured
     ONCE into a hipGraph and replayed with one host call per step.  What changes per step enters through static buffers:
 
@@ -123,96 +89,34 @@ class GraphedCETrainer(CETrainer):
 
     def __init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, batch_size, n_classes=50, mixup_alpha=0.3,
                  gain_augment=12, roll=True, wavmix=True, warmup=2):
-        super().__init__(model, mel, optimizer, bank, bank_mean, bank_cls, n_classes, mixup_alpha, gain_augment, roll, wavmix)
-        dev = bank.device
-        self.B, self.L = int(batch_size), int(bank.shape[1])
-        first = torch.full((2 * self.B,), -1, device=dev, dtype=torch.int32)
+        CETrainer.__init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, n_classes, mixup_alpha, gain_augment, roll,
+                           wavmix)
+        dev, B = bank.device, int(batch_size)
+        first = torch.full((2 * B,), -1, device=dev, dtype=torch.int32)
         first[0::2] = 0                                                       # (bank row 0, no wave-mix: the warm-up batch)
-        self._idx = _HostRing(first)
-        self._shift = _HostRing(torch.zeros(2 * self.B, device=dev, dtype=torch.int32))
-        self._amp = _HostRing(torch.ones(2 * self.B, device=dev))
-        self._mix = _HostRing(torch.ones(self.B, device=dev))
-        self._perm = _HostRing(torch.arange(self.B, device=dev, dtype=torch.int32)) if mixup_alpha else None
-        self._lam = _HostRing(torch.ones(self.B, device=dev)) if mixup_alpha else None
-        self.wave = torch.zeros((self.B, self.L), device=dev)
-        self.y = torch.zeros((self.B, self.n_classes), device=dev)
-        self.mel_in_graph = not (mel.freqm or mel.timem)
-        T = 1 + (self.L - 1) // mel.hopsize
-        self.spec = torch.empty((self.B, 1, mel.n_mels, T), device=dev)
-        mel.static_tables(dev)
-        mel.stage_tables(mel.fmin, mel.fmax)
-        self.warmup = warmup
-        self.graph = None
-        self.loss = None
-        self.recapture()
+        self._idx = HostRing(first)
+        self._shift = HostRing(torch.zeros(2 * B, device=dev, dtype=torch.int32))
+        self._amp = HostRing(torch.ones(2 * B, device=dev))
+        self._mix = HostRing(torch.ones(B, device=dev))
+        self._setup_graph(B, bank.shape[1], self.n_classes, warmup)
 
     def _front(self, fmask=(0, 0), tmask=(0, 0)):
         ops.wave_augment(self.bank, self.bank_mean, self.bank_cls, self._idx.dev, self._shift.dev, self._amp.dev, self._mix.dev,
                          self.n_classes, out=self.wave, y=self.y)
-        self.mel.forward_static(self.wave, out=self.spec, fmask=fmask, tmask=tmask)
+        super()._front(fmask, tmask)
 
-    # the captured sequence (everything reads / writes static buffers)
-    def _issue(self):
-        if self.mel_in_graph:
-            self._front()
-        spec = self.spec
-        perm = lam = None
-        if self._perm is not None:
-            perm, lam = self._perm.dev, self._lam.dev
-            spec = ops.mixup_fwd(spec, perm, lam)
-        y_hat, _ = self.model(spec)
-        loss = ce_loss(y_hat, self.y, perm, lam, self.sums)
-        loss.backward()
-        self.opt.step()
-        return loss.detach()
+    def _graph_loss(self, y_hat, perm, lam):
+        return ce_loss(y_hat, self.y, perm, lam, self.sums)
 
-    def recapture(self):
-        from .graphs import _capture_mode
-        if not self.mel_in_graph:
-            self._front()
-        keep = self.sums.clone()
-        state = _snapshot(self.model, self.opt)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(self.warmup):                 # (allocator / pack-plan warm-up on a side stream, as torch recommends)
-                self.opt.zero_grad(set_to_none=True)
-                self._issue()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        self.opt.zero_grad(set_to_none=True)
-        torch.cuda.synchronize()
-        with torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
-            self.loss = self._issue()
-        # the warm-up steps trained on the warm-up batch: put parameters, BatchNorm buffers, optimizer state and the sums back
-        _restore(self.model, self.opt, state)
-        self.sums.copy_(keep)
-        cache = getattr(self.model, "_cache", None)
-        if cache is not None:
-            cache.invalidate()
+    def _fits(self, batch):
+        return len(batch) == self.B
 
-    def step(self, batch):
-        if len(batch) != self.B:
-            return super().step(batch)                   # e.g. the last, partial batch of an epoch
-        idx, shift, amp, mix = self.draw(batch)          # host draws, reference order: augmentation, mel, mix-up
+    def _stage(self, batch):
+        idx, shift, amp, mix = self.draw(batch)          # host draws, reference order: augmentation, then the mel's, mix-up
         self._idx.put(idx)
         self._shift.put(shift)
         self._amp.put(amp)
         self._mix.put(mix)
-        fmin, fmax, fmask, tmask = self.mel.draw(self.L)
-        self.mel.stage_tables(fmin, fmax)
-        if not self.mel_in_graph:
-            self._front(fmask, tmask)
-        if self._perm is not None:
-            rn, lm = mixup(self.B, self.mixup_alpha)
-            self._perm.put(rn.to(torch.int32))
-            self._lam.put(lm)
-        self.graph.replay()
-        cache = getattr(self.model, "_cache", None)
-        if cache is not None:            # a replay updates the weights without bumping their version counters
-            cache.invalidate()
-        self.steps += 1
-        return self.loss
 
 
 def evaluate_accuracy(model, mel, bank, bank_cls, batch_size, n_classes=None, keep_outputs=False):

@@ -346,7 +346,8 @@ class _FoldCache:
     Version counters catch in-place updates made through autograd-visible ops (`load_state_dict`, `mul_`,
     the default optimizers) but NOT fused optimizers (`Adam(fused=True)`), hipGraph replays or our own
     kernels writing BN buffers through raw pointers - so the cache is also dropped on every train()/eval()
-    switch (`invalidate`, called from `MN.train` / `DyMN.train`) and by `GraphedTrainStep`."""
+    switch (`invalidate`, called from `MN.train` / `DyMN.train`) and after every training-step replay or state restore
+    (`graphs.replay_step`, `graphs.keep_state`)."""
 
     def __init__(self):
         self.key, self.val = None, None

@@ -251,8 +251,8 @@ class _ZeroArena:
         self.name, self.buf, self.off, self.req = name, None, 0, 0
 
     def end(self, name):
-        """Close a pass opened with `begin` (DyMN: called when the backward reaches the stem, and by GraphedTrainStep after
-        its capture): later un-scoped callers get their own `torch.zeros` again instead of slices of the step's buffer -
+        """Close a pass opened with `begin` (DyMN: called when the backward reaches the stem, and by `graphs.capture` after
+        every capture): later un-scoped callers get their own `torch.zeros` again instead of slices of the step's buffer -
         which a captured graph re-zeroes on every replay."""
         if self.name == name:
             self.need[name] = max(self.need.get(name, 0), self.req)

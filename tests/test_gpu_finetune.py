@@ -121,11 +121,12 @@ def _run_trainer(graphed, steps=3, B=6, L=32000, lr=1e-3, name="mn10", dropout_o
 
 
 def test_graphed_ce_trainer_follows_the_eager_trainer():
-    """Three seeded steps, captured vs eager: the tolerance of test_graphed_kd_trainer_follows_the_eager_trainer."""
+    """Three seeded steps, captured vs eager: the tolerances of test_graphed_kd_trainer_follows_the_eager_trainer."""
     res = {}
     for graphed in (False, True):
         tr, m, losses = _run_trainer(graphed)
-        res[graphed] = (losses, torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu(), tr.epoch_stats())
+        rm = torch.cat([b.detach().float().reshape(-1) for n, b in m.named_buffers() if n.endswith("running_mean")]).cpu()
+        res[graphed] = (losses, torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu(), tr.epoch_stats(), rm)
     le, lg = res[False][0], res[True][0]
     assert all(abs(a - b) < 2e-5 * max(1.0, abs(a)) for a, b in zip(le, lg)), (le, lg)
     d = (res[False][1] - res[True][1]).abs()
@@ -134,6 +135,10 @@ def test_graphed_ce_trainer_follows_the_eager_trainer():
     assert float(d.max()) <= 6.1e-3 and frac < 0.02, (float(d.max()), frac)
     se, sg = res[False][2]["train_loss"], res[True][2]["train_loss"]
     assert abs(se - sg) < 2e-5 * max(1.0, abs(se)) and abs(se - np.mean(le)) < 1e-5 * max(1.0, abs(se))
+    # the capture's warm-up steps must not leak into the BatchNorm running statistics (restored after the capture)
+    drm = float((res[False][3] - res[True][3]).abs().max())
+    print(f"running_mean max |eager - graph| {drm:.2e} (max |rm| {float(res[False][3].abs().max()):.2e})")
+    assert drm < 1e-4 * max(1.0, float(res[False][3].abs().max())), drm
 
 
 class _CountingGraph:

@@ -287,6 +287,52 @@ def test_lr_schedule_matches_the_reference_formula():
         assert abs(f(e) - ref(e)) < 1e-12
 
 
+def test_keep_state_puts_back_model_optimizer_and_extra_tensors():
+    """graphs.keep_state (the captured trainers' warm-up steps run inside it): after two Adam steps in the block, parameters,
+    BatchNorm running statistics and counters are bit-identical to before; optimizer state that existed before is back, state
+    created inside is zero; FusedAdam-style `_counters` and the extra tensor are back; the fold cache is dropped."""
+    from efficientat_amd.graphs import keep_state
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(8, 4), torch.nn.BatchNorm1d(4)).train()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-2)
+    x = torch.randn(16, 8)
+    model[0](x).square().sum().backward()               # Adam state for the Linear only (the BatchNorm has no gradient yet)
+    opt.step()
+    opt.zero_grad()
+    opt._counters = {0: torch.tensor(3.0)}
+
+    class _Cache:
+        n = 0
+
+        def invalidate(self):
+            self.n += 1
+    model._cache = _Cache()
+    sums = torch.tensor([1.5, -2.25], dtype=torch.float64)
+    lin, bn = list(model[0].parameters()), list(model[1].parameters())
+    sd0 = {k: v.clone() for k, v in model.state_dict().items()}
+    st0 = {p: {n: t.clone() for n, t in opt.state[p].items()} for p in lin}
+    assert all(p not in opt.state for p in bn)
+    with keep_state(model, opt, sums):
+        for _ in range(2):
+            opt.zero_grad()
+            model(x).square().sum().backward()
+            opt.step()
+            opt._counters[0] += 1
+            opt._counters[1] = torch.tensor(7.0)
+            sums += 1.0
+        assert not torch.equal(model[0].weight, sd0["0.weight"]) and int(model[1].num_batches_tracked) == 2
+    for k, v in model.state_dict().items():
+        assert torch.equal(v, sd0[k]), k
+    for p in lin:
+        for n, t in opt.state[p].items():
+            assert torch.equal(t, st0[p][n]), n
+    for p in bn:
+        assert opt.state[p] and all(not bool(t.any()) for t in opt.state[p].values())
+    assert float(opt._counters[0]) == 3.0 and float(opt._counters[1]) == 0.0
+    assert sums.tolist() == [1.5, -2.25]
+    assert model._cache.n == 1
+
+
 def test_band_table_with_fixed_pairs_is_the_same_basis():
     """preprocess.band_table(pairs=P): the fixed-shape table a captured step takes as an input buffer holds the same
     non-zeros as the tight one, for the corners and the widest point of the train-mode (fmin, fmax) draw space."""
