@@ -318,7 +318,7 @@ def _dyn_pw(x, bank, att, transposed, res=None, stats_bn=None):
     bf16 = ops.dyn_bf16_eligible(Co, Ci, S)
     if stats_bn is not None:
         # forward conv followed by a BatchNorm: -> (z, BatchNorm state); the batch statistics leave the conv's epilogue
-        if stats_bn.training and _EPI_STATS and (bf16 or not ops.kcat_eligible(Co, Ci, S)):
+        if stats_bn.training and (bf16 or not ops.kcat_eligible(Co, Ci, S)):
             wp = ops.dyn_pw_pack_bf16(bank2, att, Co, Ci) if bf16 else ops.dyn_pw_pack(bank2, att, Co, Ci)
             z, parts = ops.pw_conv_stats(x, wp, Co, per_sample=True)
             if z is not None:
@@ -557,7 +557,6 @@ def _block_train(blk, x):
 import os as _os
 
 _FUSED_BLOCK = True       # the dynamic block as one autograd Function (round 4; ablated blocks keep the per-layer Functions)
-_EPI_STATS = True         # BatchNorm statistics in the dynamic 1x1 convs' epilogue
 _FUSED_DW = _os.environ.get("EAT_DYMN_FUSED_DW", "1") != "0"      # A/B: the round-4 depthwise / DyReLU kernels of the block
 _WIDE_PS_WGRAD = _os.environ.get("EAT_DYMN_WIDE_WGRAD", "1") != "0"     # A/B: fp32 per-sample weight gradients on the wide-tile kernel
 _STORE16 = False          # set by forward_train for the pass: model.act_storage == "bf16" (the bf16-storage plan of the blocks)
