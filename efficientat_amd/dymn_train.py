@@ -8,26 +8,63 @@ libeat_hip.so, and autograd routes the gradients through the context path:
     DynPwConv / DynDwConv (kernel aggregation + per-sample conv; backward = per-sample weight
     gradients G_b, then dbank = att^T G, datt = G bank^T), DyReluCoordAtt.
 
+A fully dynamic block runs its feature-map path as ONE Function, `DyBlockMain`: a short driver over the stages expand,
+depthwise + DyReLU-B * CoordAtt and project (a `_<stage>_fwd` / `_<stage>_bwd` pair each, the depthwise stage once per
+plan: `_dw_merged_*` and `_dw_separate_*`), with the saved tensors in a `_DyState` record and the plan of the block
+(`_BlockPlan`: merged kernels or separate passes, fp32 or bf16 storage) decided once by `_block_train_fused`.  What belongs to
+the running pass and not to a block - bf16 storage asked for, the prepack plan with its run id, the hand-over dicts - is a
+`_Pass` record that `forward_train` installs through `_running_pass` and nothing else writes.  Every launch goes through a
+checked launcher of ops.py.
+
 Sequence-level glue on (B, L, H)-shaped tensors (BatchNorm of the context sequence, mean over L,
 3-tap average pool, softmax over K, sigmoid) stays on torch ops - these tensors are <= 4 % of the
 activation volume; every pass over a feature map and every GEMM runs in the library.
 Reference semantics: models/dymn/dy_block.py:390-409 (DY_Block.forward), :235-254 (ContextGen),
 :103-131 (DynamicConv), :172-188 (DyReLU-B), :195-201 (CoordAtt).
 """
-import os as _os
+import contextlib
+import os
+from dataclasses import dataclass
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import ops
+from ._lib import EatHipError
 from .dymn import _pool3
-from .mn_train import _zeros
 
 NONE, RELU, HSWISH = ops.ACT_NONE, ops.ACT_RELU, ops.ACT_HSWISH
+_zeros, _ones = ops.zeros_vec, ops.ones_vec           # cached constant vectors (the bias pointer of the train-mode convs)
+
+# switches for A/B runs, read once at import
+_FUSED_DW = os.environ.get("EAT_DYMN_FUSED_DW", "1") != "0"           # the merged depthwise / DyReLU kernels of the block
+_WIDE_PS_WGRAD = os.environ.get("EAT_DYMN_WIDE_WGRAD", "1") != "0"    # fp32 per-sample weight gradients on the wide-tile kernel
+_PACK_PLAN = os.environ.get("EAT_DYMN_PLAN", "1") != "0"              # the static 1x1 convs' weight packs from one launch per step
 
 
-def _s():
-    return torch.cuda.current_stream().cuda_stream
+@dataclass
+class _Pass:
+    """What a running `forward_train` shares with the Functions it builds.  plan: (ops.PrepackPlan or None, its run id) - a
+    PwConv keeps the pair in its ctx and its backward uses the plan's views only while no later forward has re-packed them
+    (two forwards before one backward).  handovers: the model's `_eat_handovers` list, filled by `_block_train_fused`."""
+    store16: bool = False                # model.act_storage == "bf16": the bf16-storage plan of the blocks that take it
+    plan: tuple = (None, 0)
+    handovers: list = None
+
+
+_passes = [_Pass()]                      # innermost last; the bottom record serves Functions applied outside `forward_train`
+
+
+@contextlib.contextmanager
+def _running_pass(store16, plan=None, handovers=None):
+    """Install the record of a pass (running its prepack plan first) for the duration of the `with` block."""
+    if plan is not None:
+        plan.run()
+    _passes.append(_Pass(store16, (plan, plan.runs) if plan is not None else (None, 0), handovers))
+    try:
+        yield
+    finally:
+        _passes.pop()
 
 
 def _t(x):
@@ -40,20 +77,6 @@ def _col_sum(m):
     return ops.col_sum(m.contiguous())
 
 
-class _in_precision:
-    """Re-enter, in a backward, the 1x1-conv arithmetic (`ops.precision`) the forward of the same Function ran under:
-    autograd calls backward() outside `forward_train`'s context manager."""
-
-    def __init__(self, ctx):
-        self.p = ops.precision(ctx.prec)
-
-    def __enter__(self):
-        self.p.__enter__()
-
-    def __exit__(self, *exc):
-        self.p.__exit__(*exc)
-
-
 # ------------------------------------------------------------------------------- Functions
 class CtxPool(torch.autograd.Function):
     @staticmethod
@@ -63,20 +86,14 @@ class CtxPool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dseq):
-        B, C, Fq, T = ctx.shape
-        dx = torch.empty(ctx.shape, device=dseq.device, dtype=torch.float32)
-        _lib.call("eat_ctx_pool_bwd", dseq.contiguous().data_ptr(), None, dx.data_ptr(), B, C, Fq, T, _s())
-        return dx
+        return ops.ctx_pool_bwd(dseq.contiguous(), ctx.shape)
 
 
 # Hand-over of a block's input gradient from the main path's backward to the context path's (below).  RESTRICTION: it
 # needs the WHOLE graph to run backward (`loss.backward()` / `torch.autograd.grad` w.r.t. the parameters or the input): a
 # partial backward that stops between the two Functions would drop the main path's dx.  The hand-over dicts of a forward
-# live on the model (`_eat_handovers`, one list per model - no process-global state); the NEXT forward of that model finds
+# live on the model (`_eat_handovers`, one list per model - no process-wide state); the NEXT forward of that model finds
 # an uncollected dx and fails loudly, naming the cause.
-
-
-_handovers = []           # the current forward's list (= model._eat_handovers of the model being run)
 
 
 class CtxPoolCm(torch.autograd.Function):
@@ -136,7 +153,7 @@ class Linear(torch.autograd.Function):
         if M >= 4096 and M % 4 == 0 and x.shape[1] % 4 == 0:
             # long reductions (M = B * (F + T) rows of the context sequence): dW = dy^T x is the 1x1 weight-gradient
             # GEMM with one "sample" of M positions - split-K over many blocks instead of 4 waves of the linear kernel
-            with _in_precision(ctx):
+            with ops.precision(ctx.prec):
                 dw = ops.pw_conv_wgrad(_t(dy).view(1, dy.shape[1], M, 1), _t(x).view(1, x.shape[1], M, 1),
                                        exact=None)
         else:
@@ -151,7 +168,6 @@ class BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, gamma, beta, bn, act):
         z = z.contiguous()
-        C = z.shape[1]
         st = ops.bn_train_state(z, bn)
         ctx.save_for_backward(z, *st)
         ctx.act = act
@@ -181,27 +197,19 @@ class StemConv(torch.autograd.Function):
 
 # All weight packs of the network's STATIC 1x1 convs (the context generators' joint_conv / conv_f / conv_t, out_c, the convs of
 # SE-less static blocks) - forward and data-gradient forms - from ONE launch per step (ops.PrepackPlan, as the MN plan does):
-# before, every PwConv packed its matrix when it ran, 92 launches of ~7 us per dymn20 step.  `_PLAN` = (plan, run id) of the
-# pass being built; a Function keeps it in its ctx and its backward uses the plan's views only while no later forward has
-# re-packed them (two forwards before one backward).
-_PLAN = (None, 0)
-
-
+# before, every PwConv packed its matrix when it ran, 92 launches of ~7 us per dymn20 step.
 def _static_prepack_plan(model):
     plan = getattr(model, "_eat_prepack_plan", None)
     if plan is not None and not plan.stale():
         return plan
-    if torch.cuda.is_current_stream_capturing() or _os.environ.get("EAT_DYMN_PLAN", "1") == "0":
+    if torch.cuda.is_current_stream_capturing() or not _PACK_PLAN:
         return None
-    entries, seen = [], set()
-    for m in model.modules():
-        if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (1, 1) and m.groups == 1 and m.weight.is_cuda \
-                and m.weight.dtype == torch.float32 and m.weight.data_ptr() not in seen:
-            seen.add(m.weight.data_ptr())
-            entries += [((m.weight.data_ptr(), False), m.weight, False), ((m.weight.data_ptr(), True), m.weight, True)]
+    weights = [m.weight for m in model.modules()
+               if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (1, 1) and m.groups == 1 and m.weight.is_cuda
+               and m.weight.dtype == torch.float32]
     try:
-        plan = ops.PrepackPlan(entries) if entries else None
-    except _lib.EatHipError:                              # channel counts the one-launch pack does not take: per-matrix packs
+        plan = ops.PrepackPlan.of_weights(weights)
+    except EatHipError:                                   # channel counts the one-launch pack does not take: per-matrix packs
         plan = None
     model._eat_prepack_plan = plan
     return plan
@@ -210,53 +218,33 @@ def _static_prepack_plan(model):
 def _pack(plan_run, w, trans):
     plan, run = plan_run
     if plan is not None and plan.runs == run:
-        v = plan.views.get((w.data_ptr(), trans))
+        v = plan.view(w, trans)
         if v is not None:
             return v
     return ops.pw_prepack(w.flatten(1), trans=trans)
 
 
 class PwConv(torch.autograd.Function):
-    """Static 1x1 conv (no bias): forward and data gradient are the same MFMA GEMM."""
+    """Static 1x1 conv: forward and data gradient are the same MFMA GEMM.  With a bias: conv_f / conv_t of the context
+    generator on the channel-major sequence."""
 
     @staticmethod
-    def forward(ctx, x, w):
+    def forward(ctx, x, w, b=None):
         ctx.save_for_backward(x, w)
-        ctx.prec = ops.precision.mode
-        ctx.plan = _PLAN
+        ctx.prec, ctx.plan, ctx.has_bias = ops.precision.mode, _passes[-1].plan, b is not None
         Co = w.shape[0]
-        return ops.pw_conv(x.contiguous(), _pack(_PLAN, w, False), _zeros.get(Co, x.device), Co, NONE)
-
-    @staticmethod
-    def backward(ctx, dz):
-        x, w = ctx.saved_tensors
-        dz = dz.contiguous()
-        Ci = x.shape[1]
-        with _in_precision(ctx):
-            dx = ops.pw_conv(dz, _pack(ctx.plan, w, True), _zeros.get(Ci, x.device), Ci, NONE)
-            return dx, ops.pw_conv_wgrad(dz, x, exact=None).view_as(w)
-
-
-class PwConvB(torch.autograd.Function):
-    """Static 1x1 conv WITH bias (conv_f / conv_t of the context generator on the channel-major sequence)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        ctx.save_for_backward(x, w)
-        ctx.prec = ops.precision.mode
-        ctx.plan = _PLAN
-        Co = w.shape[0]
-        return ops.pw_conv(x.contiguous(), _pack(_PLAN, w, False), b, Co, NONE)
+        return ops.pw_conv(x.contiguous(), _pack(ctx.plan, w, False), _zeros.get(Co, x.device) if b is None else b, Co, NONE)
 
     @staticmethod
     def backward(ctx, dz):
         x, w = ctx.saved_tensors
         dz = dz.contiguous()
         Ci, Co = x.shape[1], w.shape[0]
-        with _in_precision(ctx):
+        with ops.precision(ctx.prec):
             dx = ops.pw_conv(dz, _pack(ctx.plan, w, True), _zeros.get(Ci, x.device), Ci, NONE)
             dw = ops.pw_conv_wgrad(dz, x, exact=None).view_as(w)
-        db = ops.bn_stats(dz)[:Co].float()                   # per-channel sums over (batch, positions), fp64 accumulation
+        # bias gradient: per-channel sums over (batch, positions), fp64 accumulation
+        db = ops.bn_stats(dz)[:Co].float() if ctx.has_bias else None
         return dx, dw, db
 
 
@@ -287,15 +275,7 @@ class DwConv(torch.autograd.Function):
         return dx, ops.dw_conv_wgrad(dz, x, k, stride).view_as(w), None, None, None
 
 
-def _bank_grad(G, att, bank, datt=None):
-    """datt: zeroed (B, K) memory to accumulate into (a slice of the block's (n_att, B, K) tensor), or None."""
-    B, K, N = att.shape[0], bank.shape[0], bank.shape[1]
-    dbank = torch.empty_like(bank)
-    if datt is None:
-        datt = ops.zero_arena.zeros(tuple(att.shape), torch.float32, att.device)
-    _lib.call("eat_dyn_bank_grad", G.data_ptr(), att.data_ptr(), bank.data_ptr(), dbank.data_ptr(), datt.data_ptr(),
-              B, K, N, _s())
-    return dbank, datt
+_bank_grad = ops.dyn_bank_grad
 
 
 def _dyn_pw(x, bank, att, transposed, res=None, stats_bn=None):
@@ -354,7 +334,7 @@ def _dyn_pw_wgrad(dz, x, bank, att, datt=None):
     """-> (dbank (K, Co*Ci), datt (B, K)): per-sample weight gradients G_b = dz_b x_b^T, then dbank = att^T G,
     datt = G bank^T."""
     K, Co, Ci = bank.shape
-    B, S = x.shape[0], x.shape[2] * x.shape[3]
+    S = x.shape[2] * x.shape[3]
     if dz.dtype == torch.bfloat16 or x.dtype == torch.bfloat16:            # bf16-storage plan: one wide operand
         return _bank_grad(ops.pw_conv_dyn_wgrad_b16(dz, x), att, bank.reshape(K, Co * Ci), datt)
     if _WIDE_PS_WGRAD and S % 4 == 0 and Ci % 4 == 0:
@@ -363,12 +343,7 @@ def _dyn_pw_wgrad(dz, x, bank, att, datt=None):
         G = ops.pw_conv_dyn_wgrad_b16(dz, x)
         if G is not None:
             return _bank_grad(G, att, bank.reshape(K, Co * Ci), datt)
-    if ops.dyn_wgrad_needs_zero(Co, Ci, S):
-        G = ops.zero_arena.zeros((B, Co * Ci), torch.float32, x.device)
-    else:                                       # bf16x3 kernel in per-sample mode: plain stores
-        G = torch.empty((B, Co * Ci), device=x.device, dtype=torch.float32)
-    _lib.call("eat_pw_conv_dyn_wgrad", dz.data_ptr(), x.data_ptr(), G.data_ptr(), B, Co, Ci, S, _s())
-    return _bank_grad(G, att, bank.reshape(K, Co * Ci), datt)
+    return _bank_grad(ops.pw_conv_dyn_wgrad(dz, x), att, bank.reshape(K, Co * Ci), datt)
 
 
 class DynPwConv(torch.autograd.Function):
@@ -390,7 +365,7 @@ class DynPwConv(torch.autograd.Function):
         dz = dz.contiguous()
         Co, K = ctx.Co, weight.shape[2]
         bank = weight.view(K, Co, x.shape[1])
-        with _in_precision(ctx):
+        with ops.precision(ctx.prec):
             dx = _dyn_pw(dz, bank, att, True)
             dbank, datt = _dyn_pw_wgrad(dz, x, bank, att)
         return dx, dbank.view_as(weight), datt, None
@@ -402,8 +377,7 @@ class DynDwConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, att, k, stride, dilation=1):
         x, att = x.contiguous(), att.contiguous()
-        B, C, Fq, T = x.shape
-        K = weight.shape[2]
+        C, K = x.shape[1], weight.shape[2]
         taps = ops.dyn_aggregate(weight.view(K, C * k * k), att)
         ctx.save_for_backward(x, weight, att, taps)
         ctx.k, ctx.stride, ctx.dilation = k, stride, dilation
@@ -411,28 +385,19 @@ class DynDwConv(torch.autograd.Function):
             # dilated dynamic block (models/dymn/model.py:212-218; dy_block.py:322-348): per-sample taps = a depthwise conv over
             # B * C independent planes - the batch folded into the channel axis of the generic dilated kernels
             return ops.dw_conv_dyn_dilated(x, taps, k, stride, dilation)
-        Fo, To = ops.conv_out(Fq, k, stride), ops.conv_out(T, k, stride)
-        y = torch.empty((B, C, Fo, To), device=x.device, dtype=torch.float32)
-        _lib.call("eat_dw_conv_dyn_fwd", x.data_ptr(), taps.data_ptr(), _zeros.get(C, x.device).data_ptr(), None, None,
-                  None, y.data_ptr(), B, C, Fq, T, Fo, To, k, stride, _s())
-        return y
+        return ops.dw_conv_dyn(x, taps, _zeros.get(C, x.device), None, None, None, k, stride)
 
     @staticmethod
     def backward(ctx, dz):
         x, weight, att, taps = ctx.saved_tensors
         dz = dz.contiguous()
-        B, C, Fq, T = x.shape
+        C = x.shape[1]
         k, stride, K = ctx.k, ctx.stride, weight.shape[2]
-        Fo, To = dz.shape[2], dz.shape[3]
         if ctx.dilation > 1:
             dx, G = ops.dw_conv_dyn_dilated_bwd(dz, x, taps, k, stride, ctx.dilation)
-            dbank, datt = _bank_grad(G, att, weight.view(K, C * k * k))
-            return dx, dbank.view_as(weight), datt, None, None, None
-        dx = torch.empty_like(x)
-        _lib.call("eat_dw_conv_dyn_dgrad", dz.data_ptr(), taps.data_ptr(), None, dx.data_ptr(), B, C, Fq, T, Fo, To, k,
-                  stride, _s())
-        G = torch.zeros((B, C * k * k), device=x.device, dtype=torch.float32)
-        _lib.call("eat_dw_conv_dyn_wgrad", dz.data_ptr(), x.data_ptr(), G.data_ptr(), B, C, Fq, T, Fo, To, k, stride, _s())
+        else:
+            dx = ops.dw_conv_dyn_dgrad(dz, taps, x.shape, k, stride)
+            G = ops.dw_conv_dyn_wgrad(dz, x, k, stride)
         dbank, datt = _bank_grad(G, att, weight.view(K, C * k * k))
         return dx, dbank.view_as(weight), datt, None, None, None
 
@@ -443,23 +408,13 @@ class DyReluCoordAtt(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, coef, g_cf, g_ct):
         v, coef, g_cf, g_ct = v.contiguous(), coef.contiguous(), g_cf.contiguous(), g_ct.contiguous()
-        B, C, Fo, To = v.shape
         ctx.save_for_backward(v, coef, g_cf, g_ct)
-        out = torch.empty_like(v)
-        _lib.call("eat_dyrelu_ca_fwd", v.data_ptr(), None, None, coef.data_ptr(), g_cf.data_ptr(), g_ct.data_ptr(),
-                  out.data_ptr(), B, C, Fo, To, _s())
-        return out
+        return ops.dyrelu_ca_fwd(v, None, None, coef, g_cf, g_ct)
 
     @staticmethod
     def backward(ctx, dout):
         v, coef, g_cf, g_ct = ctx.saved_tensors
-        B, C, Fo, To = v.shape
-        dv, dcoef = torch.empty_like(v), torch.empty_like(coef)
-        dgf, dgt = torch.empty_like(g_cf), torch.empty_like(g_ct)
-        _lib.call("eat_dyrelu_ca_bwd", dout.contiguous().data_ptr(), v.data_ptr(), None, None, coef.data_ptr(),
-                  g_cf.data_ptr(), g_ct.data_ptr(), dv.data_ptr(), dcoef.data_ptr(), dgf.data_ptr(), dgt.data_ptr(), B, C,
-                  Fo, To, _s())
-        return dv, dcoef, dgf, dgt
+        return ops.dyrelu_ca_bwd(dout.contiguous(), v, None, None, coef, g_cf, g_ct)
 
 
 # ----------------------------------------------------------------------------------- plan
@@ -506,15 +461,15 @@ def _context_cm(blk, x, hand_over=None):
     gj = PwConv.apply(seq, cg.joint_conv.weight)
     g = BnAct.apply(gj, cg.joint_norm.weight, cg.joint_norm.bias, cg.joint_norm, HSWISH)
     h_cf, h_ct, h_c = CtxSplit.apply(g, B, Fq, T, blk.cnf.stride)
-    g_cf = PwConvB.apply(h_cf, cg.conv_f.weight, cg.conv_f.bias)
-    g_ct = PwConvB.apply(h_ct, cg.conv_t.weight, cg.conv_t.bias)
+    g_cf = PwConv.apply(h_cf, cg.conv_f.weight, cg.conv_f.bias)
+    g_ct = PwConv.apply(h_ct, cg.conv_t.weight, cg.conv_t.bias)
     return h_c, g_cf, g_ct
 
 
 def _block_train(blk, x):
     # (a dilated block - models/dymn/model.py:212-218 - takes the per-layer Functions: its depthwise conv runs on the generic
     #  dilated kernels with the batch folded into the channel axis, DynDwConv / DwConv)
-    if not (blk.no_dyconv or blk.no_dyrelu or blk.no_ca) and _FUSED_BLOCK and blk.cnf.dilation == 1:
+    if not (blk.no_dyconv or blk.no_dyrelu or blk.no_ca) and blk.cnf.dilation == 1:
         return _block_train_fused(blk, x)
     cnf = blk.cnf
     B, cin, Fq, T = x.shape
@@ -554,27 +509,6 @@ def _block_train(blk, x):
 
 
 # ------------------------------------------------------------------ the fully dynamic block as ONE autograd Function
-import os as _os
-
-_FUSED_BLOCK = True       # the dynamic block as one autograd Function (round 4; ablated blocks keep the per-layer Functions)
-_FUSED_DW = _os.environ.get("EAT_DYMN_FUSED_DW", "1") != "0"      # A/B: the round-4 depthwise / DyReLU kernels of the block
-_WIDE_PS_WGRAD = _os.environ.get("EAT_DYMN_WIDE_WGRAD", "1") != "0"     # A/B: fp32 per-sample weight gradients on the wide-tile kernel
-_STORE16 = False          # set by forward_train for the pass: model.act_storage == "bf16" (the bf16-storage plan of the blocks)
-
-
-class _Ones:
-    def __init__(self):
-        self.buf = None
-
-    def get(self, n, device):
-        if self.buf is None or self.buf.numel() < n or self.buf.device != device:
-            self.buf = torch.ones((max(n, 4096),), device=device, dtype=torch.float32)
-        return self.buf[:n]
-
-
-_ones = _Ones()
-
-
 class _HcHeads(torch.autograd.Function):
     """The four Linear layers that read h_c (the kernel attentions of the three dynamic convs, dy_block.py:106-109, and
     DyReLU-B's coefficient net, :176-181) as ONE GEMM over the row-concatenated weights, with their pointwise tails:
@@ -587,17 +521,12 @@ class _HcHeads(torch.autograd.Function):
         bias = torch.cat(bs, 0)
         h_c = h_c.contiguous()
         y = ops.linear(h_c, W, bias, NONE)                                    # (B, n_att * K + 4 cexp)
-        B = h_c.shape[0]
         n_att = len(ws) - 1
         K = ws[0].shape[0]
         # softmax(logits / T) per DynamicConv, sigmoid + affine of the DyReLU coefficients: ONE launch (csrc/dymn.hip)
-        att = torch.empty((n_att, B, K), device=y.device, dtype=torch.float32)
-        sg = torch.empty((B, 4 * cexp), device=y.device, dtype=torch.float32)
-        coef = torch.empty((B, cexp, 4), device=y.device, dtype=torch.float32)
         it = [1.0 / t for t in temps] + [1.0] * (3 - n_att)
         lam, iv = lambdas.contiguous().float(), init_v.contiguous().float()
-        _lib.call("eat_dyn_heads_fwd", y.data_ptr(), B, n_att, K, cexp, it[0], it[1], it[2], lam.data_ptr(), iv.data_ptr(),
-                  att.data_ptr(), sg.data_ptr(), coef.data_ptr(), _s())
+        att, sg, coef = ops.dyn_heads_fwd(y, n_att, K, cexp, it, lam, iv)
         ctx.save_for_backward(h_c, W, att, sg, lam)
         ctx.sizes, ctx.inv_t, ctx.cexp = [w.shape[0] for w in ws], it, cexp
         return att, coef
@@ -605,11 +534,7 @@ class _HcHeads(torch.autograd.Function):
     @staticmethod
     def backward(ctx, datt, dcoef):
         h_c, W, att, sg, lam = ctx.saved_tensors
-        n_att, B, K = att.shape
-        it = ctx.inv_t
-        dy = torch.empty((B, n_att * K + 4 * ctx.cexp), device=att.device, dtype=torch.float32)
-        _lib.call("eat_dyn_heads_bwd", datt.contiguous().data_ptr(), dcoef.contiguous().data_ptr(), att.data_ptr(), sg.data_ptr(),
-                  lam.data_ptr(), B, n_att, K, ctx.cexp, it[0], it[1], it[2], dy.data_ptr(), _s())
+        dy = ops.dyn_heads_bwd(datt.contiguous(), dcoef.contiguous(), att, sg, lam, ctx.cexp, ctx.inv_t)
         dh = ops.linear(dy, _t(W), None, NONE)
         dW = ops.linear(_t(dy), _t(h_c), None, NONE)
         db = _col_sum(dy)
@@ -621,6 +546,145 @@ class _HcHeads(torch.autograd.Function):
         return (dh, None, None, None, None, *outs)
 
 
+@dataclass(frozen=True)
+class _BlockPlan:
+    """How one block runs, decided by `_block_train_fused`.
+    merged: per-plane taps in the register-resident depthwise kernels with the BatchNorms evaluated on load, one-wave-per-plane
+    DyReLU on channel-major gates; otherwise the separate passes on position-major gates.
+    store16 (merged only; model.act_storage = "bf16"): z_e, z_d, x2 (and dx2, dv, g_e, dz_e in the backward) are bf16 in HBM,
+    plain bf16 GEMM operands, statistics of the values as stored (include/eat_hip.h, "bf16 activation storage for the DyMN
+    blocks"); block input / output, context path and per-sample weight gradients stay fp32."""
+    merged: bool
+    store16: bool
+    dyn_pw: object                       # the block's dynamic 1x1 conv: `_dyn_pw_b16` on bf16 storage, else `_dyn_pw`
+
+
+@dataclass
+class _DyState:
+    """What the forward of a block keeps for its backward; a field the block's plan does not produce stays None."""
+    x: torch.Tensor
+    att: torch.Tensor                    # (n_att, B, K): [expand,] depthwise, project
+    coef: torch.Tensor
+    g_cf: torch.Tensor
+    g_ct: torch.Tensor
+    w_e: torch.Tensor                    # None: block without expand conv
+    w_d: torch.Tensor
+    w_p: torch.Tensor
+    bank_e: torch.Tensor = None          # the three parameters as (K, ...) banks (`_banks`)
+    bank_d: torch.Tensor = None
+    bank_p: torch.Tensor = None
+    taps: torch.Tensor = None
+    z_e: torch.Tensor = None             # expand conv output and exp_norm's state (blocks with expand conv)
+    st_e: tuple = None
+    y_e: torch.Tensor = None             # act(exp_norm(z_e)): written by the separate-pass plan only
+    z_d: torch.Tensor = None
+    st_d: tuple = None
+    x2: torch.Tensor = None              # DyReLU-B * CoordAtt output, the project conv's input
+    z_p: torch.Tensor = None
+    st_p: tuple = None
+
+
+def _banks(blk, sv):
+    """The weight banks of the block's dynamic convs as (K, ...) matrices: (expand or None, depthwise, project)."""
+    cnf, K = blk.cnf, sv.w_d.shape[2]
+    cexp, k = cnf.expanded_channels, cnf.kernel
+    bank_e = None if sv.w_e is None else sv.w_e.view(K, cexp, sv.x.shape[1])
+    return bank_e, sv.w_d.view(K, cexp * k * k), sv.w_p.view(K, cnf.out_channels, cexp)
+
+
+def _expand_fwd(blk, plan, sv):
+    """z_e = W_b x, exp_norm's batch statistics from the conv's epilogue; the consumer evaluates BatchNorm + activation."""
+    if sv.w_e is not None:
+        sv.z_e, sv.st_e = plan.dyn_pw(sv.x, sv.bank_e, sv.att[0], False, stats_bn=blk.exp_norm)
+
+
+def _dw_merged_fwd(blk, plan, sv, act):
+    """Expand BatchNorm + activation on load, depth_norm's statistics in the epilogue (y_e is never written); DyReLU-B *
+    CoordAtt on depth_norm's affine of z_d (the normalised v is never written either)."""
+    cnf, has_e = blk.cnf, sv.w_e is not None
+    sv.z_d, parts = ops.dw_conv_dyn_stats(sv.z_e if has_e else sv.x, sv.taps, cnf.kernel, cnf.stride,
+                                          tf=(sv.st_e[0], sv.st_e[1], act) if has_e else None, out_b16=plan.store16)
+    sv.st_d = ops.bn_state_from_partials(parts, blk.depth_norm, sv.z_d.numel() // sv.z_d.shape[1]) if blk.depth_norm.training else \
+        ops.bn_frozen_state(blk.depth_norm)
+    sv.x2 = ops.dyrelu_ca_fwd2(sv.z_d, sv.st_d[0], sv.st_d[1], sv.coef, sv.g_cf, sv.g_ct)
+
+
+def _dw_separate_fwd(blk, sv, act):
+    cnf = blk.cnf
+    if sv.w_e is not None:
+        sv.y_e = ops.bn_act_fwd(sv.z_e, sv.st_e[0], sv.st_e[1], act)
+    y_e = sv.x if sv.y_e is None else sv.y_e
+    sv.z_d = ops.dw_conv_dyn(y_e, sv.taps, _zeros.get(cnf.expanded_channels, y_e.device), None, None, None, cnf.kernel, cnf.stride)
+    sv.st_d = ops.bn_train_state(sv.z_d, blk.depth_norm)
+    sv.x2 = ops.dyrelu_ca_fwd(sv.z_d, sv.st_d[0], sv.st_d[1], sv.coef, sv.g_cf, sv.g_ct)
+
+
+def _project_fwd(blk, plan, sv):
+    """z_p = W_b x2 with proj_norm's statistics from the epilogue; the BatchNorm pass adds the residual."""
+    sv.z_p, sv.st_p = plan.dyn_pw(sv.x2, sv.bank_p, sv.att[-1], False, stats_bn=blk.proj_norm)
+    return ops.bn_act_fwd(sv.z_p, sv.st_p[0], sv.st_p[1], NONE, res=sv.x if blk.use_res_connect else None)
+
+
+def _project_bwd(blk, plan, sv, dout):
+    """BatchNorm backward, data gradient, per-sample weight gradients -> (dx2, datt, dbank_p, dgamma, dbeta).  datt: the
+    attention gradients of the block's dynamic convs accumulate into ONE zeroed (n_att, B, K) tensor, allocated here, where
+    the first of them is produced."""
+    bank_p, att_p = sv.bank_p, sv.att[-1]
+    dz_p, dgp, dbp = ops.bn_act_bwd(dout, sv.z_p, *sv.st_p, NONE)
+    dx2 = plan.dyn_pw(dz_p, bank_p, att_p, True)
+    datt = ops.zero_arena.zeros(tuple(sv.att.shape), torch.float32, sv.att.device)
+    dbank_p, _ = _dyn_pw_wgrad(dz_p, sv.x2, bank_p, att_p, datt[-1])
+    return dx2, datt, dbank_p, dgp, dbp
+
+
+def _dw_merged_bwd(blk, sv, act, dx2, res, datt):
+    """-> (d_in, dcoef, dg_cf, dg_ct, dbank_d, (dgamma, dbeta) of depth_norm, of exp_norm).  d_in: with an expand conv dz_e,
+    the gradient of its output (exp_norm's backward is part of this stage: its sums leave the depthwise kernel's epilogue);
+    without, the block's dx, skip gradient (`res`) included."""
+    cnf, z_d, st_d = blk.cnf, sv.z_d, sv.st_d
+    B, cexp, k, stride = sv.x.shape[0], cnf.expanded_channels, cnf.kernel, cnf.stride
+    # DyReLU-B * CoordAtt on the BatchNorm affine of z_d; the sums of depth_norm's backward leave its epilogue
+    dv, dcoef, dgf, dgt, bnpart = ops.dyrelu_ca_bwd2(dx2, z_d, st_d[0], st_d[1], sv.coef, sv.g_cf, sv.g_ct)
+    sums_d, dgd, dbd = ops.bn_bwd_combine_partials(bnpart, bnpart.view(-1)[1:], 2, B, cexp, 1, st_d[2], st_d[3])
+    # merged depthwise backward: depth_norm's backward on load, tap gradients per plane, g_e = dy_e act'(.)
+    if sv.w_e is not None:
+        st_e = sv.st_e
+        g_e, G, parts = ops.dw_conv_dyn_bwd_bn_g(dv, z_d, st_d, NONE, sums_d, sv.taps, sv.z_e, st_e[0], st_e[1], act, k, stride)
+        sums_e, dge, dbe = ops.bn_bwd_combine_partials(parts[0], parts[1], 1, B, cexp, parts[2], st_e[2], st_e[3])
+        d_in = ops.bn_bwd_apply(g_e, sv.z_e, *st_e, sums_e)
+    else:
+        dge = dbe = None
+        one, zero = _ones.get(cexp, sv.x.device), _zeros.get(cexp, sv.x.device)
+        d_in, G, _ = ops.dw_conv_dyn_bwd_bn_g(dv, z_d, st_d, NONE, sums_d, sv.taps, sv.x, one, zero, NONE, k, stride, res=res,
+                                              want_sums=False)
+    dbank_d, _ = _bank_grad(G, sv.att[-2], sv.bank_d, datt[-2])
+    return d_in, dcoef, dgf, dgt, dbank_d, (dgd, dbd), (dge, dbe)
+
+
+def _dw_separate_bwd(blk, sv, act, dx2, res, datt):
+    """`_dw_merged_bwd` as separate passes (the skip gradient of a block without expand conv enters the data gradient)."""
+    cnf, z_d, has_e = blk.cnf, sv.z_d, sv.w_e is not None
+    B, cexp, k, stride = sv.x.shape[0], cnf.expanded_channels, cnf.kernel, cnf.stride
+    dv, dcoef, dgf, dgt = ops.dyrelu_ca_bwd(dx2, z_d, sv.st_d[0], sv.st_d[1], sv.coef, sv.g_cf, sv.g_ct)
+    dz_d, dgd, dbd = ops.bn_act_bwd(dv, z_d, *sv.st_d, NONE)
+    y_e = sv.y_e if has_e else sv.x
+    d_in = ops.dw_conv_dyn_dgrad(dz_d, sv.taps, y_e.shape, k, stride, res=None if has_e else res)
+    G = ops.dw_conv_dyn_wgrad(dz_d, y_e, k, stride, out=ops.zero_arena.zeros((B, cexp * k * k), torch.float32, y_e.device))
+    dge = dbe = None
+    if has_e:
+        d_in, dge, dbe = ops.bn_act_bwd(d_in, sv.z_e, *sv.st_e, act)
+    dbank_d, _ = _bank_grad(G, sv.att[-2], sv.bank_d, datt[-2])
+    return d_in, dcoef, dgf, dgt, dbank_d, (dgd, dbd), (dge, dbe)
+
+
+def _expand_bwd(blk, plan, sv, dz_e, res, datt):
+    """Data gradient (+ the skip gradient as its `res` operand) and per-sample weight gradients -> (dx, dw_e)."""
+    bank_e, att_e = sv.bank_e, sv.att[0]
+    dx = plan.dyn_pw(dz_e, bank_e, att_e, True, res=res)
+    dbank_e, _ = _dyn_pw_wgrad(dz_e, sv.x, bank_e, att_e, datt[0])
+    return dx, dbank_e.view_as(sv.w_e)
+
+
 class DyBlockMain(torch.autograd.Function):
     """Feature-map path of a fully dynamic DY_Block (models/dymn/dy_block.py:390-409) as one Function: dynamic expand
     1x1 -> BN -> act -> dynamic depthwise -> BN -> DyReLU-B * CoordAtt -> dynamic project 1x1 -> BN (+ residual).
@@ -630,131 +694,35 @@ class DyBlockMain(torch.autograd.Function):
     pass and enters the expand data-gradient GEMM as its `res` operand."""
 
     @staticmethod
-    def forward(ctx, blk, fused, hand_over, x, att, coef, g_cf, g_ct, w_e, w_d, w_p, ge, be, gd, bd, gp, bp):
-        cnf = blk.cnf
-        ctx.hand_over = hand_over
-        x = x.contiguous()
-        B, cin, Fq, T = x.shape
-        cexp, cout, k, stride = cnf.expanded_channels, cnf.out_channels, cnf.kernel, cnf.stride
-        act = HSWISH if cnf.use_hs else RELU
-        K = w_d.shape[2]
-        has_e = w_e is not None
-        att = att.contiguous()
-        att_e, att_d, att_p = (att[0], att[1], att[2]) if has_e else (None, att[0], att[1])
-        coef, g_cf, g_ct = coef.contiguous(), g_cf.contiguous(), g_ct.contiguous()
-        Fo, To = ops.conv_out(Fq, k, stride), ops.conv_out(T, k, stride)
-        # fused: round-4 kernels (per-plane taps in the register-resident depthwise kernels, one-wave-per-plane DyReLU on
-        # channel-major gates); otherwise the separate passes on position-major gates
-        # fused == 2: the bf16-storage plan (model.act_storage = "bf16"): z_e, z_d, x2 (and dx2, dv, g_e, dz_e in the backward)
-        # are bf16 in HBM, plain bf16 GEMM operands, statistics of the values as stored (include/eat_hip.h, "bf16 activation
-        # storage for the DyMN blocks"); block input / output, context path and per-sample weight gradients stay fp32
-        b16 = fused == 2
-        sv = {"fused": fused, "b16": b16}
-        taps = ops.dyn_aggregate(w_d.view(K, cexp * k * k), att_d)
-        if has_e and b16:
-            z_e, st_e = _dyn_pw_b16(x, w_e.view(K, cexp, cin), att_e, False, stats_bn=blk.exp_norm)
-            sv.update(z_e=z_e, st_e=st_e)
-        elif has_e:
-            z_e, st_e = _dyn_pw(x, w_e.view(K, cexp, cin), att_e, False, stats_bn=blk.exp_norm)
-            sv.update(z_e=z_e, st_e=st_e)
-        if fused:
-            # expand BatchNorm + activation on load, depth_norm's statistics in the epilogue: y_e is never written
-            z_d, parts = ops.dw_conv_dyn_stats(z_e if has_e else x, taps, k, stride,
-                                               tf=(st_e[0], st_e[1], act) if has_e else None, out_b16=b16)
-            st_d = ops.bn_state_from_partials(parts, blk.depth_norm, B * Fo * To) if blk.depth_norm.training else \
-                ops.bn_frozen_state(blk.depth_norm)
-            x2 = ops.dyrelu_ca_fwd2(z_d, st_d[0], st_d[1], coef, g_cf, g_ct)
+    def forward(ctx, blk, plan, hand_over, x, att, coef, g_cf, g_ct, w_e, w_d, w_p, ge, be, gd, bd, gp, bp):
+        act = HSWISH if blk.cnf.use_hs else RELU
+        sv = _DyState(x.contiguous(), att.contiguous(), coef.contiguous(), g_cf.contiguous(), g_ct.contiguous(), w_e, w_d, w_p)
+        sv.bank_e, sv.bank_d, sv.bank_p = _banks(blk, sv)
+        sv.taps = ops.dyn_aggregate(sv.bank_d, sv.att[-2])
+        _expand_fwd(blk, plan, sv)
+        if plan.merged:
+            _dw_merged_fwd(blk, plan, sv, act)
         else:
-            y_e = ops.bn_act_fwd(z_e, st_e[0], st_e[1], act) if has_e else x
-            z_d = torch.empty((B, cexp, Fo, To), device=x.device, dtype=torch.float32)
-            _lib.call("eat_dw_conv_dyn_fwd", y_e.data_ptr(), taps.data_ptr(), _zeros.get(cexp, x.device).data_ptr(), None,
-                      None, None, z_d.data_ptr(), B, cexp, Fq, T, Fo, To, k, stride, _s())
-            st_d = ops.bn_train_state(z_d, blk.depth_norm)
-            x2 = torch.empty_like(z_d)
-            _lib.call("eat_dyrelu_ca_fwd", z_d.data_ptr(), st_d[0].data_ptr(), st_d[1].data_ptr(), coef.data_ptr(),
-                      g_cf.data_ptr(), g_ct.data_ptr(), x2.data_ptr(), B, cexp, Fo, To, _s())
-            sv.update(y_e=y_e if has_e else None)
-        z_p, st_p = (_dyn_pw_b16 if b16 else _dyn_pw)(x2, w_p.view(K, cout, cexp), att_p, False, stats_bn=blk.proj_norm)
-        out = ops.bn_act_fwd(z_p, st_p[0], st_p[1], NONE, res=x if blk.use_res_connect else None)
-        sv.update(x=x, taps=taps, z_d=z_d, st_d=st_d, x2=x2, z_p=z_p, st_p=st_p, att=att, coef=coef, g_cf=g_cf, g_ct=g_ct,
-                  w_e=w_e, w_d=w_d, w_p=w_p)
-        ctx.sv, ctx.blk, ctx.act, ctx.prec = sv, blk, act, ops.precision.mode
+            _dw_separate_fwd(blk, sv, act)
+        out = _project_fwd(blk, plan, sv)
+        ctx.sv, ctx.blk, ctx.plan, ctx.act, ctx.hand_over, ctx.prec = sv, blk, plan, act, hand_over, ops.precision.mode
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        sv, blk, act = ctx.sv, ctx.blk, ctx.act
+        sv, blk, plan, act = ctx.sv, ctx.blk, ctx.plan, ctx.act
         ctx.sv = None
-        cnf = blk.cnf
-        x = sv["x"]
-        B, cin, Fq, T = x.shape
-        cexp, cout, k, stride = cnf.expanded_channels, cnf.out_channels, cnf.kernel, cnf.stride
-        w_e, w_d, w_p = sv["w_e"], sv["w_d"], sv["w_p"]
-        K = w_d.shape[2]
-        has_e = w_e is not None
-        att = sv["att"]
-        att_e, att_d, att_p = (att[0], att[1], att[2]) if has_e else (None, att[0], att[1])
         dout = dout.contiguous()
-        z_d, st_d = sv["z_d"], sv["st_d"]
-        Fo, To = z_d.shape[2], z_d.shape[3]
         res = dout if blk.use_res_connect else None
-        dge = dbe = None
-        with _in_precision(ctx):
-            # project: BN backward, data gradient, per-sample weight gradients
-            dz_p, dgp, dbp = ops.bn_act_bwd(dout, sv["z_p"], *sv["st_p"], NONE)
-            bank_p = w_p.view(K, cout, cexp)
-            dyn_pw = _dyn_pw_b16 if sv["b16"] else _dyn_pw
-            dx2 = dyn_pw(dz_p, bank_p, att_p, True)
-            # the attention gradients of the block's dynamic convs accumulate into ONE zeroed (n_att, B, K) tensor (was: three
-            # tensors + torch.stack)
-            datt = ops.zero_arena.zeros(tuple(att.shape), torch.float32, att.device)
-            dbank_p, _ = _dyn_pw_wgrad(dz_p, sv["x2"], bank_p, att_p, datt[-1])
-            if sv["fused"]:
-                # DyReLU-B * CoordAtt on the BatchNorm affine of z_d; the sums of depth_norm's backward leave its epilogue
-                dv, dcoef, dgf, dgt, bnpart = ops.dyrelu_ca_bwd2(dx2, z_d, st_d[0], st_d[1], sv["coef"], sv["g_cf"], sv["g_ct"])
-                sums_d, dgd, dbd = ops.bn_bwd_combine_partials(bnpart, bnpart.view(-1)[1:], 2, B, cexp, 1, st_d[2], st_d[3])
-                # merged depthwise backward: depth_norm's backward on load, tap gradients per plane, g_e = dy_e act'(.)
-                if has_e:
-                    st_e = sv["st_e"]
-                    g_e, G, parts = ops.dw_conv_dyn_bwd_bn_g(dv, z_d, st_d, NONE, sums_d, sv["taps"], sv["z_e"], st_e[0],
-                                                             st_e[1], act, k, stride)
-                    sums_e, dge, dbe = ops.bn_bwd_combine_partials(parts[0], parts[1], 1, B, cexp, parts[2], st_e[2], st_e[3])
-                    dz_e = ops.bn_bwd_apply(g_e, sv["z_e"], *st_e, sums_e)
-                else:
-                    one, zero = _ones.get(cexp, x.device), _zeros.get(cexp, x.device)
-                    dx, G, _ = ops.dw_conv_dyn_bwd_bn_g(dv, z_d, st_d, NONE, sums_d, sv["taps"], x, one, zero, NONE, k, stride,
-                                                        res=res, want_sums=False)
-            else:
-                dv, dcoef = torch.empty_like(z_d), torch.empty_like(sv["coef"])
-                dgf, dgt = torch.empty_like(sv["g_cf"]), torch.empty_like(sv["g_ct"])
-                _lib.call("eat_dyrelu_ca_bwd", dx2.data_ptr(), z_d.data_ptr(), st_d[0].data_ptr(), st_d[1].data_ptr(),
-                          sv["coef"].data_ptr(), sv["g_cf"].data_ptr(), sv["g_ct"].data_ptr(), dv.data_ptr(),
-                          dcoef.data_ptr(), dgf.data_ptr(), dgt.data_ptr(), B, cexp, Fo, To, _s())
-                dz_d, dgd, dbd = ops.bn_act_bwd(dv, z_d, *st_d, NONE)
-                y_e = sv["y_e"] if has_e else x
-                dy_e = torch.empty_like(y_e)
-                _lib.call("eat_dw_conv_dyn_dgrad", dz_d.data_ptr(), sv["taps"].data_ptr(),
-                          None if (has_e or res is None) else res.data_ptr(), dy_e.data_ptr(), B, cexp, Fq, T, Fo, To, k,
-                          stride, _s())
-                G = ops.zero_arena.zeros((B, cexp * k * k), torch.float32, x.device)
-                _lib.call("eat_dw_conv_dyn_wgrad", dz_d.data_ptr(), y_e.data_ptr(), G.data_ptr(), B, cexp, Fq, T, Fo, To, k,
-                          stride, _s())
-                if has_e:
-                    dz_e, dge, dbe = ops.bn_act_bwd(dy_e, sv["z_e"], *sv["st_e"], act)
-                else:
-                    dx = dy_e                        # (the skip connection's gradient entered the data gradient as `res`)
-            dbank_d, _ = _bank_grad(G, att_d, w_d.view(K, cexp * k * k), datt[-2])
-            if has_e:
-                bank_e = w_e.view(K, cexp, cin)
-                dx = dyn_pw(dz_e, bank_e, att_e, True, res=res)
-                dbank_e, _ = _dyn_pw_wgrad(dz_e, x, bank_e, att_e, datt[0])
-                dwe = dbank_e.view_as(w_e)
-            else:
-                dwe = None
+        with ops.precision(ctx.prec):
+            dx2, datt, dw_p, dgp, dbp = _project_bwd(blk, plan, sv, dout)
+            dw_bwd = _dw_merged_bwd if plan.merged else _dw_separate_bwd
+            d_in, dcoef, dgf, dgt, dw_d, (dgd, dbd), (dge, dbe) = dw_bwd(blk, sv, act, dx2, res, datt)
+            dx, dw_e = _expand_bwd(blk, plan, sv, d_in, res, datt) if sv.w_e is not None else (d_in, None)
         if ctx.hand_over is not None and ctx.needs_input_grad[3]:
             ctx.hand_over["dx"] = dx                  # collected (and added to the pools' gradient) by CtxPoolCm.backward
             dx = None
-        return (None, None, None, dx, datt, dcoef, dgf, dgt, dwe, dbank_d.view_as(w_d), dbank_p.view_as(w_p), dge, dbe, dgd,
+        return (None, None, None, dx, datt, dcoef, dgf, dgt, dw_e, dw_d.view_as(sv.w_d), dw_p.view_as(sv.w_p), dge, dbe, dgd,
                 dbd, dgp, dbp)
 
 
@@ -763,15 +731,18 @@ def _block_train_fused(blk, x):
     B, _, Fq, T = x.shape
     k, stride, cexp = cnf.kernel, cnf.stride, cnf.expanded_channels
     Fo, To = ops.conv_out(Fq, k, stride), ops.conv_out(T, k, stride)
-    fused = _FUSED_DW and To <= 512 and ops.dw_bwd_merged_ok((B, cexp, Fo, To), (B, cexp, Fq, T), k, stride)
-    if fused and _STORE16 and blk.depth_norm.training and ops.dyn_b16_block_ok(B, x.shape[1], cexp, cnf.out_channels, Fq, T, k, stride) \
-            and (blk.has_expand or (T > 128 and k == 3 and stride == 1)):
-        fused = 2                  # bf16 storage of this block's wide tensors (DyBlockMain); other blocks keep fp32 storage
+    cur = _passes[-1]
+    merged = bool(_FUSED_DW and To <= 512 and ops.dw_bwd_merged_ok((B, cexp, Fo, To), (B, cexp, Fq, T), k, stride))
+    # bf16 storage of this block's wide tensors; other blocks keep fp32 storage
+    store16 = bool(merged and cur.store16 and blk.depth_norm.training
+                   and ops.dyn_b16_block_ok(B, x.shape[1], cexp, cnf.out_channels, Fq, T, k, stride)
+                   and (blk.has_expand or (T > 128 and k == 3 and stride == 1)))
+    plan = _BlockPlan(merged, store16, _dyn_pw_b16 if store16 else _dyn_pw)
     # (x needs a gradient: then the context path's backward always runs after the main path's and collects its dx)
-    hand_over = {} if (fused and x.requires_grad) else None
-    if hand_over is not None:
-        _handovers.append(hand_over)
-    h_c, g_cf, g_ct = _context_cm(blk, x, hand_over) if fused else _context(blk, x)
+    hand_over = {} if (merged and x.requires_grad) else None
+    if hand_over is not None and cur.handovers is not None:
+        cur.handovers.append(hand_over)
+    h_c, g_cf, g_ct = _context_cm(blk, x, hand_over) if merged else _context(blk, x)
     convs = ([blk.exp_conv] if blk.has_expand else []) + [blk.depth_conv, blk.proj_conv]
     da = blk.depth_act
     wb = []
@@ -781,7 +752,7 @@ def _block_train_fused(blk, x):
     temps = tuple(float(cv.temperature) for cv in convs)
     att, coef = _HcHeads.apply(h_c, da.lambdas, da.init_v, temps, cnf.expanded_channels, *wb)
     e = blk.has_expand
-    return DyBlockMain.apply(blk, fused, hand_over, x, att, coef, g_cf, g_ct, blk.exp_conv.weight if e else None, blk.depth_conv.weight,
+    return DyBlockMain.apply(blk, plan, hand_over, x, att, coef, g_cf, g_ct, blk.exp_conv.weight if e else None, blk.depth_conv.weight,
                              blk.proj_conv.weight, blk.exp_norm.weight if e else None, blk.exp_norm.bias if e else None,
                              blk.depth_norm.weight, blk.depth_norm.bias, blk.proj_norm.weight, blk.proj_norm.bias)
 
@@ -806,36 +777,24 @@ def forward_train(model, x, return_fmaps=False):
     """Train-mode `(logits, embedding)` - or `(logits, fmaps)`, models/dymn/model.py:157-195 - of DyMN with autograd
     support (models/dymn/model.py:185-200).  The fully-convolutional head (:119-130) runs as torch ops on the last 4 x 32
     map (its class count, 527, is not a multiple of 4, which the library's data-gradient GEMM needs)."""
-    global _handovers
     prev = getattr(model, "_eat_handovers", None) or []
     dropped = any("dx" in h for h in prev)
-    model._eat_handovers = _handovers = []         # the hand-over dicts of THIS forward (filled by _block_train_fused)
+    model._eat_handovers = []                      # the hand-over dicts of THIS forward (filled by _block_train_fused)
     if dropped:
-        raise _lib.EatHipError("DyMN: the previous backward of this model ran only part of the graph - a dynamic block's input "
-                               "gradient was handed to its context path, whose backward never ran (torch.autograd.grad over "
-                               "a subset of the graph?).  The fused DyMN blocks need the whole backward; EAT_DYMN_FUSED_DW=0 "
-                               "selects the per-layer Functions, which have no such restriction.")
-    global _STORE16
+        raise EatHipError("DyMN: the previous backward of this model ran only part of the graph - a dynamic block's input "
+                          "gradient was handed to its context path, whose backward never ran (torch.autograd.grad over "
+                          "a subset of the graph?).  The fused DyMN blocks need the whole backward; EAT_DYMN_FUSED_DW=0 "
+                          "selects the per-layer Functions, which have no such restriction.")
     prec = getattr(model, "train_precision", "fp32")
     st = getattr(model, "act_storage", "fp32")
     if st not in ("fp32", "bf16"):
-        raise _lib.EatHipError(f"act_storage must be 'fp32' or 'bf16' (got {st!r})")
+        raise EatHipError(f"act_storage must be 'fp32' or 'bf16' (got {st!r})")
     if st == "bf16" and prec != "bf16":
-        raise _lib.EatHipError("act_storage='bf16' needs train_precision='bf16' (plain bf16 GEMM operands): the split-operand "
-                               "modes keep fp32-class products, which a bf16-stored operand cannot feed")
+        raise EatHipError("act_storage='bf16' needs train_precision='bf16' (plain bf16 GEMM operands): the split-operand "
+                          "modes keep fp32-class products, which a bf16-stored operand cannot feed")
     ops.zero_arena.begin("dymn_step")          # one zero-filled arena per step (forward + the backward autograd runs later)
-    global _PLAN
-    _STORE16 = st == "bf16"
-    try:
-        with ops.precision(prec), ops.bn_counters:
-            plan = _static_prepack_plan(model)
-            if plan is not None:
-                plan.run()
-                _PLAN = (plan, plan.runs)
-            out = _forward_train(model, x, return_fmaps)
-    finally:
-        _STORE16 = False
-        _PLAN = (None, 0)
+    with ops.precision(prec), ops.bn_counters, _running_pass(st == "bf16", _static_prepack_plan(model), model._eat_handovers):
+        out = _forward_train(model, x, return_fmaps)
     if out[0].requires_grad:
         # the arena closes when THIS backward pass is over, whichever node runs last (a frozen stem never runs its backward;
         # ADVICE r5): the first gradient to arrive queues an engine callback, which fires after the last node of the pass

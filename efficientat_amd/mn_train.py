@@ -44,19 +44,7 @@ _CAST_NARROW_MIN_CEXP = 200
 _GSTATS_MIN_ELEMS = 1 << 26
 
 
-class _Fill:
-    """Cached constant vector (zeros: the bias of the train-mode convs, whose entry points take a bias pointer)."""
-
-    def __init__(self, value):
-        self.value, self.buf = value, None
-
-    def get(self, n, device):
-        if self.buf is None or self.buf.numel() < n or self.buf.device != device:
-            self.buf = torch.full((max(n, 4096),), self.value, device=device, dtype=torch.float32)
-        return self.buf[:n]
-
-
-_zeros, _ones = _Fill(0.0), _Fill(1.0)
+_zeros, _ones = ops.zeros_vec, ops.ones_vec           # cached constant vectors (the bias pointer of the train-mode convs)
 
 
 def _prepack_plan(model):

@@ -48,6 +48,26 @@ def _dev16(t, name):
 def _is16(t):
     return t is not None and t.dtype == torch.bfloat16
 
+
+class _ConstVec:
+    """Cached constant fp32 vector, one buffer per device (zeros: the bias of the train-mode convs, whose entry points take a
+    bias pointer; ones: the identity BatchNorm scale).  A buffer that has been handed out is never freed - a captured graph
+    may hold its address - so one that has to grow keeps its predecessors alive."""
+
+    def __init__(self, value):
+        self.value, self.bufs, self.outgrown = value, {}, []
+
+    def get(self, n, device):
+        buf = self.bufs.get(device)
+        if buf is None or buf.numel() < n:
+            if buf is not None:
+                self.outgrown.append(buf)
+            buf = self.bufs[device] = torch.full((max(n, 4096),), self.value, device=device, dtype=torch.float32)
+        return buf[:n]
+
+
+zeros_vec, ones_vec = _ConstVec(0.0), _ConstVec(1.0)
+
 _KCAT = True   # K-concat form of the late dynamic 1x1 convs (eval; `kcat_eligible`)
 
 
@@ -120,7 +140,7 @@ def dw_conv_dyn_dilated(x, taps, k, stride, dilation):
     B, C, F, T = x.shape
     Fo, To = dilated_out(F, T, k, stride, dilation)
     y = torch.empty((B, C, Fo, To), device=x.device, dtype=torch.float32)
-    zb = _zero_bias(min(B, 65535 // C + 1) * C, x.device)
+    zb = zeros_vec.get(min(B, 65535 // C + 1) * C, x.device)
     for b0, b1 in _plane_chunks(B, C):
         n = (b1 - b0) * C
         _lib.call("eat_dw_conv_dilated_fwd", _dev(x, "x") + 4 * b0 * C * F * T, _dev(taps, "taps") + 4 * b0 * C * k * k,
@@ -160,10 +180,7 @@ def dyrelu_ca(z, a, b, act, coef, gate_f, gate_t):
     if gate_f is None:
         gate_f = torch.full((B * Fo, C), 40.0, device=z.device)
         gate_t = torch.full((B * To, C), 40.0, device=z.device)
-    out = torch.empty_like(z)
-    _lib.call("eat_dyrelu_ca_fwd", _dev(z, "z"), _opt(a, "a"), _opt(b, "b"), _dev(coef.contiguous(), "coef"),
-              _dev(gate_f.contiguous(), "gate_f"), _dev(gate_t.contiguous(), "gate_t"), out.data_ptr(), B, C, Fo, To, _stream())
-    return out
+    return dyrelu_ca_fwd(z, a, b, coef.contiguous(), gate_f.contiguous(), gate_t.contiguous())
 
 
 def dw_conv_dilated_dgrad(dz, w, x_shape, k, stride, dilation):
@@ -193,7 +210,7 @@ def dw_conv_tf(x, in_a, in_b, in_act, w, bias, k, stride):
     return y
 
 
-def pw_prepack(w2d, row_scale=None, trans=False):
+def _pw_prepack_fp32(w2d, row_scale=None, trans=False):
     """trans: pack w2d^T (w2d is the stored (Ci, Co) matrix) - the data-gradient GEMM without a transposed copy."""
     Co, Ci = (w2d.shape[1], w2d.shape[0]) if trans else w2d.shape
     wp = torch.empty(((Ci // 4) * ((Co + 15) // 16) * 64,), device=w2d.device, dtype=torch.float32)
@@ -202,7 +219,7 @@ def pw_prepack(w2d, row_scale=None, trans=False):
     return wp
 
 
-def pw_conv(x, wp, bias, Co, act, in_scale=None, res=None, pool=None, write=True):
+def _pw_conv_fp32(x, wp, bias, Co, act, in_scale=None, res=None, pool=None, write=True):
     B, Ci, F, T = x.shape
     y = torch.empty((B, Co, F, T), device=x.device, dtype=torch.float32) if write else None
     _lib.call("eat_pw_conv_fwd", _dev(x, "x"), _dev(wp, "wp"), _dev(bias, "bias"), _opt(in_scale, "in_scale"),
@@ -862,7 +879,7 @@ def expand_bwd_coef(W, Gx, Tm, sx, gparts, a, mean, invstd, n, frozen=False, nee
         # bf16x3 kernel (fp32-class products; round 5: the K-split `linear` kernel ran these C_in x C_in x C_exp products at
         # 15 TFLOP/s - 14 launches of up to 213 us in the mn40 step)
         wp3 = pw_prepack_bf16(w2e, None, split=True)
-        Mc = pw_conv_bf16(W.view(1, Co, Ci, 1), wp3, _zero_bias(Ci + 1, dev), Ci + 1, ACT_NONE, split=True).view(Ci + 1, Ci)
+        Mc = pw_conv_bf16(W.view(1, Co, Ci, 1), wp3, zeros_vec.get(Ci + 1, dev), Ci + 1, ACT_NONE, split=True).view(Ci + 1, Ci)
     else:
         Mc = linear(w2e, tr[1], None, ACT_NONE)                            # [W2T ; e1] . WT^T -> (Ci + 1, Ci)
     return dW, vec[0], vec[1], tr[0], Mc[:Ci], Mc[Ci]
@@ -911,6 +928,14 @@ def ctx_pool(x):
     return seq
 
 
+def ctx_pool_bwd(dseq, shape):
+    """dseq (B, F+T, C) -> dx (B, C, F, T) of `ctx_pool`."""
+    B, C, F, T = shape
+    dx = torch.empty(shape, device=dseq.device, dtype=torch.float32)
+    _lib.call("eat_ctx_pool_bwd", _dev(dseq, "dseq"), None, dx.data_ptr(), B, C, F, T, _stream())
+    return dx
+
+
 def dyn_aggregate(bank, att, gscale=None, group=1):
     K, N = bank.shape
     B = att.shape[0]
@@ -918,6 +943,40 @@ def dyn_aggregate(bank, att, gscale=None, group=1):
     _lib.call("eat_dyn_aggregate", _dev(bank, "bank"), _dev(att, "att"), _opt(gscale, "gscale"), out.data_ptr(), B, K,
               N, group, _stream())
     return out
+
+
+def dyn_bank_grad(G, att, bank, datt=None):
+    """Gradients of the kernel aggregation W_b = sum_k att[b,k] bank[k] from the per-sample weight gradients G (B, N):
+    -> (dbank (K, N) = att^T G, datt (B, K) = G bank^T).  datt: zeroed (B, K) memory to accumulate into (a slice of a
+    block's (n_att, B, K) tensor), or None."""
+    B, K, N = att.shape[0], bank.shape[0], bank.shape[1]
+    dbank = torch.empty_like(bank)
+    if datt is None:
+        datt = zero_arena.zeros(tuple(att.shape), torch.float32, att.device)
+    _lib.call("eat_dyn_bank_grad", _dev(G, "G"), _dev(att, "att"), _dev(bank, "bank"), dbank.data_ptr(), _dev(datt, "datt"),
+              B, K, N, _stream())
+    return dbank, datt
+
+
+def dyn_heads_fwd(y, n_att, K, cexp, inv_t, lam, iv):
+    """Pointwise tails of the Linear layers that read h_c, y (B, n_att*K + 4*cexp) being their row-concatenated output:
+    -> (att (n_att, B, K) = softmax(logits * inv_t), sg (B, 4*cexp) = sigmoid(.), coef (B, cexp, 4) = (2 sg - 1) * lam + iv)."""
+    B = y.shape[0]
+    att = torch.empty((n_att, B, K), device=y.device, dtype=torch.float32)
+    sg = torch.empty((B, 4 * cexp), device=y.device, dtype=torch.float32)
+    coef = torch.empty((B, cexp, 4), device=y.device, dtype=torch.float32)
+    _lib.call("eat_dyn_heads_fwd", _dev(y, "y"), B, n_att, K, cexp, inv_t[0], inv_t[1], inv_t[2], _dev(lam, "lambdas"),
+              _dev(iv, "init_v"), att.data_ptr(), sg.data_ptr(), coef.data_ptr(), _stream())
+    return att, sg, coef
+
+
+def dyn_heads_bwd(datt, dcoef, att, sg, lam, cexp, inv_t):
+    """-> dy (B, n_att*K + 4*cexp) of `dyn_heads_fwd`."""
+    n_att, B, K = att.shape
+    dy = torch.empty((B, n_att * K + 4 * cexp), device=att.device, dtype=torch.float32)
+    _lib.call("eat_dyn_heads_bwd", _dev(datt, "datt"), _dev(dcoef, "dcoef"), _dev(att, "att"), _dev(sg, "sg"),
+              _dev(lam, "lambdas"), B, n_att, K, cexp, inv_t[0], inv_t[1], inv_t[2], dy.data_ptr(), _stream())
+    return dy
 
 
 def dyn_pw_pack(bank, att, Co, Ci, row_scale=None, trans=False):
@@ -935,6 +994,18 @@ def pw_conv_dyn(x, wp_b, bias, Co, act, res=None):
     _lib.call("eat_pw_conv_dyn_fwd", _dev(x, "x"), _dev(wp_b, "wp_b"), _dev(bias, "bias"), _opt(res, "res"),
               y.data_ptr(), B, Ci, Co, F * T, act, _stream())
     return y
+
+
+def pw_conv_dyn_wgrad(dz, x):
+    """Per-sample weight gradients G (B, Co*Ci) = dz[b] x[b]^T on the per-(tile, sample) kernels (fp32 operands)."""
+    B, Co, Ci = dz.shape[0], dz.shape[1], x.shape[1]
+    S = x.shape[2] * x.shape[3]
+    if dyn_wgrad_needs_zero(Co, Ci, S):
+        G = zero_arena.zeros((B, Co * Ci), torch.float32, x.device)
+    else:                                       # bf16x3 kernel in per-sample mode: plain stores
+        G = torch.empty((B, Co * Ci), device=x.device, dtype=torch.float32)
+    _lib.call("eat_pw_conv_dyn_wgrad", _dev(dz, "dz"), _dev(x, "x"), G.data_ptr(), B, Co, Ci, S, _stream())
+    return G
 
 
 def dyn_bf16_eligible(Co, Ci, S):
@@ -999,12 +1070,53 @@ def pw_conv_kcat(x, wp_cat, bias, att, Co, act, res=None):
 
 
 def dw_conv_dyn(x, w_bc, bias, coef, gate_f, gate_t, k, stride):
+    """Depthwise conv with per-(b,c) taps w_bc (B, C*k*k); coef / gates None: the plain conv of the training step, whose
+    DyReLU-B * CoordAtt runs after the BatchNorm (`dyrelu_ca_fwd`)."""
     B, C, F, T = x.shape
     Fo, To = conv_out(F, k, stride), conv_out(T, k, stride)
     y = torch.empty((B, C, Fo, To), device=x.device, dtype=torch.float32)
-    _lib.call("eat_dw_conv_dyn_fwd", _dev(x, "x"), _dev(w_bc, "w_bc"), _dev(bias, "bias"), _dev(coef, "coef"),
-              _dev(gate_f, "gate_f"), _dev(gate_t, "gate_t"), y.data_ptr(), B, C, F, T, Fo, To, k, stride, _stream())
+    _lib.call("eat_dw_conv_dyn_fwd", _dev(x, "x"), _dev(w_bc, "w_bc"), _dev(bias, "bias"), _opt(coef, "coef"),
+              _opt(gate_f, "gate_f"), _opt(gate_t, "gate_t"), y.data_ptr(), B, C, F, T, Fo, To, k, stride, _stream())
     return y
+
+
+def dw_conv_dyn_dgrad(dz, w_bc, x_shape, k, stride, res=None):
+    """Data gradient of `dw_conv_dyn` (+ res, the skip connection's gradient)."""
+    B, C, F, T = x_shape
+    dx = torch.empty((B, C, F, T), device=dz.device, dtype=torch.float32)
+    _lib.call("eat_dw_conv_dyn_dgrad", _dev(dz, "dz"), _dev(w_bc, "w_bc"), _opt(res, "res"), dx.data_ptr(), B, C, F, T,
+              dz.shape[2], dz.shape[3], k, stride, _stream())
+    return dx
+
+
+def dw_conv_dyn_wgrad(dz, x, k, stride, out=None):
+    """Per-plane tap gradients G (B, C*k*k) of `dw_conv_dyn`, accumulated with atomics.  out: ZERO-FILLED memory for G."""
+    B, C, F, T = x.shape
+    G = out if out is not None else torch.zeros((B, C * k * k), device=x.device, dtype=torch.float32)
+    _lib.call("eat_dw_conv_dyn_wgrad", _dev(dz, "dz"), _dev(x, "x"), _dev(G, "G"), B, C, F, T, dz.shape[2], dz.shape[3], k,
+              stride, _stream())
+    return G
+
+
+def dyrelu_ca_fwd(z, a, b, coef, gate_f, gate_t):
+    """out = max(a1 v + b1, a2 v + b2) * sigmoid(gate_f) * sigmoid(gate_t), v = a[c] z + b[c] (a, b None: v = z); coef (B, C, 4),
+    position-major pre-sigmoid gates (B*Fo, C) / (B*To, C)."""
+    B, C, Fo, To = z.shape
+    out = torch.empty_like(z)
+    _lib.call("eat_dyrelu_ca_fwd", _dev(z, "z"), _opt(a, "a"), _opt(b, "b"), _dev(coef, "coef"), _dev(gate_f, "gate_f"),
+              _dev(gate_t, "gate_t"), out.data_ptr(), B, C, Fo, To, _stream())
+    return out
+
+
+def dyrelu_ca_bwd(dout, z, a, b, coef, gate_f, gate_t):
+    """-> (dv, dcoef, dgate_f, dgate_t) of `dyrelu_ca_fwd`, dv being the gradient of v = a[c] z + b[c]."""
+    B, C, Fo, To = z.shape
+    dv, dcoef = torch.empty_like(z), torch.empty_like(coef)
+    dgf, dgt = torch.empty_like(gate_f), torch.empty_like(gate_t)
+    _lib.call("eat_dyrelu_ca_bwd", _dev(dout, "dout"), _dev(z, "z"), _opt(a, "a"), _opt(b, "b"), _dev(coef, "coef"),
+              _dev(gate_f, "gate_f"), _dev(gate_t, "gate_t"), dv.data_ptr(), dcoef.data_ptr(), dgf.data_ptr(), dgt.data_ptr(), B, C,
+              Fo, To, _stream())
+    return dv, dcoef, dgf, dgt
 
 
 def dw_conv_dyn_act(x, w_bc, bias, act, coef, gate_f, gate_t, k, stride):
@@ -1030,7 +1142,7 @@ def pw_conv_stats(x, wp, Co, per_sample=False, tf=None, in_scale=None):
     part = torch.empty((tiles * 2 * Co,), device=x.device, dtype=torch.float32)
     a, b, act = tf if tf is not None else (None, None, 0)
     rc = _lib.call_rc("eat_pw_conv_stats_fwd", _dev(x, "x"), wp.data_ptr(), wmode, 1 if per_sample else 0, _opt(a, "tf_a"),
-                      _opt(b, "tf_b"), act, _opt(in_scale, "in_scale"), _zero_bias(Co, x.device).data_ptr(), y.data_ptr(),
+                      _opt(b, "tf_b"), act, _opt(in_scale, "in_scale"), zeros_vec.get(Co, x.device).data_ptr(), y.data_ptr(),
                       part.data_ptr(), B, Ci, Co, S, _stream())
     if rc == 1:
         return None, None
@@ -1056,7 +1168,7 @@ def pw_conv_gstats(x, wp, Co, z, st, act, sums=None):
     tiles = int(_lib.lib().eat_pw_conv_stat_tiles(B, S, 0))
     y = torch.empty((B, Co, F, T), device=x.device, dtype=torch.float32)
     part = torch.empty((tiles * 2 * Co,), device=x.device, dtype=torch.float32)
-    rc = _lib.call_rc("eat_pw_conv_gstats_fwd", _dev(x, "x"), wp.data_ptr(), wmode, _zero_bias(Co, x.device).data_ptr(),
+    rc = _lib.call_rc("eat_pw_conv_gstats_fwd", _dev(x, "x"), wp.data_ptr(), wmode, zeros_vec.get(Co, x.device).data_ptr(),
                       y.data_ptr(), _dev(z, "z"), a.data_ptr(), b.data_ptr(), act, part.data_ptr(), B, Ci, Co, S, _stream())
     if rc == 1:
         return None, None
@@ -1067,16 +1179,6 @@ def pw_conv_gstats(x, wp, Co, z, st, act, sums=None):
     _lib.call("eat_bn_bwd_sums_from_tiles", part.data_ptr(), tiles, Co, mean.data_ptr(), invstd.data_ptr(), a.data_ptr(),
               b.data_ptr(), None if ws is None else ws.data_ptr(), sums.data_ptr(), _stream())
     return y, sums
-
-
-_zb = {}
-
-
-def _zero_bias(n, device):
-    buf = _zb.get(device)
-    if buf is None or buf.numel() < n:
-        buf = _zb[device] = torch.zeros((max(n, 4096),), device=device, dtype=torch.float32)
-    return buf[:n]
 
 
 # ---- round 4: fused training passes of the dynamic block (csrc/dymn.hip, csrc/dw_plane.hip)
@@ -1398,7 +1500,7 @@ def pw_conv_dyn_b16(x, wp_b, Co, act, res=None, stats=False):
         tiles = int(_lib.lib().eat_pw_conv_stat_tiles(B, S, 1))
         part = torch.empty((tiles * 2 * Co,), device=x.device, dtype=torch.float32)
     _lib.call("eat_pw_conv_dyn_b16_fwd", _dev16(x, "x") if x16 else _dev(x, "x"), 1 if x16 else 0, wp_b.data_ptr(),
-              _zero_bias(Co, x.device).data_ptr(), _opt(res, "res"), y.data_ptr(), 0 if x16 else 1,
+              zeros_vec.get(Co, x.device).data_ptr(), _opt(res, "res"), y.data_ptr(), 0 if x16 else 1,
               None if part is None else part.data_ptr(), B, Ci, Co, S, act, _stream())
     return (y, (part, tiles, 1)) if stats else y
 
@@ -1441,22 +1543,27 @@ class precision:
         precision.mode = self.old
 
 
-_pw_prepack_fp32, _pw_conv_fp32 = pw_prepack, pw_conv
-
-
-def pw_prepack(w2d, row_scale=None, trans=False):  # noqa: F811
+def _pack_kind(Ci):
+    """Pack of a static 1x1 conv with Ci input channels under the active `precision`: 0 fp32 fragments, 1 plain bf16,
+    2 split bf16 hi / lo ('bf16x3' everywhere, 'auto' from C_in = 40 on)."""
     m = precision.mode
-    ci = w2d.shape[0] if trans else w2d.shape[1]
     if m == "bf16":
+        return 1
+    return 2 if m == "bf16x3" or (m == "auto" and Ci >= 40 and Ci % 4 == 0) else 0
+
+
+def pw_prepack(w2d, row_scale=None, trans=False):
+    kind = _pack_kind(w2d.shape[0] if trans else w2d.shape[1])
+    if kind == 1:
         return pw_prepack_bf16(w2d, row_scale, split=False, trans=trans)
-    if m == "bf16x3" or (m == "auto" and ci >= 40 and ci % 4 == 0):
+    if kind == 2:
         wp = pw_prepack_bf16(w2d, row_scale, split=True, trans=trans)
         wp._eat_split = True                 # both bf16 packs share the dtype: mark the hi/lo one
         return wp
     return _pw_prepack_fp32(w2d, row_scale, trans=trans)
 
 
-def pw_conv(x, wp, bias, Co, act, in_scale=None, res=None, pool=None, write=True):  # noqa: F811
+def pw_conv(x, wp, bias, Co, act, in_scale=None, res=None, pool=None, write=True):
     if wp.dtype == torch.bfloat16:
         return pw_conv_bf16(x, wp, bias, Co, act, getattr(wp, "_eat_split", False), in_scale=in_scale, res=res,
                             pool=pool, write=write)
@@ -1479,13 +1586,7 @@ class PrepackPlan:
                 raise _lib.EatHipError("PrepackPlan: weights must be contiguous")
             rows, cols = w2d.shape[0], w2d.numel() // w2d.shape[0]
             Co, Ci = (cols, rows) if trans else (rows, cols)
-            m = self.mode
-            if m == "bf16":
-                kind = 1
-            elif m == "bf16x3" or (m == "auto" and Ci >= 40 and Ci % 4 == 0):
-                kind = 2
-            else:
-                kind = 0
+            kind = _pack_kind(Ci)
             mt = (Co + 15) // 16
             if kind == 0:
                 if Ci % 4:
@@ -1509,6 +1610,21 @@ class PrepackPlan:
         self.keep = [r[0] for r in recs]
         self.views, self.n, self.max_threads = views, len(recs), max_threads
         self.table = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
+
+    @classmethod
+    def of_weights(cls, weights):
+        """The plan with the forward and the data-gradient pack of every distinct matrix of `weights` (`view(w, trans)` finds
+        them); None for an empty list."""
+        entries, seen = [], set()
+        for w in weights:
+            if w.data_ptr() not in seen:
+                seen.add(w.data_ptr())
+                entries += [((w.data_ptr(), False), w, False), ((w.data_ptr(), True), w, True)]
+        return cls(entries) if entries else None
+
+    def view(self, w, trans):
+        """The pack of parameter `w` in a plan built by `of_weights`, or None if it holds none."""
+        return self.views.get((w.data_ptr(), trans))
 
     def stale(self):
         """Parameters were re-allocated (model.to(), a new state dict with fresh storage) or the arithmetic changed."""
