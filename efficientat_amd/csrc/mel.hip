@@ -115,11 +115,14 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(
 
   // Raw samples of one frame: lane holds frame positions n = 2*(lane + 64 r) + e.  Interior frames (no reflection):
   // (x[j], x[j+1]) as one aligned 8-byte load and x[j+2] as a third word - raw[r] = (x0, x1, x2), pre-emphasised later.
+  // "Aligned" is a property of the ADDRESS x + q0, not of q0 and L alone: a row of an odd-length batch, or a wave that is
+  // a view at an odd element offset of a larger buffer, starts on a 4-byte boundary - those frames take the edge path.
   // Edge frames (first / last two of a clip): raw[r] = (pre[n], pre[n+1], -) computed here.  All loads are
   // unconditional so they issue back to back; the next frame's loads are issued before the current frame's FFT.
+  const int x_odd = static_cast<int>(reinterpret_cast<size_t>(x) >> 2) & 1;   // x sits on an odd 4-byte word
   auto load_frame = [&](int t, float (&raw)[8][3]) -> bool {
     const int q0 = t * hop - kNfft / 2;        // padded-signal origin of this frame, in pre[] indices
-    if (q0 >= 0 && q0 + kNfft <= Lp && ((q0 | L) & 1) == 0) {
+    if (q0 >= 0 && q0 + kNfft <= Lp && ((q0 + x_odd) & 1) == 0) {
       const float* xf = x + q0 + 2 * lane;
 #pragma unroll
       for (int r = 0; r < 8; ++r) {

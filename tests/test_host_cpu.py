@@ -403,3 +403,115 @@ def test_hdf5_reader_round_trip(tmp_path, monkeypatch):
     assert x.shape == (1, 10 * sr) and x.dtype == np.float32 and name == "clip1" and y.shape == (527,) and y[1] == 1.0
     assert 0.1 < np.abs(x[0, :2 * sr]).max() < 0.5 and np.abs(x[0, 3 * sr:]).max() == 0.0        # decoded tone, zero padding
     assert ds.targets().shape == (n, 527)
+
+
+# ------------------------------------------------------------------ mel tables beyond the default geometry
+def _default_fmax(sr):
+    return sr // 2 - 1000
+
+
+def _dense_from_table(table, nb=512):
+    """The dense basis a band table stands for, from ALL its pairs (not only the cnt[m] the kernel must walk)."""
+    w2, st, cnt = table
+    P, n_mels, _ = w2.shape
+    d = torch.zeros(n_mels, nb)
+    for m in range(n_mels):
+        d[m, int(st[m]):int(st[m]) + 2 * P] = w2[:, m, :].reshape(-1)
+    return d
+
+
+@pytest.mark.parametrize("sr", [16000, 32000, 44100])
+@pytest.mark.parametrize("n_mels", [1, 8, 40, 63, 64, 65, 129, 256])
+def test_band_table_round_trips_at_other_mel_counts_and_rates(n_mels, sr):
+    """band_table -> dense is the identity (bit-equal) for tight and fixed-width tables, incl. all-zero mel rows."""
+    basis = kaldi_mel_basis(n_mels, 1024, sr, 0.0, _default_fmax(sr))
+    assert torch.equal(basis, O.kaldi_mel_banks(n_mels, 1024, sr, 0.0, float(_default_fmax(sr)))[:, :512])
+    empty = ~(basis != 0).any(dim=1)
+    if (n_mels, sr) == (256, 32000):
+        assert int(empty.sum()) >= 1                              # 13 where this was written
+    tight = band_table(basis)
+    widest = tight[0].shape[0]
+    assert int(tight[2].max()) == widest or not (basis != 0).any()
+    for pairs in (None, min(256, widest + 3), 256):
+        w2, st, cnt = table = band_table(basis, pairs=pairs)
+        P = w2.shape[0]
+        assert P == (widest if pairs is None else pairs) and w2.shape == (P, n_mels, 2)
+        assert st.dtype == torch.int32 and cnt.dtype == torch.int32
+        assert not (st % 2).any() and int(st.min()) >= 0 and int(st.max()) + 2 * P <= 512
+        assert int(cnt.min()) >= 0 and int(cnt.max()) <= P
+        assert torch.equal(cnt == 0, empty)
+        for m in range(n_mels):
+            assert not w2[int(cnt[m]):, m, :].any()               # the kernel stops after max(cnt) pairs per 64 rows
+        assert torch.equal(_dense_from_table(table), basis)
+    if widest > 1:
+        with pytest.raises(ValueError):
+            band_table(basis, pairs=widest - 1)
+
+
+def test_band_table_round_trips_at_128_mels_44100():
+    basis = kaldi_mel_basis(128, 1024, 44100, 0.0, 21050)
+    assert int((~(basis != 0).any(dim=1)).sum()) >= 1             # 1 where this was written
+    for pairs in (None, 16, 64):
+        table = band_table(basis, pairs=pairs)
+        assert torch.equal(_dense_from_table(table), basis) and int((table[2] == 0).sum()) >= 1
+
+
+def _widest_pairs(basis):
+    return band_table(basis)[0].shape[0]
+
+
+# (n_mels, sr, module kwargs, widest band of the whole jitter space by brute force, one draw that has it, static P)
+JITTER_SPACES = [
+    (128, 32000, {}, 14, (0, 15952), 15),
+    (40, 32000, {}, 39, (0, 15750), 40),
+    (64, 32000, {}, 26, (0, 15876), 27),
+    (128, 44100, {}, 15, (0, 21620), 16),
+    (64, 16000, dict(fmax_aug_range=1000), 22, (0, 7938), 23),
+]
+
+
+@pytest.mark.parametrize("n_mels,sr,kw,worst,worst_at,P", JITTER_SPACES,
+                         ids=[f"mels{c[0]}_sr{c[1]}" for c in JITTER_SPACES])
+def test_max_band_pairs_bounds_the_jitter_space(n_mels, sr, kw, worst, worst_at, P):
+    """A captured trainer stages band_table(..., pairs=max_band_pairs()) every step and raises mid-run if one draw needs
+    more.  Sweep of the (fmin, fmax) draw space: every fmin, fmax with a stride of 8 (the full 20000-draw sweep, which
+    gave the `worst` recorded above, takes ~10 s per space), plus the corners and the recorded widest draw.  `worst` is
+    a record, not a bar: the last non-zero of a filter is an fp32 value next to zero whose sign the host's log decides,
+    so the width at one draw can differ by a pair between hosts.  The bar is P."""
+    mel = _quiet(AugmentMelSTFT, n_mels=n_mels, sr=sr, **kw)
+    assert mel.max_band_pairs() == P and worst <= P
+    hi = mel.fmax + mel.fmax_aug_range // 2
+    lo = hi - mel.fmax_aug_range + 1
+    fmins = range(int(mel.fmin), int(mel.fmin) + mel.fmin_aug_range)
+    draws = {(a, b) for a in fmins for b in list(range(lo, hi + 1, 8)) + [lo, hi, mel.fmax]} | {worst_at}
+    seen = max(_widest_pairs(kaldi_mel_basis(n_mels, 1024, sr, a, b)) for a, b in sorted(draws))
+    assert P - 2 <= seen <= P, (seen, worst, P)          # P is the widest corner + 2
+    # and the fixed-width table of the widest draw is the same basis
+    basis = kaldi_mel_basis(n_mels, 1024, sr, *worst_at)
+    assert torch.equal(_dense_from_table(band_table(basis, pairs=P)), basis)
+
+
+def test_draw_computes_the_frame_count_the_kernel_demands():
+    """For every geometry of tests/test_gpu_mel_geometry.py: the T that draw() hands to the time-mask draw is the T the
+    entry point demands (1 + (L-1) // hop) and the number of frames the oracle's STFT yields, and both mask draws stay
+    inside their axes.  Mask parameters are capped at the axis length, which is torchaudio's precondition for
+    mask_along_axis (a larger one draws a negative start; the kernel then masks nothing, like torchaudio's compare)."""
+    from tests import mel_cases as MC
+    for _, cid, L, _, geom in MC.ALL:
+        g = MC.full_geom(geom)
+        T = MC.frames(L, g["hopsize"])
+        ref = O.mel_forward(torch.zeros(1, L), **g)
+        assert ref.shape == (1, g["n_mels"], T), cid
+        mel = _quiet(AugmentMelSTFT, n_mels=g["n_mels"], sr=g["sr"], win_length=g["win_length"], hopsize=g["hopsize"],
+                     fmin=g["fmin"], fmax=g["fmax"], freqm=min(48, g["n_mels"]), timem=min(192, T)).train()
+        sizes = []
+        real = mel._draw_mask
+        mel._draw_mask = lambda param, size: (sizes.append((param, size)), real(param, size))[1]
+        torch.manual_seed(len(cid))
+        for _ in range(50):
+            fmin, fmax, fmask, tmask = mel.draw(L)
+            assert g["fmin"] <= fmin < g["fmin"] + 10 and g["fmax"] - 1000 < fmax <= g["fmax"] + 1000
+            assert 0 <= fmask[0] <= fmask[1] <= g["n_mels"], (cid, fmask)
+            assert 0 <= tmask[0] <= tmask[1] <= T, (cid, tmask)
+        assert set(sizes) == {(mel.freqm, g["n_mels"]), (mel.timem, T)}, cid
+        assert mel.eval().draw(L) == (g["fmin"], g["fmax"], (0, 0), (0, 0))
