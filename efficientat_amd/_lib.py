@@ -154,6 +154,10 @@ SIGNATURES = {
     # single-label fine-tuning (finetune.py)
     "eat_softmax_ce_fwd_bwd": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     "eat_wave_augment": [_P, _P, _P, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
+    # OpenMIC fine-tuning (finetune.py): masked BCE, wave-mix labels, masked ranking metrics
+    "eat_masked_bce_fwd_bwd": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, ctypes.c_longlong, _P],
+    "eat_openmic_targets": [_P, ctypes.c_longlong, _I, _P, _P, _P, _I, _P],
+    "eat_rank_metrics_masked": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 
 RESTYPES = {"eat_rank_metrics_ws_bytes": ctypes.c_longlong}   # every other entry point returns int

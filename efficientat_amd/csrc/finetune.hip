@@ -4,6 +4,10 @@
 //                           (ex_esc50.py:102-118 training, :154-178 evaluation)
 //   eat_wave_augment        gain + roll + wave-mix of clips gathered from a device-resident bank (datasets/esc50.py gain and
 //                           pad, datasets/helpers/audiodatasets.py roll, MixupDataset), and the matching target rows
+// and the multi-label, partially observed variant of ex_openmic.py:
+//   eat_masked_bce_fwd_bwd  BCE-with-logits times the "this label was annotated" mask, the mix-up of the binarized labels
+//                           folded in, its gradient, the per-row loss and sigmoid(z) in one pass (ex_openmic.py:102-121, :160-187)
+//   eat_openmic_targets     the label rule of OpenMIC's MixupDataset (datasets/openmic.py:74-95) for the rows of a wave-mixed batch
 #include "eat_common.h"
 
 namespace {
@@ -226,6 +230,103 @@ __global__ __launch_bounds__(256) void wave_augment_kernel(const float* __restri
   }
 }
 
+// ---- masked BCE.  One row by one wave, one pass: lane l takes columns l, l + 64, ... in order, then a fixed butterfly.
+// yy row = [labels (C) | mask (C)].  -> sum_c m_c bce(z_c, t_c) / C; dz / probs (if not NULL) are written on the way.
+__device__ double bce_row(const float* __restrict__ z, const float* __restrict__ yy, const int* __restrict__ perm,
+                          const float* __restrict__ lam, int B, int C, int binarize, int b, float* __restrict__ dz,
+                          float* __restrict__ probs, long long probs_stride) {
+  const int lane = threadIdx.x & 63;
+  int pb = -1;
+  double l = 1.0;
+  if (perm != nullptr) {
+    pb = perm[b];
+    l = (double)lam[b];
+    if (pb < 0 || pb >= B) pb = b, l = __builtin_nan("");   // (as ce_row: a bad permutation poisons its row, nothing outside yy is read)
+  }
+  const float* zr = z + (size_t)b * C;
+  const float* ya = yy + (size_t)b * 2 * C;
+  const float* yp = yy + (size_t)(pb < 0 ? b : pb) * 2 * C;
+  const double inv_bc = 1.0 / ((double)B * (double)C);
+  double acc = 0.0;
+  for (int c = lane; c < C; c += 64) {
+    const double v = (double)zr[c];
+    const double m = (double)ya[C + c];                     // the mask of row b only: the log-mel mix-up does not mix masks
+    double t = binarize ? (ya[c] > 0.5f ? 1.0 : 0.0) : (double)ya[c];
+    if (pb >= 0) t = l * t + (1.0 - l) * (binarize ? (yp[c] > 0.5f ? 1.0 : 0.0) : (double)yp[c]);
+    const double e = exp(-fabs(v));
+    const double sg = v >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);          // NaN logit: NaN
+    acc += m * ((v > 0.0 ? v : 0.0) - v * t + log1p(e));                   // 0 * NaN = NaN: a NaN logit shows under mask 0 too
+    if (dz != nullptr) dz[(size_t)b * C + c] = (float)(m * (sg - t) * inv_bc);
+    if (probs != nullptr) probs[(long long)b * probs_stride + c] = (float)sg;
+  }
+  return wave_sum_d(acc) / (double)C;
+}
+
+__global__ __launch_bounds__(256) void bce_rows_kernel(const float* __restrict__ z, const float* __restrict__ yy,
+                                                       const int* __restrict__ perm, const float* __restrict__ lam, int B, int C,
+                                                       int binarize, float* __restrict__ dz, float* __restrict__ row_loss,
+                                                       float* __restrict__ probs, long long probs_stride) {
+  const int b = blockIdx.x * kCeRowsPerBlock + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const double r = bce_row(z, yy, perm, lam, B, C, binarize, b, dz, probs, probs_stride);
+  if ((threadIdx.x & 63) == 0 && row_loss) row_loss[b] = (float)r;
+}
+
+// sums[0] += mean_b row_b in the fixed order of ce_sum_kernel (rows as fp32, thread t adds rows t, t + 256, ...); with
+// row_loss == NULL the rows are recomputed here so that the same values are added in the same order.
+__global__ __launch_bounds__(256) void bce_sum_kernel(const float* __restrict__ z, const float* __restrict__ yy,
+                                                      const int* __restrict__ perm, const float* __restrict__ lam, int B, int C,
+                                                      int binarize, const float* __restrict__ row_loss, float* __restrict__ sums) {
+  __shared__ float s_row[256];
+  __shared__ double s_red[4];
+  const int t = threadIdx.x, w = t >> 6;
+  double acc = 0.0;
+  for (int r0 = 0; r0 < B; r0 += 256) {
+    if (row_loss != nullptr) {
+      if (r0 + t < B) acc += (double)row_loss[r0 + t];
+    } else {
+      for (int r = w; r < 256 && r0 + r < B; r += 4) {
+        const double v = bce_row(z, yy, perm, lam, B, C, binarize, r0 + r, nullptr, nullptr, 0);
+        if ((t & 63) == 0) s_row[r] = (float)v;
+      }
+      __syncthreads();
+      if (r0 + t < B) acc += (double)s_row[t];
+      __syncthreads();
+    }
+  }
+  acc = wave_sum_d(acc);
+  if ((t & 63) == 0) s_red[w] = acc;
+  __syncthreads();
+  if (t == 0) sums[0] += (float)((((s_red[0] + s_red[1]) + s_red[2]) + s_red[3]) / (double)B);
+}
+
+// ---- OpenMIC wave-mix labels: block b writes yy row b (2C values) from bank_y rows idx[2b], idx[2b + 1].
+__global__ __launch_bounds__(64) void openmic_targets_kernel(const float* __restrict__ bank_y, long long n_bank, int C,
+                                                             const int* __restrict__ idx, const float* __restrict__ mix,
+                                                             float* __restrict__ yy) {
+  const int b = blockIdx.x;
+  const int i0 = idx[2 * b], i1 = idx[2 * b + 1];
+  const bool ok = i0 >= 0 && i0 < n_bank && i1 >= -1 && i1 < n_bank;   // (as wave_augment_kernel: never read outside bank_y)
+  const bool wm = ok && i1 >= 0;
+  const float* y1 = bank_y + (ok ? (long long)i0 * 2 * C : 0);
+  const float* y2 = bank_y + (wm ? (long long)i1 * 2 * C : 0);
+  const double l = wm ? (double)mix[b] : 1.0;
+  float* o = yy + (long long)b * 2 * C;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    if (!ok) {
+      o[c] = o[C + c] = __builtin_nanf("");
+    } else if (!wm) {
+      o[c] = y1[c];                                          // an unmixed row is a copy: its labels are not masked
+      o[C + c] = y1[C + c];
+    } else {
+      const double m1 = y1[C + c] > 0.5f ? 1.0 : 0.0, m2 = y2[C + c] > 0.5f ? 1.0 : 0.0;
+      // (both products are exact in fp64, so the sum is rounded once there and once to fp32, fused or not)
+      o[c] = (float)(l * ((double)y1[c] * m1) + (1.0 - l) * ((double)y2[c] * m2));
+      o[C + c] = (float)(m1 > m2 ? m1 : m2);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int eat_softmax_ce_fwd_bwd(const float* logits, const float* y, const int* perm, const float* lam, int B, int C,
@@ -260,4 +361,33 @@ extern "C" int eat_wave_augment(const float* bank, const double* bank_mean, cons
   hipLaunchKernelGGL(wave_augment_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, bank, bank_mean,
                      bank_cls, n_bank, L, C, idx, shift, amp, mix, out, y, vec);
   return eat::check_launch("eat_wave_augment");
+}
+
+extern "C" int eat_masked_bce_fwd_bwd(const float* logits, const float* yy, const int* perm, const float* lam, int B, int C,
+                                      int binarize, float* sums, float* dlogits, float* row_loss, float* probs,
+                                      long long probs_stride, eat_stream_t stream) {
+  eat::clear_stale_error();
+  if (B < 1 || C < 1 || 2LL * B * C > 0x7fffffffLL)
+    return eat::fail(EAT_EINVAL, "eat_masked_bce_fwd_bwd: bad shape (B = %d, C = %d)", B, C);
+  if ((perm == nullptr) != (lam == nullptr)) return eat::fail(EAT_EINVAL, "eat_masked_bce_fwd_bwd: perm and lam go together");
+  if (!logits || !yy) return eat::fail(EAT_EINVAL, "eat_masked_bce_fwd_bwd: logits and yy are required");
+  if (probs != nullptr && probs_stride < C)
+    return eat::fail(EAT_EINVAL, "eat_masked_bce_fwd_bwd: probs_stride = %lld < C = %d", probs_stride, C);
+  hipStream_t s = (hipStream_t)stream;
+  if (dlogits || row_loss || probs)
+    hipLaunchKernelGGL(bce_rows_kernel, dim3((unsigned)((B + kCeRowsPerBlock - 1) / kCeRowsPerBlock)), dim3(256), 0, s, logits,
+                       yy, perm, lam, B, C, binarize ? 1 : 0, dlogits, row_loss, probs, probs_stride);
+  if (sums)
+    hipLaunchKernelGGL(bce_sum_kernel, dim3(1), dim3(256), 0, s, logits, yy, perm, lam, B, C, binarize ? 1 : 0, row_loss, sums);
+  return eat::check_launch("eat_masked_bce_fwd_bwd");
+}
+
+extern "C" int eat_openmic_targets(const float* bank_y, long long n_bank, int C, const int* idx, const float* mix, float* yy,
+                                   int B, eat_stream_t stream) {
+  eat::clear_stale_error();
+  if (B < 1 || C < 1 || n_bank < 1 || 2LL * B * C > 0x7fffffffLL)
+    return eat::fail(EAT_EINVAL, "eat_openmic_targets: bad shape (B = %d, C = %d, n_bank = %lld)", B, C, n_bank);
+  if (!bank_y || !idx || !mix || !yy) return eat::fail(EAT_EINVAL, "eat_openmic_targets: a required pointer is NULL");
+  hipLaunchKernelGGL(openmic_targets_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, bank_y, n_bank, C, idx, mix, yy);
+  return eat::check_launch("eat_openmic_targets");
 }

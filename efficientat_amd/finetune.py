@@ -13,12 +13,17 @@ the mix-up lambda -> a `.cpu()` read of the loss (a device sync) -> backward -> 
 
 Host RNG order of a step: the augmentation draws (torch, numpy), the mel's (fmin, fmax) draw, then `mixup` (torch.randperm,
 numpy beta) - the reference's order within the main process, with the DataLoader's draws moved in front of the step.
+
+Multi-label fine-tuning with partially observed labels (ex_openmic.py:96-206) has the same shape: `MaskedBCETrainer` /
+`GraphedMaskedBCETrainer` build the batch with `eat_wave_augment` (waveforms) and `eat_openmic_targets` (label | mask rows,
+openmic.draw_augment's order), the loss is `eat_masked_bce_fwd_bwd`, and `evaluate_masked` takes the probabilities from the
+same kernel and the masked mAP / ROC from `metrics.ap_auc(..., sample_weight=mask)`.
 """
 import time
 
 import torch
 
-from . import ops
+from . import metrics, openmic, ops
 from .esc50 import draw_augment
 from .graphs import HostRing
 from .train_loop import FusedLoss, GraphedTrainer, Trainer
@@ -165,6 +170,144 @@ def evaluate_accuracy(model, mel, bank, bank_cls, batch_size, n_classes=None, ke
     out = {"accuracy": res[0], "val_loss": res[1], "n_clips": n, "eval_s": eval_s, "clips_per_s": n / max(eval_s, 1e-9)}
     if keep_outputs:
         out["logits"], out["targets"] = logits, targets
+    return out
+
+
+def masked_bce_loss(logits, yy, perm=None, lam=None, sums=None):
+    """mean_bc mask * BCE-with-logits(z, lam y + (1 - lam) y[perm]), y = labels > 0.5 (ex_openmic.py:102-121) as a device
+    scalar that supports .backward(); yy (B, 2C) = [labels | mask]; `sums` (1,) accumulates it across calls."""
+    if sums is None:
+        sums = torch.zeros(1, device=logits.device, dtype=torch.float64)
+    yy = yy.contiguous().float()
+    return FusedLoss.apply(logits, sums, 1, lambda z, step: ops.masked_bce_fwd_bwd(
+        z, yy, perm, lam, sums=step, row_loss=torch.empty(z.shape[0], device=z.device, dtype=torch.float32)))
+
+
+class MaskedBCETrainer(Trainer):
+    """step(batch) = one iteration of ex_openmic.py's training loop (:96-129) on the bank rows `batch` (host indices).
+
+    bank (N, L) fp32, bank_mean (N) fp64, bank_y (N, 2C) fp32 = [labels | mask]: the resident training split
+    (openmic.load_bank); the other arguments as `CETrainer`."""
+
+    STATS = ("train_loss",)
+
+    def __init__(self, model, mel, optimizer, bank, bank_mean, bank_y, mixup_alpha=0.3, gain_augment=12, roll=True,
+                 wavmix=True):
+        self.model, self.mel, self.opt = model, mel, optimizer
+        self.bank, self.bank_mean, self.bank_y = bank, bank_mean, bank_y.float().contiguous()
+        if (bank.dim() != 2 or bank_mean.numel() != bank.shape[0] or self.bank_y.dim() != 2
+                or self.bank_y.shape[0] != bank.shape[0] or self.bank_y.shape[1] % 2):
+            raise ValueError("MaskedBCETrainer: bank (N, L), bank_mean (N) and bank_y (N, 2C) do not match")
+        self.mixup_alpha = mixup_alpha
+        self.gain_augment, self.roll, self.wavmix = int(gain_augment), bool(roll), bool(wavmix)
+        dev = next(model.parameters()).device
+        self.sums = torch.zeros(1, device=dev, dtype=torch.float64)
+        self.steps = 0
+
+    def draw(self, batch):
+        idx, shift, amp, mix = openmic.draw_augment(batch, self.bank.shape[0], self.gain_augment, self.roll, self.wavmix)
+        ops.check_augment_draws(idx, shift, self.bank.shape[0], self.bank.shape[1])
+        return idx, shift, amp, mix
+
+    def loss_and_backward(self, batch):
+        """augment -> mel -> log-mel mix-up -> model -> masked BCE -> backward; leaves the gradients in `.grad`."""
+        dev = self.bank.device
+        idx, shift, amp, mix = (t.to(dev, non_blocking=True) for t in self.draw(batch))    # validated: uploaded once for both
+        x, _ = ops.wave_augment(self.bank, self.bank_mean, None, idx, shift, amp, mix, 0)
+        yy = ops.openmic_targets(self.bank_y, idx, mix)
+        spec = self.mel(x).unsqueeze(1)                                       # _mel_forward, ex_openmic.py:152-157
+        spec, perm, lam = self._mixup(spec)                                   # host draws, reference order
+        y_hat, _ = self.model(spec)
+        loss = masked_bce_loss(y_hat, yy, perm, lam, self.sums)
+        loss.backward()
+        return loss.detach()
+
+
+class GraphedMaskedBCETrainer(GraphedTrainer, MaskedBCETrainer):
+    """`MaskedBCETrainer` with the whole iteration captured once and replayed, on `GraphedCETrainer`'s static-buffer scheme
+    (the same rings for idx / shift / amp / mix, perm / lam and the mel basis); `self.y` holds the (B, 2C) label | mask rows
+    that `eat_openmic_targets` writes inside the graph.  Everything said there about the optimizer, SpecAugment masks, DyMN
+    and partial batches holds here."""
+
+    def __init__(self, model, mel, optimizer, bank, bank_mean, bank_y, batch_size, mixup_alpha=0.3, gain_augment=12,
+                 roll=True, wavmix=True, warmup=2):
+        MaskedBCETrainer.__init__(self, model, mel, optimizer, bank, bank_mean, bank_y, mixup_alpha, gain_augment, roll, wavmix)
+        dev, B = bank.device, int(batch_size)
+        first = torch.full((2 * B,), -1, device=dev, dtype=torch.int32)
+        first[0::2] = 0                                                       # (bank row 0, no wave-mix: the warm-up batch)
+        self._idx = HostRing(first)
+        self._shift = HostRing(torch.zeros(2 * B, device=dev, dtype=torch.int32))
+        self._amp = HostRing(torch.ones(2 * B, device=dev))
+        self._mix = HostRing(torch.ones(B, device=dev))
+        self._setup_graph(B, bank.shape[1], self.bank_y.shape[1], warmup)     # (y is as wide as a packed row: 2C)
+
+    def _front(self, fmask=(0, 0), tmask=(0, 0)):
+        ops.wave_augment(self.bank, self.bank_mean, None, self._idx.dev, self._shift.dev, self._amp.dev, self._mix.dev, 0,
+                         out=self.wave)
+        ops.openmic_targets(self.bank_y, self._idx.dev, self._mix.dev, out=self.y)
+        super()._front(fmask, tmask)
+
+    def _graph_loss(self, y_hat, perm, lam):
+        return masked_bce_loss(y_hat, self.y, perm, lam, self.sums)
+
+    def _fits(self, batch):
+        return len(batch) == self.B
+
+    def _stage(self, batch):
+        idx, shift, amp, mix = self.draw(batch)          # host draws, reference order: augmentation, then the mel's, mix-up
+        self._idx.put(idx)
+        self._shift.put(shift)
+        self._amp.put(amp)
+        self._mix.put(mix)
+
+
+def evaluate_masked(model, mel, bank, bank_y, batch_size, keep_outputs=False):
+    """The reference's `_test` (ex_openmic.py:160-206) on a resident split -> {"mAP", "ROC", "val_loss", "n_clips", "eval_s",
+    "clips_per_s"} (+ "probs" (N, C) and "targets" (N, 2C) = [labels > 0.5 | mask] device tensors with keep_outputs=True).
+
+    val_loss: the MEAN OF THE PER-BATCH MEAN masked losses at `batch_size` (the reference's `losses.mean()`; the last batch
+    may be short).  `eat_masked_bce_fwd_bwd` writes sigmoid(logits) of every batch into its rows of one (N, C) matrix; mAP /
+    ROC are the plain means over the classes of `metrics.ap_auc(probs, labels > 0.5, sample_weight=mask)`, so a class
+    without weighted positives and negatives makes ROC NaN, and input sklearn refuses with a ValueError (a non-finite
+    probability, a mask entry other than 0 / 1) makes both NaN - the reference's `except ValueError`.  The host waits once, at
+    the end (the metrics' status word, then the three results).  Mode restore and forked RNG as `evaluate_accuracy`."""
+    n = bank.shape[0]
+    if n == 0:
+        raise ValueError("evaluate_masked: the split is empty")
+    dev = bank.device
+    yy = bank_y.to(device=dev, dtype=torch.float32).contiguous()
+    C = yy.shape[1] // 2
+    n_batches = (n + batch_size - 1) // batch_size
+    was_training = (model.training, mel.training)
+    model.eval()
+    mel.eval()
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    try:
+        with torch.random.fork_rng(devices=[]), torch.no_grad():
+            probs = torch.empty((n, C), device=dev, dtype=torch.float32)
+            bsum = torch.zeros(n_batches, device=dev, dtype=torch.float32)
+            for k in range(n_batches):
+                s, e = k * batch_size, min(n, (k + 1) * batch_size)
+                y_hat, _ = model(mel(bank[s:e]).unsqueeze(1))                 # _mel_forward + model (ex_openmic.py:177-179)
+                y_hat = y_hat.reshape(e - s, -1).float().contiguous()
+                ops.masked_bce_fwd_bwd(y_hat, yy[s:e], sums=bsum[k:k + 1], grad=False, probs=probs[s:e])
+            labels, mask = (yy[:, :C] > 0.5).float(), yy[:, C:]
+            nan = torch.full((), float("nan"), device=dev, dtype=torch.float64)
+            try:
+                ap, auc = metrics.ap_auc(probs, labels, sample_weight=mask)
+                m_ap, m_auc = ap.mean(), auc.mean()
+            except ValueError:
+                m_ap = m_auc = nan
+            res = torch.stack([m_ap, m_auc, bsum.double().mean()]).cpu().tolist()
+    finally:
+        model.train(was_training[0])
+        mel.train(was_training[1])
+    eval_s = time.perf_counter() - t0
+    out = {"mAP": res[0], "ROC": res[1], "val_loss": res[2], "n_clips": n, "eval_s": eval_s,
+           "clips_per_s": n / max(eval_s, 1e-9)}
+    if keep_outputs:
+        out["probs"], out["targets"] = probs, torch.cat([labels, mask], 1)
     return out
 
 

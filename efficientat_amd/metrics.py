@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from .ops import _stream
 
-_BAD_SCORE, _BAD_TARGET = 1, 2
+_BAD_SCORE, _BAD_TARGET, _BAD_WEIGHT = 1, 2, 4
 
 
 def _as_matrix(t, name):
@@ -27,15 +27,25 @@ def _as_matrix(t, name):
     return t
 
 
-def ap_auc(scores, targets):
+def ap_auc(scores, targets, sample_weight=None):
     """scores (N, C) or (N,) fp32 / bf16 / fp16, targets of the same shape (0 / 1) -> (ap, auc): float64 device tensors of
-    shape (C,).  One launch sequence and one read of the status word (a host sync)."""
+    shape (C,).  One launch sequence and one read of the status word (a host sync).  sample_weight: a 0 / 1 matrix of the same
+    shape (ex_openmic.py:194-204, sklearn's `sample_weight`): an item of weight 0 is left out of its column, and the
+    degenerate rules apply to what is left (no weighted item at all: AP 0.0, AUC NaN)."""
     s = _as_matrix(scores, "scores")
     y = _as_matrix(targets, "targets")
     if s.shape != y.shape:
         raise ValueError(f"scores {tuple(s.shape)} and targets {tuple(y.shape)} differ in shape")
     if s.device != y.device:
         raise ValueError(f"scores on {s.device}, targets on {y.device}")
+    w = None
+    if sample_weight is not None:
+        w = _as_matrix(sample_weight, "sample_weight")
+        if w.shape != s.shape:
+            raise ValueError(f"scores {tuple(s.shape)} and sample_weight {tuple(w.shape)} differ in shape")
+        if w.device != s.device:
+            raise ValueError(f"scores on {s.device}, sample_weight on {w.device}")
+        w = w.to(torch.float32).contiguous()
     if s.dtype not in (torch.float32, torch.bfloat16):
         s = s.float()                                   # fp16 (and anything else) is widened to fp32
     s = s.contiguous()
@@ -51,13 +61,18 @@ def ap_auc(scores, targets):
         auc = torch.empty(C, dtype=torch.float64, device=s.device)
         n_pos = torch.empty(C, dtype=torch.int32, device=s.device)
         status = torch.empty(1, dtype=torch.int32, device=s.device)
-        _lib.call("eat_rank_metrics", s.data_ptr(), int(s.dtype == torch.bfloat16), y.data_ptr(), N, C, ws.data_ptr(),
-                  ap.data_ptr(), auc.data_ptr(), n_pos.data_ptr(), status.data_ptr(), _stream())
+        out = (N, C, ws.data_ptr(), ap.data_ptr(), auc.data_ptr(), n_pos.data_ptr(), status.data_ptr(), _stream())
+        if w is None:
+            _lib.call("eat_rank_metrics", s.data_ptr(), int(s.dtype == torch.bfloat16), y.data_ptr(), *out)
+        else:
+            _lib.call("eat_rank_metrics_masked", s.data_ptr(), int(s.dtype == torch.bfloat16), y.data_ptr(), w.data_ptr(), *out)
         st = int(status.item())
     if st & _BAD_SCORE:
         raise ValueError("scores contain NaN or infinity")
     if st & _BAD_TARGET:
         raise ValueError("targets must be exactly 0 or 1")
+    if st & _BAD_WEIGHT:
+        raise ValueError("sample_weight must be exactly 0 or 1")
     return ap, auc
 
 
@@ -69,11 +84,11 @@ def _reduce(v, average):
     raise ValueError(f"average must be None or 'macro', got {average!r}")
 
 
-def average_precision(scores, targets, average=None):
+def average_precision(scores, targets, average=None, sample_weight=None):
     """Per-class AP (average=None) or its plain mean ("macro"): sklearn's average_precision_score."""
-    return _reduce(ap_auc(scores, targets)[0], average)
+    return _reduce(ap_auc(scores, targets, sample_weight)[0], average)
 
 
-def roc_auc(scores, targets, average=None):
+def roc_auc(scores, targets, average=None, sample_weight=None):
     """Per-class ROC AUC (average=None) or its plain mean ("macro"): sklearn's roc_auc_score."""
-    return _reduce(ap_auc(scores, targets)[1], average)
+    return _reduce(ap_auc(scores, targets, sample_weight)[1], average)

@@ -1730,7 +1730,8 @@ def check_augment_draws(idx, shift, n_bank, L):
 def wave_augment(bank, bank_mean, bank_cls, idx, shift, amp, mix, n_classes, out=None, y=None):
     """Gain + roll + wave-mix of a batch gathered from the resident bank (include/eat_hip.h: eat_wave_augment) -> (out (B, L),
     y (B, n_classes)).  idx / shift (2B) int32, amp (2B) / mix (B) fp32: CPU tensors are validated here and uploaded; device
-    tensors (the static buffers of a captured step) must have been validated before they were staged."""
+    tensors (the static buffers of a captured step) must have been validated before they were staged.  bank_cls = None:
+    the waveforms only, -> (out, None) (the labels of a multi-label bank come from `openmic_targets`)."""
     n_bank, L = bank.shape
     B = torch.as_tensor(mix).numel()
     dev = bank.device
@@ -1742,11 +1743,65 @@ def wave_augment(bank, bank_mean, bank_cls, idx, shift, amp, mix, n_classes, out
         raise _lib.EatHipError("wave_augment: bank_mean must be a float64 GPU tensor of one value per bank row")
     if out is None:
         out = torch.empty((B, L), device=dev, dtype=torch.float32)
-    if y is None:
+    if bank_cls is None:
+        if y is not None:
+            raise _lib.EatHipError("wave_augment: y needs bank_cls")
+        n_classes = 0
+    elif y is None:
         y = torch.empty((B, n_classes), device=dev, dtype=torch.float32)
-    if out.numel() != B * L or y.numel() != B * n_classes or amp.numel() != 2 * B:
+    if out.numel() != B * L or (y is not None and y.numel() != B * n_classes) or amp.numel() != 2 * B:
         raise _lib.EatHipError("wave_augment: out / y / amp do not match the batch")
     _lib.call("eat_wave_augment", _dev(bank, "bank"), bank_mean.data_ptr(), _dev_int32(bank_cls, "bank_cls", n_bank), n_bank, L,
               n_classes, _dev_int32(idx, "idx", 2 * B), _dev_int32(shift, "shift", 2 * B), _dev(amp, "amp"), _dev(mix, "mix"),
-              _dev(out, "out"), _dev(y, "y"), B, _stream())
+              _dev(out, "out"), _opt(y, "y"), B, _stream())
     return out, y
+
+
+# ------------------------------------------------------------------ OpenMIC fine-tuning (ex_openmic.py:96-206)
+def masked_bce_fwd_bwd(logits, yy, perm=None, lam=None, sums=None, grad=True, row_loss=None, probs=None, binarize=True):
+    """Masked BCE-with-logits of (B, C) logits against packed rows yy (B, 2C) = [labels | mask], the mix-up of the (binarized)
+    labels folded in (include/eat_hip.h: eat_masked_bce_fwd_bwd).  -> dlogits (B, C) (None with grad=False); `sums` (>= 1 fp32)
+    += the batch mean; `row_loss` (B) fp32 is filled when given; `probs` (B, C) fp32 receives sigmoid(logits) - it may be a
+    row slice of a wider matrix (unit column stride)."""
+    if logits.dim() != 2:
+        raise _lib.EatHipError(f"masked_bce_fwd_bwd: logits must be (B, C), got {tuple(logits.shape)}")
+    B, C = logits.shape
+    if tuple(yy.shape) != (B, 2 * C):
+        raise _lib.EatHipError(f"masked_bce_fwd_bwd: yy {tuple(yy.shape)} does not match the logits: expected {(B, 2 * C)}")
+    if (perm is None) != (lam is None):
+        raise _lib.EatHipError("masked_bce_fwd_bwd: perm and lam go together")
+    if lam is not None and lam.numel() != B:
+        raise _lib.EatHipError("masked_bce_fwd_bwd: lam must hold B values")
+    if row_loss is not None and row_loss.numel() != B:
+        raise _lib.EatHipError("masked_bce_fwd_bwd: row_loss must hold B values")
+    if sums is not None and (sums.dtype != torch.float32 or sums.numel() < 1):
+        raise _lib.EatHipError("masked_bce_fwd_bwd: sums must be a float32 tensor")
+    stride = 0
+    if probs is not None:
+        if (not probs.is_cuda or probs.dtype != torch.float32 or tuple(probs.shape) != (B, C) or probs.stride(1) != 1
+                or (B > 1 and probs.stride(0) < C)):
+            raise _lib.EatHipError(f"masked_bce_fwd_bwd: probs must be a float32 GPU view of shape {(B, C)} with unit column "
+                                   f"stride (got {probs.dtype}, {tuple(probs.shape)}, strides {probs.stride()})")
+        stride = probs.stride(0) if B > 1 else C
+    dlogits = torch.empty_like(logits) if grad else None
+    _lib.call("eat_masked_bce_fwd_bwd", _dev(logits, "logits"), _dev(yy, "yy"), _dev_int32(perm, "perm", B), _opt(lam, "lam"),
+              B, C, int(bool(binarize)), _opt(sums, "sums"), _opt(dlogits, "dlogits"), _opt(row_loss, "row_loss"),
+              None if probs is None else probs.data_ptr(), stride, _stream())
+    return dlogits
+
+
+def openmic_targets(bank_y, idx, mix, out=None):
+    """Label rows (B, 2C) of a wave-mixed batch from the resident labels bank_y (N, 2C) (include/eat_hip.h:
+    eat_openmic_targets).  idx (2B) int32 / mix (B) fp32: the DEVICE tables handed to `wave_augment`, validated
+    (`check_augment_draws`) before they were uploaded."""
+    n_bank, W = bank_y.shape
+    B = mix.numel()
+    if W % 2 or W == 0:
+        raise _lib.EatHipError(f"openmic_targets: bank_y must be (N, 2C), got {tuple(bank_y.shape)}")
+    if out is None:
+        out = torch.empty((B, W), device=bank_y.device, dtype=torch.float32)
+    if out.numel() != B * W:
+        raise _lib.EatHipError("openmic_targets: out does not match the batch")
+    _lib.call("eat_openmic_targets", _dev(bank_y, "bank_y"), n_bank, W // 2, _dev_int32(idx, "idx", 2 * B), _dev(mix, "mix"),
+              _dev(out, "out"), B, _stream())
+    return out

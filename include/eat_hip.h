@@ -874,6 +874,13 @@ int eat_pw_conv_dyn_wgrad_b16(const void* dz, int dz_b16, const void* x, int x_b
 long long eat_rank_metrics_ws_bytes(int N, int C);
 int eat_rank_metrics(const void* scores, int scores_b16, const float* targets, int N, int C, void* ws, double* ap,
                      double* auc, int* n_pos, int* status, eat_stream_t stream);
+/* The same with sklearn's sample_weight restricted to 0 / 1 (ex_openmic.py:194-204: the "label was annotated" mask):
+ * weights (N, C) fp32; an item of weight 0 is left out of its column.  count and TP become sums of weights, n_pos counts
+ * weighted positives, and the degenerate rules apply to the weighted items: no weighted positives: AP 0.0; only positives:
+ * AP 1.0; one class only, or no weighted item at all: AUC NaN.  Scores and targets of weight-0 items are still validated.
+ * status bit 4: a weight is neither 0 nor 1.  All-ones weights give eat_rank_metrics' results bit for bit.  Same workspace. */
+int eat_rank_metrics_masked(const void* scores, int scores_b16, const float* targets, const float* weights, int N, int C,
+                            void* ws, double* ap, double* auc, int* n_pos, int* status, eat_stream_t stream);
 
 /* ---- single-label fine-tuning: ex_esc50.py:95-178 ---------------------------------------------------------------------
  * Soft-target softmax cross-entropy with the mix-up of the targets folded in (F.cross_entropy with probability targets,
@@ -908,6 +915,34 @@ int eat_softmax_ce_fwd_bwd(const float* logits, const float* y, const int* perm,
 int eat_wave_augment(const float* bank, const double* bank_mean, const int* bank_cls, long long n_bank, int L, int C,
                      const int* idx, const int* shift, const float* amp, const float* mix, float* out, float* y, int B,
                      eat_stream_t stream);
+
+/* ---- multi-label fine-tuning with partially observed labels: ex_openmic.py:96-206 -------------------------------------
+ * Masked BCE-with-logits (ex_openmic.py:102-121), its gradient and the evaluation's probabilities (:160-187) in one pass
+ * over the (B, C) logits.  yy (B, 2C) packs a row as the dataset returns it: labels [0, C), then the mask [C, 2C).
+ *   y_bc  = yy[b, c], or (yy[b, c] > 0.5 ? 1 : 0) with binarize != 0 (the reference binarizes; soft labels: binarize = 0)
+ *   m_bc  = yy[b, C + c], a float multiplier, not thresholded, of row b only (the log-mel mix-up does not mix masks)
+ *   t_b   = lam[b] y_b + (1 - lam[b]) y_perm[b]         (perm / lam (B) int32 / fp32, both NULL: t_b = y_b)
+ *   l_bc  = m_bc [max(z, 0) - z t + log1p(exp(-|z|))]
+ *   sums (1)          += sum_bc l_bc / (B C), reduced in a fixed order (no atomics): repeated calls are bit-identical
+ *   dlogits (B, C)     = m_bc (sigmoid(z_bc) - t_bc) / (B C)
+ *   row_loss (B)       = sum_c l_bc / C
+ *   probs              = sigmoid(z_bc) at probs[b * probs_stride + c] (probs_stride >= C: a slice of a wider matrix)
+ * Any of sums / dlogits / row_loss / probs may be NULL.  Arithmetic in fp64.  A NaN logit makes its row's loss NaN even under
+ * mask 0 (0 * NaN, as torch); a perm entry outside [0, B) makes its row NaN and nothing outside yy is read.  Two launches at
+ * most, as eat_softmax_ce_fwd_bwd (pass row_loss on a hot path).  B >= 1, C >= 1, 2 B C < 2^31, perm and lam given together,
+ * else EAT_EINVAL. */
+int eat_masked_bce_fwd_bwd(const float* logits, const float* yy, const int* perm, const float* lam, int B, int C, int binarize,
+                           float* sums, float* dlogits, float* row_loss, float* probs, long long probs_stride,
+                           eat_stream_t stream);
+
+/* Label rows of a wave-mixed OpenMIC batch (MixupDataset.__getitem__, datasets/openmic.py:74-95) from the resident labels
+ * bank_y (n_bank, 2C) and the idx (2B) / mix (B) tables of eat_wave_augment, which produces the waveforms (y = NULL):
+ *   idx[2b+1] < 0:  yy[b] = bank_y[idx[2b]], copied unchanged (labels not multiplied by the mask)
+ *   else:           m_k = bank_y[idx_k, C:] > 0.5;  yy[b, :C] = l y_0[:C] m_0 + (1 - l) y_1[:C] m_1, l = mix[b] (evaluated in
+ *                   fp64, rounded to fp32);  yy[b, C:] = max(m_0, m_1)
+ * An idx outside the bank gives a NaN row and no read outside bank_y.  B, C, n_bank >= 1, 2 B C < 2^31, else EAT_EINVAL. */
+int eat_openmic_targets(const float* bank_y, long long n_bank, int C, const int* idx, const float* mix, float* yy, int B,
+                        eat_stream_t stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
