@@ -158,6 +158,9 @@ SIGNATURES = {
     "eat_masked_bce_fwd_bwd": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, ctypes.c_longlong, _P],
     "eat_openmic_targets": [_P, ctypes.c_longlong, _I, _P, _P, _P, _I, _P],
     "eat_rank_metrics_masked": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    # FSD50K fine-tuning (finetune.py): the batch gathered from a ragged clip bank
+    "eat_wave_augment_ragged": [_P, ctypes.c_longlong, _P, _P, _P, _P, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                                _I, _P],
 }
 
 RESTYPES = {"eat_rank_metrics_ws_bytes": ctypes.c_longlong}   # every other entry point returns int

@@ -18,12 +18,17 @@ Multi-label fine-tuning with partially observed labels (ex_openmic.py:96-206) ha
 `GraphedMaskedBCETrainer` build the batch with `eat_wave_augment` (waveforms) and `eat_openmic_targets` (label | mask rows,
 openmic.draw_augment's order), the loss is `eat_masked_bce_fwd_bwd`, and `evaluate_masked` takes the probabilities from the
 same kernel and the masked mAP / ROC from `metrics.ap_auc(..., sample_weight=mask)`.
+
+Multi-label fine-tuning on clips of any length (ex_fsd50k.py:89-178): `BCETrainer` / `GraphedBCETrainer` build the batch and
+its mixed soft labels from a ragged bank (fsd50k.load_bank) with `eat_wave_augment_ragged` (fsd50k.draw_augment's order: the
+crop of a long clip is redrawn on every fetch), the loss is `eat_masked_bce_fwd_bwd` with soft labels and a mask of ones, and
+`evaluate_multilabel` ranks the logits at a fixed length or at every clip's own.
 """
 import time
 
 import torch
 
-from . import metrics, openmic, ops
+from . import fsd50k, metrics, openmic, ops
 from .esc50 import draw_augment
 from .graphs import HostRing
 from .train_loop import FusedLoss, GraphedTrainer, Trainer
@@ -173,14 +178,16 @@ def evaluate_accuracy(model, mel, bank, bank_cls, batch_size, n_classes=None, ke
     return out
 
 
-def masked_bce_loss(logits, yy, perm=None, lam=None, sums=None):
+def masked_bce_loss(logits, yy, perm=None, lam=None, sums=None, binarize=True):
     """mean_bc mask * BCE-with-logits(z, lam y + (1 - lam) y[perm]), y = labels > 0.5 (ex_openmic.py:102-121) as a device
-    scalar that supports .backward(); yy (B, 2C) = [labels | mask]; `sums` (1,) accumulates it across calls."""
+    scalar that supports .backward(); yy (B, 2C) = [labels | mask]; `sums` (1,) accumulates it across calls.
+    binarize=False: y = the labels as they are (the soft labels of ex_fsd50k.py:102-115)."""
     if sums is None:
         sums = torch.zeros(1, device=logits.device, dtype=torch.float64)
     yy = yy.contiguous().float()
     return FusedLoss.apply(logits, sums, 1, lambda z, step: ops.masked_bce_fwd_bwd(
-        z, yy, perm, lam, sums=step, row_loss=torch.empty(z.shape[0], device=z.device, dtype=torch.float32)))
+        z, yy, perm, lam, sums=step, row_loss=torch.empty(z.shape[0], device=z.device, dtype=torch.float32),
+        binarize=binarize))
 
 
 class MaskedBCETrainer(Trainer):
@@ -308,6 +315,155 @@ def evaluate_masked(model, mel, bank, bank_y, batch_size, keep_outputs=False):
            "clips_per_s": n / max(eval_s, 1e-9)}
     if keep_outputs:
         out["probs"], out["targets"] = probs, torch.cat([labels, mask], 1)
+    return out
+
+
+class BCETrainer(Trainer):
+    """step(batch) = one iteration of ex_fsd50k.py's training loop (:96-123) on the bank clips `batch` (host indices).
+
+    bank: the resident training split, the dict of `fsd50k.load_bank` (ragged: waves, offsets, lengths, clip_sum, bank_y,
+    lengths_cpu); clip_samples: the length every clip is padded or cropped to (10 s); the other arguments as `CETrainer`."""
+
+    STATS = ("train_loss",)
+
+    def __init__(self, model, mel, optimizer, bank, clip_samples=320000, mixup_alpha=0.3, gain_augment=12, roll=True,
+                 wavmix=True):
+        self.model, self.mel, self.opt = model, mel, optimizer
+        self.bank, self.L = bank, int(clip_samples)
+        n = bank["lengths"].numel()
+        if (bank["waves"].dim() != 1 or bank["offsets"].numel() != n or bank["clip_sum"].numel() != n
+                or bank["bank_y"].dim() != 2 or bank["bank_y"].shape[0] != n or len(bank["lengths_cpu"]) != n or self.L < 1):
+            raise ValueError("BCETrainer: waves (S), offsets / lengths / clip_sum (N), bank_y (N, C) and lengths_cpu (N) do not match")
+        self.mixup_alpha = mixup_alpha
+        self.gain_augment, self.roll, self.wavmix = int(gain_augment), bool(roll), bool(wavmix)
+        dev = next(model.parameters()).device
+        self.sums = torch.zeros(1, device=dev, dtype=torch.float64)
+        self.steps = 0
+
+    def draw(self, batch):
+        idx, start, shift, amp, mix = fsd50k.draw_augment(batch, self.bank["lengths_cpu"], self.L, self.gain_augment, self.roll,
+                                                          self.wavmix)
+        ops.check_ragged_draws(idx, start, shift, self.bank["lengths_cpu"], self.L)
+        return idx, start, shift, amp, mix
+
+    def loss_and_backward(self, batch):
+        """crop / pad + augment + labels -> mel -> log-mel mix-up -> model -> BCE -> backward; leaves the gradients in `.grad`."""
+        x, yy = ops.wave_augment_ragged(self.bank, *self.draw(batch), self.L)
+        spec = self.mel(x).unsqueeze(1)                                       # _mel_forward, ex_fsd50k.py:145-150
+        spec, perm, lam = self._mixup(spec)                                   # host draws, reference order
+        y_hat, _ = self.model(spec)
+        loss = masked_bce_loss(y_hat, yy, perm, lam, self.sums, binarize=False)
+        loss.backward()
+        return loss.detach()
+
+
+class GraphedBCETrainer(GraphedTrainer, BCETrainer):
+    """`BCETrainer` with the whole iteration captured once and replayed, on `GraphedCETrainer`'s static-buffer scheme: rings
+    for idx / start / shift / amp / mix, perm / lam and the mel basis; `eat_wave_augment_ragged` runs inside the graph and
+    writes `self.wave` and the (B, 2C) label | ones rows `self.y`, with its window-mean workspace as one more static buffer.
+    Everything said there about the optimizer, SpecAugment masks, DyMN and partial batches holds here."""
+
+    def __init__(self, model, mel, optimizer, bank, batch_size, clip_samples=320000, mixup_alpha=0.3, gain_augment=12,
+                 roll=True, wavmix=True, warmup=2):
+        BCETrainer.__init__(self, model, mel, optimizer, bank, clip_samples, mixup_alpha, gain_augment, roll, wavmix)
+        dev, B = bank["waves"].device, int(batch_size)
+        first = torch.full((2 * B,), -1, device=dev, dtype=torch.int32)
+        first[0::2] = 0                                                       # (clip 0 from its start, no wave-mix: the warm-up batch)
+        self._idx = HostRing(first)
+        self._start = HostRing(torch.zeros(2 * B, device=dev, dtype=torch.int32))
+        self._shift = HostRing(torch.zeros(2 * B, device=dev, dtype=torch.int32))
+        self._amp = HostRing(torch.ones(2 * B, device=dev))
+        self._mix = HostRing(torch.ones(B, device=dev))
+        self._win_mean = torch.zeros(2 * B, device=dev, dtype=torch.float64)
+        self._setup_graph(B, self.L, 2 * bank["bank_y"].shape[1], warmup)     # (y is as wide as a packed row: 2C)
+
+    def _front(self, fmask=(0, 0), tmask=(0, 0)):
+        ops.wave_augment_ragged(self.bank, self._idx.dev, self._start.dev, self._shift.dev, self._amp.dev, self._mix.dev, self.L,
+                                out=self.wave, yy=self.y, win_mean=self._win_mean)
+        super()._front(fmask, tmask)
+
+    def _graph_loss(self, y_hat, perm, lam):
+        return masked_bce_loss(y_hat, self.y, perm, lam, self.sums, binarize=False)
+
+    def _fits(self, batch):
+        return len(batch) == self.B
+
+    def _stage(self, batch):
+        idx, start, shift, amp, mix = self.draw(batch)   # host draws, reference order: augmentation, then the mel's, mix-up
+        self._idx.put(idx)
+        self._start.put(start)
+        self._shift.put(shift)
+        self._amp.put(amp)
+        self._mix.put(mix)
+
+
+def evaluate_multilabel(model, mel, bank, batch_size, clip_samples=320000, variable_length=False, keep_outputs=False):
+    """The reference's `_test` (ex_fsd50k.py:153-178) on a resident ragged split -> {"mAP", "ROC", "val_loss", "n_clips",
+    "eval_s", "clips_per_s"} (+ "logits" (N, C) and "targets" (N, C) device tensors with keep_outputs=True).
+
+    Fixed length (the default): batches of `batch_size` clips padded or cropped to `clip_samples` by `eat_wave_augment_ragged`
+    (gain 1, no roll, no wave-mix).  The reference crops a long clip at random in evaluation too; those offsets are
+    `fsd50k.draw_eval_crops`, drawn first inside the forked RNG.  val_loss: the MEAN OF THE PER-BATCH MEAN losses (the
+    reference's `losses.mean()`; the last batch may be short).
+    variable_length (--variable_eval_length): every clip at its own length, one by one (the reference's batch size 1), as a
+    view of the flat buffer - nothing is copied; val_loss is then the mean over the clips.
+    mAP / ROC: the plain means over the classes of `metrics.ap_auc` on the LOGITS, as `_test` hands y_hat to sklearn (sigmoid
+    values would tie where fp32 saturates).  A class with one label value only makes ROC NaN where the reference's
+    roc_auc_score raises ValueError; non-finite logits make both NaN.  One host wait at the end.  Mode restore and forked RNG
+    as `evaluate_accuracy`."""
+    n = bank["lengths"].numel()
+    if n == 0:
+        raise ValueError("evaluate_multilabel: the split is empty")
+    dev = bank["waves"].device
+    L = int(clip_samples)
+    y = bank["bank_y"].to(device=dev, dtype=torch.float32).contiguous()
+    C = y.shape[1]
+    yy = torch.cat([y, torch.ones_like(y)], 1)                                # packed rows: a mask of ones
+    lengths, offsets = bank["lengths_cpu"].tolist(), bank["offsets"].cpu().tolist()
+    n_batches = n if variable_length else (n + batch_size - 1) // batch_size
+    was_training = (model.training, mel.training)
+    model.eval()
+    mel.eval()
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    try:
+        with torch.random.fork_rng(devices=[]), torch.no_grad():
+            logits = torch.empty((n, C), device=dev, dtype=torch.float32)
+            bsum = torch.zeros(n_batches, device=dev, dtype=torch.float32)
+            if variable_length:
+                for k in range(n):
+                    x = bank["waves"][offsets[k]:offsets[k] + lengths[k]].unsqueeze(0)
+                    y_hat, _ = model(mel(x).unsqueeze(1))                     # _mel_forward + model (ex_fsd50k.py:167-168)
+                    logits[k:k + 1].copy_(y_hat.reshape(1, -1).float())
+                    ops.masked_bce_fwd_bwd(logits[k:k + 1], yy[k:k + 1], sums=bsum[k:k + 1], grad=False, binarize=False)
+            else:
+                crops = fsd50k.draw_eval_crops(bank["lengths_cpu"], L)
+                for k in range(n_batches):
+                    s, e = k * batch_size, min(n, (k + 1) * batch_size)
+                    idx = torch.full((2 * (e - s),), -1, dtype=torch.int32)
+                    idx[0::2] = torch.arange(s, e, dtype=torch.int32)
+                    start = torch.zeros(2 * (e - s), dtype=torch.int32)
+                    start[0::2] = crops[s:e]
+                    x, _ = ops.wave_augment_ragged(bank, idx, start, torch.zeros_like(idx), torch.ones(2 * (e - s)),
+                                                   torch.ones(e - s), L, labels=False)
+                    y_hat, _ = model(mel(x).unsqueeze(1))
+                    logits[s:e].copy_(y_hat.reshape(e - s, -1).float())
+                    ops.masked_bce_fwd_bwd(logits[s:e], yy[s:e], sums=bsum[k:k + 1], grad=False, binarize=False)
+            nan = torch.full((), float("nan"), device=dev, dtype=torch.float64)
+            try:
+                ap, auc = metrics.ap_auc(logits, y)
+                m_ap, m_auc = ap.mean(), auc.mean()
+            except ValueError:
+                m_ap = m_auc = nan
+            res = torch.stack([m_ap, m_auc, bsum.double().mean()]).cpu().tolist()
+    finally:
+        model.train(was_training[0])
+        mel.train(was_training[1])
+    eval_s = time.perf_counter() - t0
+    out = {"mAP": res[0], "ROC": res[1], "val_loss": res[2], "n_clips": n, "eval_s": eval_s,
+           "clips_per_s": n / max(eval_s, 1e-9)}
+    if keep_outputs:
+        out["logits"], out["targets"] = logits, y
     return out
 
 

@@ -1805,3 +1805,68 @@ def openmic_targets(bank_y, idx, mix, out=None):
     _lib.call("eat_openmic_targets", _dev(bank_y, "bank_y"), n_bank, W // 2, _dev_int32(idx, "idx", 2 * B), _dev(mix, "mix"),
               _dev(out, "out"), B, _stream())
     return out
+
+
+# ------------------------------------------------------------------ FSD50K fine-tuning (ex_fsd50k.py:96-178)
+def check_ragged_draws(idx, start, shift, lengths_cpu, L):
+    """Host-side validation of the draw tables of `wave_augment_ragged` (CPU tensors of 2B values; lengths_cpu (N) the clip
+    lengths): primary rows in [0, N), partners in [-1, N), shifts in (-L, L); start == 0 for a clip that fits (length <= L),
+    0 <= start <= length - L for a longer one (the window is never padded: datasets/fsd50k.py:55-59)."""
+    idx, start, shift = torch.as_tensor(idx), torch.as_tensor(start), torch.as_tensor(shift)
+    lengths = torch.as_tensor(lengths_cpu).to(torch.int64)
+    n_bank = lengths.numel()
+    if idx.numel() % 2 or idx.numel() == 0 or idx.numel() != shift.numel() or idx.numel() != start.numel():
+        raise ValueError(f"wave_augment_ragged: idx / start / shift must hold 2B values each (got {idx.numel()}, "
+                         f"{start.numel()}, {shift.numel()})")
+    prim, part = idx[0::2], idx[1::2]
+    if bool(((prim < 0) | (prim >= n_bank)).any()) or bool(((part < -1) | (part >= n_bank)).any()):
+        raise ValueError(f"wave_augment_ragged: a bank index lies outside [0, {n_bank}) (partners may be -1)")
+    if bool((shift.abs() >= L).any()):
+        raise ValueError(f"wave_augment_ragged: a shift lies outside (-{L}, {L})")
+    used = idx >= 0
+    room = (lengths[idx[used].long()] - L).clamp(min=0)                       # 0 for a clip that fits
+    st = start[used].to(torch.int64)
+    if bool(((st < 0) | (st > room)).any()):
+        raise ValueError(f"wave_augment_ragged: a crop start lies outside [0, max(0, length - {L})]")
+
+
+def wave_augment_ragged(bank, idx, start, shift, amp, mix, L, out=None, yy=None, win_mean=None, labels=True):
+    """Crop / pad + gain + roll + wave-mix of a batch gathered from a ragged resident bank, and its mixed label rows
+    (include/eat_hip.h: eat_wave_augment_ragged) -> (out (B, L), yy (B, 2C) = [labels | ones]).  bank: the dict of
+    `fsd50k.load_bank` (waves, offsets, lengths, clip_sum, bank_y on the device, lengths_cpu).  idx / start / shift (2B)
+    int32, amp (2B) / mix (B) fp32: CPU tensors are validated here and uploaded; device tensors (the static buffers of a
+    captured step) must have been validated before they were staged.  win_mean (2B) fp64: the kernel's workspace, allocated
+    here unless given (a captured step passes a static one).  labels=False: the waveforms only, -> (out, None)."""
+    waves, offsets, lengths, clip_sum, bank_y = (bank[k] for k in ("waves", "offsets", "lengths", "clip_sum", "bank_y"))
+    n_bank, L = lengths.numel(), int(L)
+    B = torch.as_tensor(mix).numel()
+    dev = waves.device
+    if not idx.is_cuda:
+        check_ragged_draws(idx, start, shift, bank["lengths_cpu"], L)
+        idx, start, shift = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, start, shift))
+        amp, mix = (t.to(dev, torch.float32, non_blocking=True) for t in (amp, mix))
+    if waves.dim() != 1 or offsets.dtype != torch.int64 or not offsets.is_cuda or offsets.numel() != n_bank:
+        raise _lib.EatHipError("wave_augment_ragged: waves must be flat and offsets an int64 GPU tensor of one value per clip")
+    if clip_sum.dtype != torch.float64 or not clip_sum.is_cuda or clip_sum.numel() != n_bank:
+        raise _lib.EatHipError("wave_augment_ragged: clip_sum must be a float64 GPU tensor of one value per clip")
+    if bank_y.dim() != 2 or bank_y.shape[0] != n_bank:
+        raise _lib.EatHipError(f"wave_augment_ragged: bank_y must be (N, C) with N = {n_bank}, got {tuple(bank_y.shape)}")
+    C = bank_y.shape[1]
+    if out is None:
+        out = torch.empty((B, L), device=dev, dtype=torch.float32)
+    if not labels:
+        if yy is not None:
+            raise _lib.EatHipError("wave_augment_ragged: yy was given with labels=False")
+    elif yy is None:
+        yy = torch.empty((B, 2 * C), device=dev, dtype=torch.float32)
+    if win_mean is None:
+        win_mean = torch.empty(2 * B, device=dev, dtype=torch.float64)
+    if (out.numel() != B * L or (yy is not None and yy.numel() != 2 * B * C) or amp.numel() != 2 * B
+            or win_mean.dtype != torch.float64 or not win_mean.is_cuda or win_mean.numel() != 2 * B
+            or not win_mean.is_contiguous()):
+        raise _lib.EatHipError("wave_augment_ragged: out / yy / amp / win_mean do not match the batch")
+    _lib.call("eat_wave_augment_ragged", _dev(waves, "waves"), waves.numel(), offsets.data_ptr(),
+              _dev_int32(lengths, "lengths", n_bank), clip_sum.data_ptr(), _dev(bank_y, "bank_y"), n_bank, L, C,
+              _dev_int32(idx, "idx", 2 * B), _dev_int32(start, "start", 2 * B), _dev_int32(shift, "shift", 2 * B),
+              _dev(amp, "amp"), _dev(mix, "mix"), win_mean.data_ptr(), _dev(out, "out"), _opt(yy, "yy"), B, _stream())
+    return out, yy

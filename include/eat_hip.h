@@ -944,6 +944,40 @@ int eat_masked_bce_fwd_bwd(const float* logits, const float* yy, const int* perm
 int eat_openmic_targets(const float* bank_y, long long n_bank, int C, const int* idx, const float* mix, float* yy, int B,
                         eat_stream_t stream);
 
+/* ---- multi-label fine-tuning on clips of any length: ex_fsd50k.py:96-178 ----------------------------------------------
+ * Training batch of the FSD50K loop built on the device from a RAGGED resident clip bank (datasets/fsd50k.py: gain, pad or
+ * random crop, roll of datasets/helpers/audiodatasets.py, MixupDataset wave-mix and its mixed labels):
+ *   waves (n_samples) fp32 flat sample buffer; offsets (n_bank) int64 / lengths (n_bank) int32: clip i is
+ *   waves[offsets[i] : offsets[i] + lengths[i]] - clip starts need no alignment; clip_sum (n_bank) fp64 sum of all samples of
+ *   clip i; bank_y (n_bank, C) fp32 multi-hot labels.  Per sample b, slot 0 = the clip, slot 1 = its wave-mix partner, as in
+ *   eat_wave_augment: idx (2B) int32 bank rows, idx[2b+1] = -1 for no wave-mix; start (2B) int32 first sample of the slot's
+ *   window inside its clip; shift (2B) int32; amp (2B) fp32 linear gains; mix (B) fp32 wave-mix weights.
+ * Slot k with clip i, window length w = min(lengths[i] - start_k, L):
+ *   u_k[n] = amp_k waves[offsets[i] + start_k + n]  for n < w, and exactly 0 for w <= n < L   (gain BEFORE the padding)
+ *   r_k[n] = u_k[(n - shift_k) mod L]                (torch.roll: the padding rolls with the clip; any shift)
+ *   m_k    = amp_k / L * sum_{n < w} waves[offsets[i] + start_k + n]      (the mean of u_k, padding included)
+ *   out[b] = r_0                                                          without wave-mix (no mean is subtracted)
+ *   out[b] = l (r_0 - m_0) + (1 - l) (r_1 - m_1), l = mix[b]              with it
+ *   yy[b]  = [y_0 | 1] without wave-mix, [l y_0 + (1 - l) y_1 | 1] with it, y_k = bank_y[idx_k]: the sum is taken in fp64
+ *            and rounded once; the second half (the mask of eat_masked_bce_fwd_bwd's packed rows) is all ones.  yy (B, 2C)
+ *            may be NULL: no label row is written (C and bank_y are then unused).
+ * The reference's final `x - x.mean()` of a mixed clip removes a mean that is zero in real arithmetic (the two terms have
+ * mean zero each): omitted, as in eat_wave_augment.
+ * Two launches.  The first writes win_mean (2B) fp64, a caller-supplied workspace: m_k for both slots of every wave-mixed
+ * row, 0 for the slots of the other rows.  A slot whose window is its whole clip (start = 0, lengths <= L) takes the sum from
+ * clip_sum; any other window is summed in fp64 by one block in a fixed order, without atomics.  The second launch reads the
+ * workspace and writes out (and yy): repeated calls are bit-identical.  out rows are written with 16-byte stores from the
+ * first 16-byte boundary of each row on (scalar stores for the < 4 samples before it and behind the last whole group).
+ * Every index into waves is 64-bit (n_samples may pass 2^31).  The caller validates the tables on the host (0 <= idx_0 <
+ * n_bank, -1 <= idx_1 < n_bank, 0 <= start < lengths); the kernels check them again, and also 0 <= offsets[i], 1 <=
+ * lengths[i], offsets[i] + lengths[i] <= n_samples: a row with a slot that fails is written as NaN (out and yy) and nothing is
+ * read for it; no read goes past a clip's own end.  out must not alias waves.
+ * B, L, n_bank, n_samples >= 1, B <= 65535, (with yy) C >= 1 and 2 B C < 2^31, no required pointer NULL, else EAT_EINVAL. */
+int eat_wave_augment_ragged(const float* waves, long long n_samples, const long long* offsets, const int* lengths,
+                            const double* clip_sum, const float* bank_y, long long n_bank, int L, int C, const int* idx,
+                            const int* start, const int* shift, const float* amp, const float* mix, double* win_mean,
+                            float* out, float* yy, int B, eat_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
