@@ -161,6 +161,8 @@ SIGNATURES = {
     # FSD50K fine-tuning (finetune.py): the batch gathered from a ragged clip bank
     "eat_wave_augment_ragged": [_P, ctypes.c_longlong, _P, _P, _P, _P, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _I, _P],
+    # DCASE20 fine-tuning (finetune.py): frequency-wise MixStyle of the log-mel batch
+    "eat_freq_mixstyle": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
 }
 
 RESTYPES = {"eat_rank_metrics_ws_bytes": ctypes.c_longlong}   # every other entry point returns int

@@ -23,12 +23,18 @@ Multi-label fine-tuning on clips of any length (ex_fsd50k.py:89-178): `BCETraine
 its mixed soft labels from a ragged bank (fsd50k.load_bank) with `eat_wave_augment_ragged` (fsd50k.draw_augment's order: the
 crop of a long clip is redrawn on every fetch), the loss is `eat_masked_bce_fwd_bwd` with soft labels and a mask of ones, and
 `evaluate_multilabel` ranks the logits at a fixed length or at every clip's own.
+
+Acoustic scene classification (ex_dcase20.py:91-183): `SceneCETrainer` / `GraphedSceneCETrainer` are the single-label
+trainers with DCASE20's draw order (dcase20.draw_augment) and the reference's three-way branch on the log-mel: frequency-wise
+MixStyle (`eat_freq_mixstyle`, ops.freq_mixstyle) when --mixstyle_p > 0, else the mix-up, else nothing.  In the captured
+step the MixStyle coin of a step is a device flag, so applied and unapplied steps replay the same graph.
+`evaluate_accuracy(..., groups=)` adds the per-recording-device accuracy.
 """
 import time
 
 import torch
 
-from . import fsd50k, metrics, openmic, ops
+from . import dcase20, fsd50k, metrics, openmic, ops
 from .esc50 import draw_augment
 from .graphs import HostRing
 from .train_loop import FusedLoss, GraphedTrainer, Trainer
@@ -129,19 +135,109 @@ class GraphedCETrainer(GraphedTrainer, CETrainer):
         self._mix.put(mix)
 
 
-def evaluate_accuracy(model, mel, bank, bank_cls, batch_size, n_classes=None, keep_outputs=False):
+class SceneCETrainer(CETrainer):
+    """step(batch) = one iteration of ex_dcase20.py's training loop (:98-131) on the bank rows `batch` (host indices).
+
+    The arguments of `CETrainer` on a bank of dcase20.load_bank, plus mixstyle_p / mixstyle_alpha = --mixstyle_p /
+    --mixstyle_alpha.  The reference's branch (:104-120): with mixstyle_p > 0 the log-mel goes through frequency-wise MixStyle
+    and the loss is the plain soft-target cross-entropy - NO mix-up and none of its draws, also on a step whose coin says
+    "not applied" (`mixup_alpha` then reads 0 on the trainer); otherwise the mix-up when mixup_alpha is non-zero; otherwise
+    neither.  Host RNG order of a step: the augmentation draws in DCASE20's order (dcase20.draw_augment), the mel's draw,
+    then dcase20.draw_mixstyle or `mixup`."""
+
+    def __init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, n_classes=10, mixup_alpha=0.3, mixstyle_p=0.0,
+                 mixstyle_alpha=0.4, gain_augment=12, roll=True, wavmix=True):
+        self.mixstyle_p, self.mixstyle_alpha = float(mixstyle_p), float(mixstyle_alpha)
+        CETrainer.__init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, n_classes,
+                           0.0 if self.mixstyle_p > 0 else mixup_alpha, gain_augment, roll, wavmix)
+
+    def draw(self, batch):
+        idx, shift, amp, mix = dcase20.draw_augment(batch, self.bank.shape[0], self.gain_augment, self.roll, self.wavmix)
+        ops.check_augment_draws(idx, shift, self.bank.shape[0], self.bank.shape[1])
+        return idx, shift, amp, mix
+
+    def loss_and_backward(self, batch):
+        """augment -> mel -> MixStyle or mix-up -> model -> CE -> backward; leaves the gradients in `.grad`."""
+        draws = self.draw(batch)
+        x, y = ops.wave_augment(self.bank, self.bank_mean, self.bank_cls, *draws, self.n_classes)
+        spec = self.mel(x).unsqueeze(1)                                       # _mel_forward, ex_dcase20.py:151-156
+        perm = lam = None
+        if self.mixstyle_p > 0:
+            on, ms_perm, ms_lam = dcase20.draw_mixstyle(spec.shape[0], self.mixstyle_p, self.mixstyle_alpha)
+            if on:
+                spec = ops.freq_mixstyle(spec, ms_perm, ms_lam)
+        else:
+            spec, perm, lam = self._mixup(spec)                               # host draws, reference order
+        y_hat, _ = self.model(spec)
+        loss = ce_loss(y_hat, y, perm, lam, self.sums)
+        loss.backward()
+        return loss.detach()
+
+
+class GraphedSceneCETrainer(GraphedCETrainer, SceneCETrainer):
+    """`SceneCETrainer` as `GraphedCETrainer`'s captured step.  With mixstyle_p > 0 MixStyle runs inside the graph on static
+    buffers of its own: rings for perm (B) int32 and lam (B), a one-element int32 ring for the step's coin (`apply`: read by the
+    kernel, 0 = the spec passes through bit for bit), the (B, n_mels, 2) statistics workspace and the output spec.  Applied
+    and unapplied steps replay the same graph: nothing is captured again.  Everything said on `GraphedCETrainer` about the
+    optimizer, SpecAugment masks, DyMN `recapture()` and partial batches holds here."""
+
+    def __init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, batch_size, n_classes=10, mixup_alpha=0.3,
+                 mixstyle_p=0.0, mixstyle_alpha=0.4, gain_augment=12, roll=True, wavmix=True, warmup=2):
+        self.mixstyle_p, self.mixstyle_alpha = float(mixstyle_p), float(mixstyle_alpha)
+        if self.mixstyle_p > 0:
+            dev, B = bank.device, int(batch_size)
+            self._ms_perm = HostRing(torch.arange(B, device=dev, dtype=torch.int32))
+            self._ms_lam = HostRing(torch.ones(B, device=dev))
+            self._ms_apply = HostRing(torch.ones(1, device=dev, dtype=torch.int32))    # (the warm-up batch: applied)
+            self._ms_stats = torch.zeros((B, mel.n_mels, 2), device=dev)
+            self._ms_out = None                                               # (shaped like the spec: made by the first issue)
+        GraphedCETrainer.__init__(self, model, mel, optimizer, bank, bank_mean, bank_cls, batch_size, n_classes,
+                                  0.0 if self.mixstyle_p > 0 else mixup_alpha, gain_augment, roll, wavmix, warmup)
+
+    def _stage_mix(self):
+        if self.mixstyle_p <= 0:
+            return super()._stage_mix()
+        on, perm, lam = dcase20.draw_mixstyle(self.B, self.mixstyle_p, self.mixstyle_alpha)
+        self._ms_apply.put(torch.tensor([int(on)], dtype=torch.int32))
+        if on:
+            ops.check_mixstyle_perm(perm, self.B)                             # validated before it is staged
+            self._ms_perm.put(perm.to(torch.int32))
+            self._ms_lam.put(lam)
+
+    def _mix_spec(self, spec):
+        if self.mixstyle_p <= 0:
+            return super()._mix_spec(spec)
+        if self._ms_out is None:
+            self._ms_out = torch.empty_like(spec)
+        ops.freq_mixstyle(spec, self._ms_perm.dev, self._ms_lam.dev, apply=self._ms_apply.dev, out=self._ms_out,
+                          stats=self._ms_stats)
+        return self._ms_out, None, None
+
+
+def evaluate_accuracy(model, mel, bank, bank_cls, batch_size, n_classes=None, keep_outputs=False, groups=None):
     """The reference's `_test` (ex_esc50.py:154-178) on a resident split -> {"accuracy", "val_loss", "n_clips", "eval_s",
     "clips_per_s"} (+ "logits" / "targets" (N, C) device tensors with keep_outputs=True).
 
     accuracy: argmax(logits) == class over every clip; val_loss: the MEAN OF THE PER-BATCH MEAN cross-entropies at
     `batch_size` (the reference's `losses.mean()`; the last batch of a fold may be short, so this is not the clip mean).
     Both come from `eat_softmax_ce_fwd_bwd` (row argmax, per-batch sums); one host sync at the end.  Runs in eval mode under
-    no_grad inside a forked torch RNG (the mel draws its jitter even in eval); both modules get their previous mode back."""
+    no_grad inside a forked torch RNG (the mel draws its jitter even in eval); both modules get their previous mode back.
+    groups = (g, n_groups), g an (N) integer tensor with values in [0, n_groups) (e.g. DCASE20's recording device of every
+    clip): the result also holds "accuracy_by_group", a list of n_groups accuracies (NaN for a group without clips), counted
+    on the device and read in the same single host sync.  Nothing else changes."""
     n = bank.shape[0]
     if n == 0:
         raise ValueError("evaluate_accuracy: the split is empty")
     dev = bank.device
     cls = bank_cls.to(device=dev, dtype=torch.int64)
+    if groups is not None:
+        g, n_groups = groups
+        n_groups = int(n_groups)
+        if g.numel() != n or n_groups < 1 or g.is_floating_point():
+            raise ValueError(f"evaluate_accuracy: groups must be ({n} integers, a group count >= 1)")
+        if not g.is_cuda and bool(((g < 0) | (g >= n_groups)).any()):
+            raise ValueError(f"evaluate_accuracy: a group lies outside [0, {n_groups})")
+        g = g.reshape(-1).to(device=dev, dtype=torch.int64)
     n_batches = (n + batch_size - 1) // batch_size
     was_training = (model.training, mel.training)
     model.eval()
@@ -167,12 +263,20 @@ def evaluate_accuracy(model, mel, bank, bank_cls, batch_size, n_classes=None, ke
                         targets = torch.empty((n, y.shape[1]), device=dev)
                     logits[s:e].copy_(y_hat)
                     targets[s:e].copy_(y)
-            res = torch.stack([(amax.long() == cls).double().mean(), bsum.double().mean()]).cpu().tolist()
+            hit = (amax.long() == cls).double()
+            res = torch.stack([hit.mean(), bsum.double().mean()])
+            if groups is not None:                                            # (sums of 0 / 1 in fp64: exact in any order)
+                hits = torch.zeros(n_groups, device=dev, dtype=torch.float64).index_add_(0, g, hit)
+                count = torch.zeros(n_groups, device=dev, dtype=torch.float64).index_add_(0, g, torch.ones_like(hit))
+                res = torch.cat([res, hits / count])
+            res = res.cpu().tolist()
     finally:
         model.train(was_training[0])
         mel.train(was_training[1])
     eval_s = time.perf_counter() - t0
     out = {"accuracy": res[0], "val_loss": res[1], "n_clips": n, "eval_s": eval_s, "clips_per_s": n / max(eval_s, 1e-9)}
+    if groups is not None:
+        out["accuracy_by_group"] = res[2:]
     if keep_outputs:
         out["logits"], out["targets"] = logits, targets
     return out

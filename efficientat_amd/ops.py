@@ -1870,3 +1870,46 @@ def wave_augment_ragged(bank, idx, start, shift, amp, mix, L, out=None, yy=None,
               _dev_int32(idx, "idx", 2 * B), _dev_int32(start, "start", 2 * B), _dev_int32(shift, "shift", 2 * B),
               _dev(amp, "amp"), _dev(mix, "mix"), win_mean.data_ptr(), _dev(out, "out"), _opt(yy, "yy"), B, _stream())
     return out, yy
+
+
+# ------------------------------------------------------------------ DCASE20 fine-tuning (ex_dcase20.py:99-123)
+def check_mixstyle_perm(perm, B):
+    """Host-side validation of the permutation of `freq_mixstyle` (a CPU tensor): B values in [0, B)."""
+    perm = torch.as_tensor(perm)
+    if perm.numel() != B:
+        raise ValueError(f"freq_mixstyle: perm must hold B = {B} values (got {perm.numel()})")
+    if bool(((perm < 0) | (perm >= B)).any()):
+        raise ValueError(f"freq_mixstyle: a perm value lies outside [0, {B})")
+
+
+def freq_mixstyle(x, perm, lam, apply=None, out=None, stats=None, eps=1e-6):
+    """Frequency-wise MixStyle of a log-mel batch x (B, C, F, T) (include/eat_hip.h: eat_freq_mixstyle) -> out.  perm (B)
+    integer, lam (B) fp32 (any shape of B values): CPU tensors are validated here and uploaded; device tensors (the static
+    buffers of a captured step) must be int32 / fp32 and validated before they were staged.  apply: None, or a device int32
+    scalar read by the kernel (0: out = x bit for bit, stats untouched).  stats (B, F, 2) fp32: the kernel's workspace ({mu,
+    sig} per row), allocated here unless given."""
+    if x.dim() != 4:
+        raise _lib.EatHipError(f"freq_mixstyle: x must be (B, C, F, T), got {tuple(x.shape)}")
+    B, C, F, T = x.shape
+    dev = x.device
+    if not perm.is_cuda:
+        check_mixstyle_perm(perm, B)
+        perm = perm.reshape(-1).to(dev, torch.int32, non_blocking=True)
+    if lam.numel() != B:
+        raise _lib.EatHipError(f"freq_mixstyle: lam must hold B = {B} values (got {lam.numel()})")
+    if not lam.is_cuda:
+        lam = lam.to(dev, torch.float32, non_blocking=True)
+    lam = lam.reshape(-1)
+    if apply is not None and (not torch.is_tensor(apply) or apply.numel() != 1):
+        raise _lib.EatHipError("freq_mixstyle: apply must be None or a device int32 scalar")
+    if out is None:
+        out = torch.empty_like(x)
+    if stats is None:
+        stats = torch.empty((B, F, 2), device=dev, dtype=torch.float32)
+    if out.numel() != x.numel() or stats.numel() != 2 * B * F:
+        raise _lib.EatHipError("freq_mixstyle: out / stats do not match x")
+    if out.data_ptr() == x.data_ptr():
+        raise _lib.EatHipError("freq_mixstyle: out must not be x")
+    _lib.call("eat_freq_mixstyle", _dev(x, "x"), _dev_int32(perm, "perm", B), _dev(lam, "lam"), _dev_int32(apply, "apply", 1),
+              _dev(out, "out"), _dev(stats, "stats"), B, C, F, T, float(eps), _stream())
+    return out

@@ -167,15 +167,26 @@ class GraphedTrainer(Trainer):
     def _front(self, fmask=(0, 0), tmask=(0, 0)):
         self.mel.forward_static(self.wave, out=self.spec, fmask=fmask, tmask=tmask)
 
+    # How the step mixes the log-mel, as a pair a subclass overrides together: `_stage_mix` makes the host draws (after the
+    # mel's) and stages them, `_mix_spec` is the matching part of the captured sequence.  Here: the mix-up.
+    def _stage_mix(self):
+        if self._perm is not None:
+            rn, lm = mixup(self.B, self.mixup_alpha)
+            self._perm.put(rn.to(torch.int32))
+            self._lam.put(lm)
+
+    def _mix_spec(self, spec):
+        """-> (the spec the model sees, perm, lam as `_graph_loss` takes them)."""
+        if self._perm is None:
+            return spec, None, None
+        perm, lam = self._perm.dev, self._lam.dev
+        return ops.mixup_fwd(spec, perm, lam), perm, lam
+
     # the captured sequence (everything reads / writes static buffers)
     def _issue(self):
         if self.mel_in_graph:
             self._front()
-        spec = self.spec
-        perm = lam = None
-        if self._perm is not None:
-            perm, lam = self._perm.dev, self._lam.dev
-            spec = ops.mixup_fwd(spec, perm, lam)
+        spec, perm, lam = self._mix_spec(self.spec)
         y_hat, _ = self.model(spec)
         loss = self._graph_loss(y_hat, perm, lam)
         loss.backward()
@@ -197,10 +208,7 @@ class GraphedTrainer(Trainer):
         self.mel.stage_tables(fmin, fmax)
         if not self.mel_in_graph:
             self._front(fmask, tmask)
-        if self._perm is not None:
-            rn, lm = mixup(self.B, self.mixup_alpha)
-            self._perm.put(rn.to(torch.int32))
-            self._lam.put(lm)
+        self._stage_mix()
         replay_step(self)
         self.steps += 1
         return self.loss

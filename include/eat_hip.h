@@ -978,6 +978,26 @@ int eat_wave_augment_ragged(const float* waves, long long n_samples, const long 
                             const int* start, const int* shift, const float* amp, const float* mix, double* win_mean,
                             float* out, float* yy, int B, eat_stream_t stream);
 
+/* ---- acoustic scene fine-tuning: ex_dcase20.py:99-123 ------------------------------------------------------------------
+ * Frequency-wise MixStyle (helpers/utils.py `mixstyle`, ex_dcase20.py:104-107) of a log-mel batch x (B, C, F, T) fp32 into
+ * out (same shape, must not be x).  With n = C T, per row (b, f):
+ *   mu[b, f]  = mean of x[b, :, f, :]
+ *   sig[b, f] = sqrt(var + eps), var = the UNBIASED variance (divisor n - 1, torch.var), summed around mu in fp64
+ *   out[b, c, f, t] = (x - mu) / sig * (l sig + (1 - l) sig[p]) + (l mu + (1 - l) mu[p]),  l = lam[b], p = perm[b]
+ * perm (B) int32 with values in [0, B) - validated by the caller; a value outside poisons its sample with NaN and nothing
+ * outside the buffers is read - and lam (B) fp32.  stats (B, F, 2) fp32 is a caller-supplied workspace that receives
+ * {mu, sig} of every row.  No backward exists: x comes from the parameter-free mel and the reference detaches the statistics.
+ * apply: NULL, or a DEVICE int32 read by the kernels.  NULL or non-zero: as above.  Zero: out is a bit-exact copy of x and
+ * stats is not written - the reference's `np.random.rand() > p` outcome of a step, decided without a new capture.
+ * Two launches (row statistics: one wave per row, the row in registers when n <= 1024, re-read otherwise; then the apply,
+ * whose coefficients are combined in fp64 from the fp32 statistics, one fp64 multiply-add per element).  No atomics, fixed
+ * summation order: repeated calls are bit-identical.  Rows of out are written with 16-byte stores from the first 16-byte
+ * boundary of each row on (scalar stores before it and behind the last whole group): any T, any 4-byte aligned base.
+ * B, C, F, T >= 1, C T >= 2, B C F T < 2^31, x / perm / lam / out / stats not NULL, out != x, else EAT_EINVAL and nothing is
+ * launched. */
+int eat_freq_mixstyle(const float* x, const int* perm, const float* lam, const int* apply, float* out, float* stats, int B,
+                      int C, int F, int T, float eps, eat_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

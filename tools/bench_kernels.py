@@ -1,5 +1,5 @@
 """Per-kernel timings of the train step's candidates at B = 256 (GPU diagnostic, not product):
-   python tools/bench_kernels.py [stem] [dwbn]"""
+   python tools/bench_kernels.py [stem] [dwbn] [se] [wgrad] [mixstyle]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -96,3 +96,25 @@ if "wgrad" in what:
                 t = timeit(lambda: ops.pw_conv_wgrad(dz, x, x_scale=sc, tf=(a, b, ops.ACT_HSWISH)), n=20)
             mb = (Co + Ci) * S * B * 4 / 1e6
             print("wgrad_tf %4d x %4d @ %5d  %7.1f us  %6.0f MB alg  %5.2f TB/s" % (Co, Ci, S, t, mb, mb / t))
+if "mixstyle" in what:
+    # frequency-wise MixStyle of a DCASE20 batch (64 log-mels of 10 s) next to the torch-op restatement of the same maths
+    # (dropin/helpers/utils.py `mixstyle` past its draws); bytes: x read twice (statistics, apply) + out written once
+    Bm = 64
+    x = torch.randn(Bm, 1, 128, 1000, device=dev) * 2 - 4
+    perm, lam = torch.randperm(Bm, device=dev).to(torch.int32), torch.rand(Bm, device=dev)
+    out, stats = torch.empty_like(x), torch.empty(Bm, 128, 2, device=dev)
+    flag = torch.ones(1, device=dev, dtype=torch.int32)
+    permL, lmda = perm.long(), lam.reshape(Bm, 1, 1, 1)
+
+    def torch_ops():
+        mu = x.mean(dim=[1, 3], keepdim=True)
+        sig = (x.var(dim=[1, 3], keepdim=True) + 1e-6).sqrt()
+        return (x - mu) / sig * (sig * lmda + sig[permL] * (1 - lmda)) + (mu * lmda + mu[permL] * (1 - lmda))
+
+    t_k = timeit(lambda: ops.freq_mixstyle(x, perm, lam, apply=flag, out=out, stats=stats), n=50)
+    t_t = timeit(torch_ops, n=50)
+    flag.zero_()
+    t_c = timeit(lambda: ops.freq_mixstyle(x, perm, lam, apply=flag, out=out, stats=stats), n=50)
+    mb = 3 * x.numel() * 4 / 1e6
+    print("freq_mixstyle 64x1x128x1000: kernel %7.1f us (%5.2f TB/s of %.0f MB) | flag 0 (copy) %7.1f us | torch ops %7.1f us"
+          % (t_k, mb / t_k, mb, t_c, t_t))
