@@ -384,6 +384,9 @@ extern "C" int eat_dw_conv_dyn_act_fwd(const float* x, const float* w_bc, const 
 // ---- depthwise conv with dilation (models/mn/model.py:244-269 `dilated=True`: the last three blocks run their 5x5
 // depthwise conv with dilation 2 and stride 1; torch pads (k-1)/2*dilation).  Not a measured path (no released
 // checkpoint uses it): one thread per output element, taps and bias through the scalar cache, reads coalesced along T.
+// Unmeasured, but tested: tests/test_gpu_dilated_kernels.py holds this kernel and its two gradients against fp64 at pad >= F,
+// every k and dilation, stride 2, planes around one block and beyond the 32-block grid-stride pass, and B * C beyond one
+// launch.  The plane is blockIdx.y: callers pass at most 65535 planes per call (ops._plane_chunks splits the batch).
 namespace {
 __global__ __launch_bounds__(256) void dw_conv_dilated_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                               const float* __restrict__ bias, float* __restrict__ y,

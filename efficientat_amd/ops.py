@@ -112,13 +112,17 @@ def dw_conv(x, w, bias, k, stride, act, pool=None):
 
 
 def dw_conv_dilated(x, w, bias, k, stride, dilation, act, pool=None):
+    """Dilated depthwise conv + bias + activation (+ per-plane sums of the output added into `pool` (B, C)); the batch goes
+    through in ranges of <= 65535 planes (`_plane_chunks`: whole samples, so plane % C stays the channel)."""
     B, C, F, T = x.shape
-    pad = (k - 1) // 2 * dilation
-    Fo = (F + 2 * pad - dilation * (k - 1) - 1) // stride + 1
-    To = (T + 2 * pad - dilation * (k - 1) - 1) // stride + 1
+    Fo, To = dilated_out(F, T, k, stride, dilation)
     y = torch.empty((B, C, Fo, To), device=x.device, dtype=torch.float32)
-    _lib.call("eat_dw_conv_dilated_fwd", _dev(x, "x"), _dev(w, "w"), _dev(bias, "bias"), y.data_ptr(), _opt(pool, "pool"),
-              B, C, F, T, Fo, To, k, stride, dilation, act, _stream())
+    if w.numel() != C * k * k or bias.numel() < C or (pool is not None and pool.numel() != B * C):
+        raise _lib.EatHipError(f"dw_conv_dilated: w must hold {C} x {k * k} taps, bias {C} values, pool {B} x {C} sums")
+    xp, wp, bp, pp = _dev(x, "x"), _dev(w, "w"), _dev(bias, "bias"), _opt(pool, "pool")
+    for b0, b1 in _plane_chunks(B, C):
+        _lib.call("eat_dw_conv_dilated_fwd", xp + 4 * b0 * C * F * T, wp, bp, y.data_ptr() + 4 * b0 * C * Fo * To,
+                  None if pp is None else pp + 4 * b0 * C, b1 - b0, C, F, T, Fo, To, k, stride, dilation, act, _stream())
     return y
 
 
@@ -127,9 +131,17 @@ def dilated_out(F, T, k, stride, dilation):
     return (F + 2 * pad - dilation * (k - 1) - 1) // stride + 1, (T + 2 * pad - dilation * (k - 1) - 1) // stride + 1
 
 
+# Planes of one launch of the generic dilated kernels (their grids' y dimension).  65535 is the bound the project keeps for
+# that dimension everywhere; the HIP runtime on an MI355X was seen to take 67200 in one launch, so this is portability, not a
+# fault that was met.
+_GRID_Y = 65535
+
+
 def _plane_chunks(B, C):
     """Batch ranges whose (samples x channels) planes fit the y dimension of a launch grid (65535)."""
-    step = max(1, 65535 // C)
+    if not 1 <= C <= _GRID_Y:
+        raise _lib.EatHipError(f"dilated depthwise conv: {C} channels do not fit one launch (1..{_GRID_Y} planes per sample)")
+    step = _GRID_Y // C
     return [(i, min(B, i + step)) for i in range(0, B, step)]
 
 
@@ -140,8 +152,9 @@ def dw_conv_dyn_dilated(x, taps, k, stride, dilation):
     B, C, F, T = x.shape
     Fo, To = dilated_out(F, T, k, stride, dilation)
     y = torch.empty((B, C, Fo, To), device=x.device, dtype=torch.float32)
-    zb = zeros_vec.get(min(B, 65535 // C + 1) * C, x.device)
-    for b0, b1 in _plane_chunks(B, C):
+    chunks = _plane_chunks(B, C)
+    zb = zeros_vec.get(max(b1 - b0 for b0, b1 in chunks) * C, x.device)
+    for b0, b1 in chunks:
         n = (b1 - b0) * C
         _lib.call("eat_dw_conv_dilated_fwd", _dev(x, "x") + 4 * b0 * C * F * T, _dev(taps, "taps") + 4 * b0 * C * k * k,
                   zb.data_ptr(), y.data_ptr() + 4 * b0 * C * Fo * To, None, 1, n, F, T, Fo, To, k, stride, dilation, ACT_NONE,
@@ -184,16 +197,24 @@ def dyrelu_ca(z, a, b, act, coef, gate_f, gate_t):
 
 
 def dw_conv_dilated_dgrad(dz, w, x_shape, k, stride, dilation):
-    """Data gradient of the dilated depthwise conv (training of `dilated=True` networks; generic kernel)."""
+    """Data gradient of the dilated depthwise conv (training of `dilated=True` networks; generic kernel), in the same batch
+    ranges as the forward."""
     B, C, F, T = x_shape
+    Fo, To = dz.shape[2], dz.shape[3]
     dx = torch.empty((B, C, F, T), device=dz.device, dtype=torch.float32)
-    _lib.call("eat_dw_conv_dilated_dgrad", _dev(dz, "dz"), _dev(w, "w"), dx.data_ptr(), B, C, F, T, dz.shape[2], dz.shape[3],
-              k, stride, dilation, _stream())
+    if tuple(dz.shape[:2]) != (B, C) or w.numel() != C * k * k:
+        raise _lib.EatHipError(f"dw_conv_dilated_dgrad: dz must be ({B}, {C}, Fo, To) and w hold {C} x {k * k} taps")
+    gp, wp = _dev(dz, "dz"), _dev(w, "w")
+    for b0, b1 in _plane_chunks(B, C):
+        _lib.call("eat_dw_conv_dilated_dgrad", gp + 4 * b0 * C * Fo * To, wp, dx.data_ptr() + 4 * b0 * C * F * T, b1 - b0, C,
+                  F, T, Fo, To, k, stride, dilation, _stream())
     return dx
 
 
 def dw_conv_dilated_wgrad(dz, x, k, stride, dilation):
     B, C, F, T = x.shape
+    if C > _GRID_Y:   # one block per (tap, channel): the channels are the grid's y dimension
+        raise _lib.EatHipError(f"dw_conv_dilated_wgrad: {C} channels do not fit one launch (at most {_GRID_Y})")
     dw = torch.empty((C, k * k), device=dz.device, dtype=torch.float32)
     _lib.call("eat_dw_conv_dilated_wgrad", _dev(dz, "dz"), _dev(x, "x"), dw.data_ptr(), B, C, F, T, dz.shape[2], dz.shape[3],
               k, stride, dilation, _stream())

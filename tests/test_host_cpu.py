@@ -515,3 +515,25 @@ def test_draw_computes_the_frame_count_the_kernel_demands():
             assert 0 <= tmask[0] <= tmask[1] <= T, (cid, tmask)
         assert set(sizes) == {(mel.freqm, g["n_mels"]), (mel.timem, T)}, cid
         assert mel.eval().draw(L) == (g["fmin"], g["fmax"], (0, 0), (0, 0))
+
+
+@pytest.mark.parametrize("C", [1, 7, 960, 65535])
+@pytest.mark.parametrize("B", [1, 68, 69, 70, 300])
+def test_plane_chunks_partition_the_batch_within_one_launch(B, C):
+    """ops._plane_chunks: the batch ranges of the dilated depthwise launchers are disjoint, in order, cover [0, B) and hold at
+    most 65535 (sample, channel) planes each - the y dimension of one launch grid."""
+    from efficientat_amd import ops
+    chunks = ops._plane_chunks(B, C)
+    assert chunks[0][0] == 0 and chunks[-1][1] == B
+    for (a0, a1), (b0, _) in zip(chunks, chunks[1:]):
+        assert a1 == b0                                           # in order, no gap, no overlap
+    for b0, b1 in chunks:
+        assert b0 < b1 and (b1 - b0) * C <= 65535
+    assert len(chunks) == -(-B // (65535 // C))                   # and no more launches than that takes
+
+
+@pytest.mark.parametrize("C", [65536, 100000, 0])
+def test_plane_chunks_refuse_a_sample_wider_than_one_launch(C):
+    from efficientat_amd import ops
+    with pytest.raises(_lib.EatHipError, match="channels"):
+        ops._plane_chunks(4, C)
