@@ -199,9 +199,10 @@ int dispatch_dw(const float* x, const float* w, const float* bias, float* y, flo
     return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd: output %dx%d inconsistent with input %dx%d k=%d s=%d", Fo, To, F, T, k, stride);
   if (!dyn || (!dyn->coef && !dyn->gate_f)) {
     // register-resident kernels (dw_plane.hip: whole small planes, tiles of large ones); 1 = geometry not instantiated
-    const int rc = eat::dw_plane_try(x, w, bias, dyn ? dyn->res : nullptr, y, pool, B, C, F, T, Fo, To, k, stride, act,
-                                     dyn ? dyn->flip : 0, dyn ? dyn->per_plane_w : 0, dyn ? dyn->in_a : nullptr,
-                                     dyn ? dyn->in_b : nullptr, dyn ? dyn->in_act : 0, s, epi);
+    eat::DwFwdReq r{}; r.dim = {B, C, F, T, Fo, To, k, stride};
+    r.x = x; r.w = w; r.bias = bias; r.y = y; r.pool = pool; r.act = act; r.epi = epi; r.stream = s;
+    if (dyn) { r.res = dyn->res; r.flip = dyn->flip; r.per_plane_w = dyn->per_plane_w; r.tf = {dyn->in_a, dyn->in_b, dyn->in_act}; }
+    const int rc = eat::dw_plane_try(r);
     if (rc != 1) return rc;
   }
   if (epi) return 1;       // training epilogues exist in the register-resident kernels only: the caller falls back
@@ -244,60 +245,62 @@ extern "C" int eat_dw_conv_fwd_tf(const float* x, const float* in_a, const float
 
 // Train-mode depthwise conv (models/mn/block_types.py:150-162 under model.train()): y = conv(act_in(in_a x + in_b)) (in_a
 // NULL: plain x) with the per-wave partial sums of y for the BatchNorm that follows (layout [b][2][C][inner] floats;
-// *h_inner receives inner, which never exceeds inner_cap = eat_dw_partials_inner(...)).  Geometries without a
-// register-resident kernel run the row-ring kernel followed by a one-block-per-plane statistics pass (inner = 1).
-static int dw_conv_fwd_stats_impl(int per_plane_w, const float* x, const float* in_a, const float* in_b, int in_act, const float* w,
-                                     float* y, float* part, int inner_cap, int* h_inner, int B, int C, int F, int T,
-                                     int Fo, int To, int k, int stride, eat_stream_t stream) {
-  if ((in_a == nullptr) != (in_b == nullptr)) return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats: in_a and in_b come together");
-  if (in_act < 0 || in_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats: bad in_act %d", in_act);
+// *h_inner receives inner, which never exceeds inner_cap = eat_dw_partials_inner(...)).  One validation and launch for the
+// four entry points below; `who` is the entry point called, `store` the storage of x and y (act_io.h).
+//   fp32: geometries without a register-resident kernel run the row-ring kernel + a one-block-per-plane statistics pass (inner = 1);
+//   bf16 (the bf16-storage plan of BASELINE configs[2]; kDwB16XF32: x fp32 - a block without expand conv): register-resident
+//     kernels only (csrc/dw_plane.hip; eat_dw_conv_b16_ok tells whether a geometry is covered), sums of the ROUNDED outputs.
+static int dw_conv_fwd_stats_run(const char* who, eat::DwStore store, int per_plane_w, const void* x, const float* in_a,
+                                 const float* in_b, int in_act, const float* w, void* y, float* part, int inner_cap,
+                                 int* h_inner, int B, int C, int F, int T, int Fo, int To, int k, int stride,
+                                 eat_stream_t stream) {
+  eat::clear_stale_error();
+  if (!x || !w || !y) return eat::fail(EAT_EINVAL, "%s: missing operand", who);
+  if ((in_a == nullptr) != (in_b == nullptr)) return eat::fail(EAT_EINVAL, "%s: in_a and in_b come together", who);
+  if (in_act < 0 || in_act > 2) return eat::fail(EAT_EINVAL, "%s: bad in_act %d", who, in_act);
+  const int p = (k - 1) / 2;
+  if (stride < 1 || Fo != (F + 2 * p - k) / stride + 1 || To != (T + 2 * p - k) / stride + 1)
+    return eat::fail(EAT_EINVAL, "%s: output %dx%d inconsistent with input %dx%d k=%d s=%d", who, Fo, To, F, T, k, stride);
   if (!part || !h_inner || inner_cap < eat_dw_partials_inner(F, T, Fo, To, k, stride, 0))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats: partial buffer too small (inner_cap %d)", inner_cap);
-  const DwDyn dyn{nullptr, nullptr, nullptr, nullptr, 0, per_plane_w, in_a, in_b, in_act};
+    return eat::fail(EAT_EINVAL, "%s: partial buffer too small (inner_cap %d)", who, inner_cap);
+  hipStream_t s = (hipStream_t)stream;
   int inner = 1;
-  {
-    const eat::DwEpi epi{part, nullptr, nullptr, nullptr, 0, nullptr, &inner};
-    const int rc = dispatch_dw(x, w, nullptr, y, nullptr, B, C, F, T, Fo, To, k, stride, EAT_ACT_NONE, &dyn, (hipStream_t)stream, &epi);
-    if (rc != 1) { *h_inner = inner; return rc; }
+  const eat::DwEpi epi{part, nullptr, nullptr, nullptr, 0, nullptr, &inner};
+  if (store != eat::kDwF32) {
+    if ((F * T) % 2 != 0 || (Fo * To) % 2 != 0)
+      return eat::fail(EAT_EINVAL, "%s: planes must hold an even number of elements (%d, %d)", who, F * T, Fo * To);
+    eat::DwFwdReq r{}; r.dim = {B, C, F, T, Fo, To, k, stride};
+    r.x = x; r.w = w; r.y = y; r.act = EAT_ACT_NONE; r.per_plane_w = per_plane_w; r.tf = {in_a, in_b, in_act};
+    r.epi = &epi; r.store = store; r.stream = s;
+    const int rc = eat::dw_plane_try(r);
+    if (rc == 1)
+      return eat::fail(EAT_EINVAL, "%s: no register-resident kernel for F=%d T=%d k=%d stride=%d x_b16=%d", who, F, T, k, stride,
+                       store == eat::kDwB16);
+    *h_inner = inner;
+    return rc;
   }
-  const int rc = dispatch_dw(x, w, nullptr, y, nullptr, B, C, F, T, Fo, To, k, stride, EAT_ACT_NONE, &dyn, (hipStream_t)stream);
+  const float* xf = static_cast<const float*>(x); float* yf = static_cast<float*>(y);
+  const DwDyn dyn{nullptr, nullptr, nullptr, nullptr, 0, per_plane_w, in_a, in_b, in_act};
+  int rc = dispatch_dw(xf, w, nullptr, yf, nullptr, B, C, F, T, Fo, To, k, stride, EAT_ACT_NONE, &dyn, s, &epi);
+  if (rc != 1) { *h_inner = inner; return rc; }
+  rc = dispatch_dw(xf, w, nullptr, yf, nullptr, B, C, F, T, Fo, To, k, stride, EAT_ACT_NONE, &dyn, s);
   if (rc != 0) return rc;
   *h_inner = 1;
-  return eat::bn_stats_partial(y, B, C, Fo * To, part, (hipStream_t)stream);
+  return eat::bn_stats_partial(yf, B, C, Fo * To, part, s);
 }
 
 extern "C" int eat_dw_conv_fwd_stats(const float* x, const float* in_a, const float* in_b, int in_act, const float* w,
                                      float* y, float* part, int inner_cap, int* h_inner, int B, int C, int F, int T,
                                      int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  return dw_conv_fwd_stats_impl(0, x, in_a, in_b, in_act, w, y, part, inner_cap, h_inner, B, C, F, T, Fo, To, k, stride, stream);
+  return dw_conv_fwd_stats_run("eat_dw_conv_fwd_stats", eat::kDwF32, 0, x, in_a, in_b, in_act, w, y, part, inner_cap, h_inner,
+                               B, C, F, T, Fo, To, k, stride, stream);
 }
 
-// The same over bf16-stored x and y (act_io.h; the bf16-storage plan of BASELINE configs[2]: the expand conv's output z_e in,
-// the depthwise output z_d out, both 16-bit in HBM - x_b16 = 0: x is fp32, the first block's depthwise conv reads the stem
-// output; taps, transform coefficients and statistics fp32).  The partial sums are
-// those of the ROUNDED outputs - the values the BatchNorm that follows will actually read.  Register-resident kernels only
-// (csrc/dw_plane.hip): eat_dw_conv_b16_ok tells whether a geometry is covered.
 extern "C" int eat_dw_conv_fwd_stats_b16(const void* x, int x_b16, const float* in_a, const float* in_b, int in_act, const float* w,
                                          void* y, float* part, int inner_cap, int* h_inner, int B, int C, int F, int T,
                                          int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!x || !w || !y) return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats_b16: missing operand");
-  if ((in_a == nullptr) != (in_b == nullptr)) return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats_b16: in_a and in_b come together");
-  if (in_act < 0 || in_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats_b16: bad in_act %d", in_act);
-  if (!part || !h_inner || inner_cap < eat_dw_partials_inner(F, T, Fo, To, k, stride, 0))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats_b16: partial buffer too small (inner_cap %d)", inner_cap);
-  if ((F * T) % 2 != 0 || (Fo * To) % 2 != 0)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats_b16: planes must hold an even number of elements (%d, %d)", F * T, Fo * To);
-  int inner = 1;
-  const eat::DwEpi epi{part, nullptr, nullptr, nullptr, 0, nullptr, &inner};
-  const int rc = eat::dw_plane_try(reinterpret_cast<const float*>(x), w, nullptr, nullptr, reinterpret_cast<float*>(y), nullptr, B,
-                                   C, F, T, Fo, To, k, stride, EAT_ACT_NONE, 0, 0, in_a, in_b, in_act, (hipStream_t)stream, &epi,
-                                   x_b16 ? 1 : 2);
-  if (rc == 1)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_fwd_stats_b16: no register-resident kernel for F=%d T=%d k=%d stride=%d", F, T, k, stride);
-  *h_inner = inner;
-  return rc;
+  return dw_conv_fwd_stats_run("eat_dw_conv_fwd_stats_b16", x_b16 ? eat::kDwB16 : eat::kDwB16XF32, 0, x, in_a, in_b, in_act, w,
+                               y, part, inner_cap, h_inner, B, C, F, T, Fo, To, k, stride, stream);
 }
 
 // 1 where eat_dw_conv_fwd_stats_b16 and eat_dw_conv_bwd_bn_g_b16 cover the geometry (host helper: a training plan keeps fp32
@@ -321,33 +324,16 @@ extern "C" int eat_dw_conv_b16_ok(int B, int C, int F, int T, int Fo, int To, in
 extern "C" int eat_dw_conv_dyn_fwd_stats(const float* x, const float* in_a, const float* in_b, int in_act, const float* w_bc,
                                          float* y, float* part, int inner_cap, int* h_inner, int B, int C, int F, int T,
                                          int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  return dw_conv_fwd_stats_impl(1, x, in_a, in_b, in_act, w_bc, y, part, inner_cap, h_inner, B, C, F, T, Fo, To, k, stride,
-                                stream);
+  return dw_conv_fwd_stats_run("eat_dw_conv_dyn_fwd_stats", eat::kDwF32, 1, x, in_a, in_b, in_act, w_bc, y, part, inner_cap,
+                               h_inner, B, C, F, T, Fo, To, k, stride, stream);
 }
 
-// ... over bf16-stored x and y (the DyMN blocks of the bf16-storage plan; x_b16 = 0: the block without expand conv reads the
-// fp32 block input - tile geometries only): eat_dw_conv_fwd_stats_b16 with per-(b,c) taps.
+// ... over bf16-stored x and y (x_b16 = 0: the block without expand conv reads the fp32 block input - tile geometries only)
 extern "C" int eat_dw_conv_dyn_fwd_stats_b16(const void* x, int x_b16, const float* in_a, const float* in_b, int in_act,
                                              const float* w_bc, void* y, float* part, int inner_cap, int* h_inner, int B, int C,
                                              int F, int T, int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!x || !w_bc || !y) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_fwd_stats_b16: missing operand");
-  if ((in_a == nullptr) != (in_b == nullptr)) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_fwd_stats_b16: in_a and in_b come together");
-  if (in_act < 0 || in_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_fwd_stats_b16: bad in_act %d", in_act);
-  if (!part || !h_inner || inner_cap < eat_dw_partials_inner(F, T, Fo, To, k, stride, 0))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_fwd_stats_b16: partial buffer too small (inner_cap %d)", inner_cap);
-  if ((F * T) % 2 != 0 || (Fo * To) % 2 != 0)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_fwd_stats_b16: planes must hold an even number of elements (%d, %d)", F * T, Fo * To);
-  int inner = 1;
-  const eat::DwEpi epi{part, nullptr, nullptr, nullptr, 0, nullptr, &inner};
-  const int rc = eat::dw_plane_try(reinterpret_cast<const float*>(x), w_bc, nullptr, nullptr, reinterpret_cast<float*>(y), nullptr, B,
-                                   C, F, T, Fo, To, k, stride, EAT_ACT_NONE, 0, 1, in_a, in_b, in_act, (hipStream_t)stream, &epi,
-                                   x_b16 ? 1 : 2);
-  if (rc == 1)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_fwd_stats_b16: no register-resident kernel for F=%d T=%d k=%d stride=%d x_b16=%d", F, T, k, stride, x_b16);
-  *h_inner = inner;
-  return rc;
+  return dw_conv_fwd_stats_run("eat_dw_conv_dyn_fwd_stats_b16", x_b16 ? eat::kDwB16 : eat::kDwB16XF32, 1, x, in_a, in_b, in_act,
+                               w_bc, y, part, inner_cap, h_inner, B, C, F, T, Fo, To, k, stride, stream);
 }
 
 // stride-1 depthwise data gradient = the same sliding-window kernel with the taps read reversed

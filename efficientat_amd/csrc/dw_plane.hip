@@ -37,12 +37,9 @@ __device__ __forceinline__ float from_next(float v, bool last) {
   return (LPP < 64 && last) ? 0.0f : r;
 }
 
-// Optional transform of the conv INPUT, evaluated once per loaded element: act_in(in_a[c] * x + in_b[c]) - the train-mode
-// BatchNorm + activation of the expand conv, so that the activated tensor is never written (mn_train.py,
-// EAT_FUSE_EXPAND_BN).  Zero padding applies to the transformed map: elements outside the plane stay 0.
-struct InTf {
-  const float* a; const float* b; int act;
-};
+// InTf (eat_common.h) is the train-mode BatchNorm + activation of the expand conv, so that the activated tensor is never
+// written (mn_train.py, EAT_FUSE_EXPAND_BN).  Zero padding applies to the transformed map: elements outside the plane stay 0.
+using eat::InTf;
 struct TfCoef { float a, b, lo, ca, cb; };
 __device__ __forceinline__ TfCoef tf_coef(const InTf& t, int c) {
   TfCoef k;
@@ -64,7 +61,7 @@ struct PlaneArgs {
   InTf tf;
   eat::DwEpi epi;
   int per_plane_w;
-  int b16 = 0;           // 1: x and y are bf16 in HBM (act_io.h), 2: y only (x fp32) - the statistics instance only
+  eat::DwStore b16 = eat::kDwF32;   // kDwB16: x and y are bf16 in HBM (act_io.h), kDwB16XF32: y only - the statistics instance only
 };
 
 // d act(u) / du, PyTorch conventions (nn.ReLU / nn.Hardswish backward); `act` is wave-uniform
@@ -368,11 +365,11 @@ int launch_plane(const PlaneArgs& a0, hipStream_t s) {
   if (a.b16) {                                            // bf16 storage: train-mode conv + statistics (eat_dw_conv_fwd_stats_b16)
     if (!a.epi.stats || a.epi.gz || a.res || a.pool || a.act != EAT_ACT_NONE || a.flip) return 1;
     if (a.per_plane_w) {                                  // ... with per-plane taps (DyMN, eat_dw_conv_dyn_fwd_stats_b16): bf16 -> bf16
-      if (a.b16 == 2) return 1;
+      if (a.b16 == eat::kDwB16XF32) return 1;
       hipLaunchKernelGGL((dw_plane_kernel<K, S, CPL, LPP, F, PF, EAT_ACT_NONE, 0, true, true, eat::bf16_t>), grid, blk, 0, s, a, a.w, a.bias);
       return eat::check_launch("eat_dw_conv_dyn_fwd_stats_b16(plane)");
     }
-    if (a.b16 == 2)
+    if (a.b16 == eat::kDwB16XF32)
       hipLaunchKernelGGL((dw_plane_kernel<K, S, CPL, LPP, F, PF, EAT_ACT_NONE, 0, true, false, float, eat::bf16_t>), grid, blk, 0, s, a, a.w, a.bias);
     else
       hipLaunchKernelGGL((dw_plane_kernel<K, S, CPL, LPP, F, PF, EAT_ACT_NONE, 0, true, false, eat::bf16_t>), grid, blk, 0, s, a, a.w, a.bias);
@@ -409,7 +406,7 @@ struct TileArgs {
   int B, C, F, T, Fo, To, n_rc, n_cs, WO, flip, per_plane_w;
   InTf tf;
   eat::DwEpi epi;
-  int b16 = 0;           // x and y are bf16 in HBM (act_io.h): the statistics instance only
+  eat::DwStore b16 = eat::kDwF32;   // x and y (kDwB16XF32: y only) are bf16 in HBM (act_io.h): the statistics instance only
 };
 
 template <int K, int S, int RO, int ACT, int EPI, bool STATS, typename XT = float, typename YT = XT>
@@ -569,7 +566,7 @@ int launch_tile(TileArgs a, const float* w, const float* bias, int act, hipStrea
   if (a.epi.inner) *a.epi.inner = a.n_rc * a.n_cs;
   if (a.b16) {                                            // bf16 storage: train-mode conv + statistics
     if (!a.epi.stats || a.epi.gz || a.res || a.pool || act != EAT_ACT_NONE || a.flip) return 1;
-    if (a.b16 == 2)
+    if (a.b16 == eat::kDwB16XF32)
       hipLaunchKernelGGL((dw_tile_kernel<K, S, RO, EAT_ACT_NONE, 0, true, float, eat::bf16_t>), grid, blk, 0, s, a, w, bias);
     else
       hipLaunchKernelGGL((dw_tile_kernel<K, S, RO, EAT_ACT_NONE, 0, true, eat::bf16_t>), grid, blk, 0, s, a, w, bias);
@@ -1006,7 +1003,7 @@ struct DwBwdArgs {
   DzBn bn;
   const float* res;      // PPW: added to g (the gradient of a skip connection that ends at the conv input), or NULL
   float* gzpart;         // PPW: per-tile partials of sum g * x (x = the raw conv input), layout of gpart, or NULL
-  int b16 = 0;           // 1: dz, bn.z, x and g are bf16 in HBM (act_io.h), 2: dz and bn.z only - the BatchNorm-on-load instances
+  eat::DwStore b16 = eat::kDwF32;   // kDwB16: dz, bn.z, x and g are bf16 in HBM (act_io.h), kDwB16XF32: dz and bn.z only - the BatchNorm-on-load instances
 };
 
 // LPP = 64: a wave owns one tile of one plane (column strips with halo lanes).  LPP = 32 / 16 (small planes, T <= 2 LPP): a
@@ -1407,10 +1404,18 @@ int launch_dw_bwd(DwBwdArgs a, const float* w, int* h_inner, hipStream_t s, bool
   if (waves > 0x7fffffffLL) return 1;
   if (h_inner) *h_inner = a.n_rc * a.n_cs;
   const dim3 grid((unsigned)((waves + 3) / 4));
-  if (ppw && a.b16) {                                    // per-plane taps with bf16 storage (eat_dw_conv_dyn_bwd_bn_g_b16)
-    using BT = eat::bf16_t;
-    if (!bn) return 1;
-    if (a.b16 == 2) {                                     // x and g fp32 (the block without expand conv: 3x3 / stride 1 on the stem planes)
+  // the BatchNorm-on-load instances of one (taps, storage) kind: by lane-group width, whole rows or column strips
+#define EAT_BWD_BN(PPW_, XT_, ZT_)                                                                                               \
+  do {                                                                                                                          \
+    if (lpp == 64 && wr) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, true, PPW_, XT_, ZT_>), grid, dim3(256), 0, s, a, w);  \
+    else if (lpp == 64) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, false, PPW_, XT_, ZT_>), grid, dim3(256), 0, s, a, w); \
+    else if (lpp == 32) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 32, true, PPW_, XT_, ZT_>), grid, dim3(256), 0, s, a, w);  \
+    else hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 16, true, PPW_, XT_, ZT_>), grid, dim3(256), 0, s, a, w);                \
+  } while (0)
+  using BT = eat::bf16_t;
+  if ((ppw || a.b16) && !bn) return 1;                   // per-plane taps (DyMN), bf16 storage: the BatchNorm-on-load instances only
+  if (ppw && a.b16) {                                    // eat_dw_conv_dyn_bwd_bn_g_b16
+    if (a.b16 == eat::kDwB16XF32) {                       // x and g fp32 (the block without expand conv: 3x3 / stride 1 on the stem planes)
       if constexpr (K == 3 && S == 1 && RO == 8) {
         if (lpp == 64 && !wr) {
           hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, false, true, float, BT>), grid, dim3(256), 0, s, a, w);
@@ -1420,39 +1425,20 @@ int launch_dw_bwd(DwBwdArgs a, const float* w, int* h_inner, hipStream_t s, bool
       return 1;
     }
     if (a.res) return 1;                                  // (the fp32 skip gradient goes with an fp32 g)
-    if (lpp == 64 && wr) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, true, true, BT, BT>), grid, dim3(256), 0, s, a, w);
-    else if (lpp == 64) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, false, true, BT, BT>), grid, dim3(256), 0, s, a, w);
-    else if (lpp == 32) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 32, true, true, BT, BT>), grid, dim3(256), 0, s, a, w);
-    else hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 16, true, true, BT, BT>), grid, dim3(256), 0, s, a, w);
+    EAT_BWD_BN(true, BT, BT);
     return eat::check_launch("eat_dw_conv_dyn_bwd_bn_g_b16");
   }
-  if (ppw) {                                             // per-plane taps (DyMN): the BatchNorm-on-load instances only
-    if (!bn) return 1;
-    if (lpp == 64 && wr) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, true, true>), grid, dim3(256), 0, s, a, w);
-    else if (lpp == 64) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, false, true>), grid, dim3(256), 0, s, a, w);
-    else if (lpp == 32) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 32, true, true>), grid, dim3(256), 0, s, a, w);
-    else hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 16, true, true>), grid, dim3(256), 0, s, a, w);
+  if (ppw) {
+    EAT_BWD_BN(true, float, float);
     return eat::check_launch("eat_dw_conv_dyn_bwd_bn_g");
   }
   if (a.b16) {
-    using BT = eat::bf16_t;
-    if (!bn) return 1;
-#define EAT_BWD16(XT_)                                                                                                          \
-    do {                                                                                                                          \
-      if (lpp == 64 && wr) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, true, false, XT_, BT>), grid, dim3(256), 0, s, a, w);  \
-      else if (lpp == 64) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, false, false, XT_, BT>), grid, dim3(256), 0, s, a, w); \
-      else if (lpp == 32) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 32, true, false, XT_, BT>), grid, dim3(256), 0, s, a, w);  \
-      else hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 16, true, false, XT_, BT>), grid, dim3(256), 0, s, a, w);                \
-    } while (0)
-    if (a.b16 == 2) EAT_BWD16(float); else EAT_BWD16(BT);          // 2: x and g fp32 (a block without expand conv)
-#undef EAT_BWD16
+    if (a.b16 == eat::kDwB16XF32) EAT_BWD_BN(false, float, BT); else EAT_BWD_BN(false, BT, BT);   // XF32: x and g fp32 (a block without expand conv)
     return eat::check_launch("eat_dw_conv_bwd_bn_g_b16");
   }
   if (!bn) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, false, 64, false>), grid, dim3(256), 0, s, a, w);
-  else if (lpp == 64 && wr) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, true>), grid, dim3(256), 0, s, a, w);
-  else if (lpp == 64) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 64, false>), grid, dim3(256), 0, s, a, w);
-  else if (lpp == 32) hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 32, true>), grid, dim3(256), 0, s, a, w);
-  else hipLaunchKernelGGL((dw_bwd_tile_kernel<K, S, RO, true, 16, true>), grid, dim3(256), 0, s, a, w);
+  else EAT_BWD_BN(false, float, float);
+#undef EAT_BWD_BN
   return eat::check_launch("eat_dw_conv_bwd_g");
 }
 
@@ -1476,85 +1462,90 @@ int launch_plane_wgrad(const PlaneWgArgs& a0, hipStream_t s) {
 
 namespace eat {
 
-int dw_plane_try(const float* x, const float* w, const float* bias, const float* res, float* y, float* pool, int B, int C,
-                 int F, int T, int Fo, int To, int k, int stride, int act, int flip, int per_plane_w, const float* in_a,
-                 const float* in_b, int in_act, hipStream_t s, const DwEpi* epi_, int b16) {
-  const long long n_planes = (long long)B * C;
+// (the kernels' argument structs type every wide tensor float* and an instance reinterprets it by its XT / YT / ZT: here, next
+// to the launch_* that picks the instance, is the one place where a request's void* becomes that float*)
+int dw_plane_try(const DwFwdReq& r) {
+  const DwGeom& d = r.dim;
+  const float* x = static_cast<const float*>(r.x); float* y = static_cast<float*>(r.y);
+  const long long n_planes = (long long)d.B * d.C;
   if (n_planes > 0x3fffffffLL) return 1;                 // plane bases are 64-bit, offsets inside a plane 32-bit
-  if (res && act != EAT_ACT_NONE) return 1;              // residual add: the data-gradient form only
-  const DwEpi epi = epi_ ? *epi_ : DwEpi{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  if ((epi.stats || epi.gz) && (res || pool || act != EAT_ACT_NONE)) return 1;   // training epilogues: plain conv only
-  if (epi.gz && per_plane_w) return 1;
+  if (r.res && r.act != EAT_ACT_NONE) return 1;          // residual add: the data-gradient form only
+  const DwEpi epi = r.epi ? *r.epi : DwEpi{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+  if ((epi.stats || epi.gz) && (r.res || r.pool || r.act != EAT_ACT_NONE)) return 1;   // training epilogues: plain conv only
+  if (epi.gz && r.per_plane_w) return 1;
+  const int k = d.k, stride = d.stride, F = d.F, T = d.T;
   if (T > 128 && (long long)F * T < (1 << 28)) {            // large planes: tiles of rows x column strips
-    TileArgs ta{x, res, y, pool, B, C, F, T, Fo, To, 0, 0, 0, flip, per_plane_w, InTf{in_a, in_b, in_act}, epi, b16};
-    if (k == 3 && stride == 1) return launch_tile<3, 1, 16>(ta, w, bias, act, s);
-    if (k == 5 && stride == 1) return launch_tile<5, 1, 16>(ta, w, bias, act, s);
-    if (k == 3 && stride == 2) return launch_tile<3, 2, 8>(ta, w, bias, act, s);
-    if (k == 5 && stride == 2) return launch_tile<5, 2, 8>(ta, w, bias, act, s);
+    TileArgs ta{x, r.res, y, r.pool, d.B, d.C, F, T, d.Fo, d.To, 0, 0, 0, r.flip, r.per_plane_w, r.tf, epi, r.store};
+    if (k == 3 && stride == 1) return launch_tile<3, 1, 16>(ta, r.w, r.bias, r.act, r.stream);
+    if (k == 5 && stride == 1) return launch_tile<5, 1, 16>(ta, r.w, r.bias, r.act, r.stream);
+    if (k == 3 && stride == 2) return launch_tile<3, 2, 8>(ta, r.w, r.bias, r.act, r.stream);
+    if (k == 5 && stride == 2) return launch_tile<5, 2, 8>(ta, r.w, r.bias, r.act, r.stream);
   }
-  if (per_plane_w && (res || pool || act != EAT_ACT_NONE)) return 1;     // per-plane taps: the plain conv (+ statistics) only
-  PlaneArgs a{x, w, bias, res, y, pool, B, C, T, To, 2, flip, act, InTf{in_a, in_b, in_act}, epi, per_plane_w, b16};
-  if (k == 3 && stride == 1 && F == 8 && T > 32 && T <= 64) return launch_plane<3, 1, 1, 64, 8, true>(a, s);
+  if (r.per_plane_w && (r.res || r.pool || r.act != EAT_ACT_NONE)) return 1;     // per-plane taps: the plain conv (+ statistics) only
+  PlaneArgs a{x, r.w, r.bias, r.res, y, r.pool, d.B, d.C, T, d.To, 2, r.flip, r.act, r.tf, epi, r.per_plane_w, r.store};
+  if (k == 3 && stride == 1 && F == 8 && T > 32 && T <= 64) return launch_plane<3, 1, 1, 64, 8, true>(a, r.stream);
   // (no prefetch of the next plane group here: 2 x 16 rows x 2 columns of registers cost the occupancy it would buy)
-  if (k == 5 && stride == 1 && F == 16 && T > 64 && T <= 128) return launch_plane<5, 1, 2, 64, 16, false>(a, s);
-  if (k == 5 && stride == 2 && F == 8 && T > 32 && T <= 64) return launch_plane<5, 2, 2, 32, 8, true>(a, s);
-  if (k == 3 && stride == 2 && F == 16 && T > 64 && T <= 128) return launch_plane<3, 2, 2, 64, 16, true>(a, s);
-  if (k == 5 && stride == 1 && F == 4 && T <= 32) return launch_plane<5, 1, 1, 32, 4, true>(a, s);
-  (void)Fo;
+  if (k == 5 && stride == 1 && F == 16 && T > 64 && T <= 128) return launch_plane<5, 1, 2, 64, 16, false>(a, r.stream);
+  if (k == 5 && stride == 2 && F == 8 && T > 32 && T <= 64) return launch_plane<5, 2, 2, 32, 8, true>(a, r.stream);
+  if (k == 3 && stride == 2 && F == 16 && T > 64 && T <= 128) return launch_plane<3, 2, 2, 64, 16, true>(a, r.stream);
+  if (k == 5 && stride == 1 && F == 4 && T <= 32) return launch_plane<5, 1, 1, 32, 4, true>(a, r.stream);
   return 1;
 }
 
-int dw_plane_wgrad_try(const float* dz, const float* x, float* dw, int B, int C, int F, int T, int Fo, int To, int k,
-                       int stride, int per_plane, const float* in_a, const float* in_b, int in_act, hipStream_t s) {
-  if ((long long)B * C > 0x3fffffffLL) return 1;
+int dw_plane_wgrad_try(const DwWgradReq& r) {
+  const DwGeom& d = r.dim;
+  const int k = d.k, stride = d.stride, F = d.F, T = d.T;
+  if ((long long)d.B * d.C > 0x3fffffffLL) return 1;
   if (T > 128 && (long long)F * T < (1 << 28)) {
-    TileWgArgs ta{dz, x, dw, B, C, F, T, Fo, To, 0, 0, 0, 1, per_plane, InTf{in_a, in_b, in_act}};
-    if (k == 3 && stride == 1) return launch_tile_wgrad<3, 1, 16>(ta, s);
-    if (k == 3 && stride == 2) return launch_tile_wgrad<3, 2, 8>(ta, s);
-    if (k == 5 && stride == 2) return launch_tile_wgrad<5, 2, 8>(ta, s);
+    TileWgArgs ta{r.dz, r.x, r.dw, d.B, d.C, F, T, d.Fo, d.To, 0, 0, 0, 1, r.per_plane, r.tf};
+    if (k == 3 && stride == 1) return launch_tile_wgrad<3, 1, 16>(ta, r.stream);
+    if (k == 3 && stride == 2) return launch_tile_wgrad<3, 2, 8>(ta, r.stream);
+    if (k == 5 && stride == 2) return launch_tile_wgrad<5, 2, 8>(ta, r.stream);
   }
-  PlaneWgArgs a{dz, x, dw, B, C, T, To, 1, per_plane, InTf{in_a, in_b, in_act}};
-  if (k == 3 && stride == 1 && F == 8 && T > 32 && T <= 64) return launch_plane_wgrad<3, 1, 1, 64, 8>(a, s);
-  if (k == 5 && stride == 1 && F == 16 && T > 64 && T <= 128) return launch_plane_wgrad<5, 1, 2, 64, 16>(a, s);
-  if (k == 5 && stride == 2 && F == 8 && T > 32 && T <= 64) return launch_plane_wgrad<5, 2, 2, 32, 8>(a, s);
-  if (k == 3 && stride == 2 && F == 16 && T > 64 && T <= 128) return launch_plane_wgrad<3, 2, 2, 64, 16>(a, s);
-  if (k == 5 && stride == 1 && F == 4 && T <= 32) return launch_plane_wgrad<5, 1, 1, 32, 4>(a, s);
-  (void)Fo;
+  PlaneWgArgs a{r.dz, r.x, r.dw, d.B, d.C, T, d.To, 1, r.per_plane, r.tf};
+  if (k == 3 && stride == 1 && F == 8 && T > 32 && T <= 64) return launch_plane_wgrad<3, 1, 1, 64, 8>(a, r.stream);
+  if (k == 5 && stride == 1 && F == 16 && T > 64 && T <= 128) return launch_plane_wgrad<5, 1, 2, 64, 16>(a, r.stream);
+  if (k == 5 && stride == 2 && F == 8 && T > 32 && T <= 64) return launch_plane_wgrad<5, 2, 2, 32, 8>(a, r.stream);
+  if (k == 3 && stride == 2 && F == 16 && T > 64 && T <= 128) return launch_plane_wgrad<3, 2, 2, 64, 16>(a, r.stream);
+  if (k == 5 && stride == 1 && F == 4 && T <= 32) return launch_plane_wgrad<5, 1, 1, 32, 4>(a, r.stream);
   return 1;
 }
 
-int dw_bwd_try(const float* dz, const float* x, const float* in_a, const float* in_b, int in_act, const float* w, float* g,
-               float* dw, float* gpart, int* h_inner, int B, int C, int F, int T, int Fo, int To, int k, int stride,
-               hipStream_t s, const DwBnBwd* bn, int per_plane_w, const float* res, float* gzpart, int b16) {
-  if ((long long)B * C > 0x3fffffffLL || (long long)F * T >= (1 << 28)) return 1;
+int dw_bwd_try(const DwBwdReq& r) {
+  const DwGeom& d = r.dim;
+  const int k = d.k, stride = d.stride, F = d.F, T = d.T, Fo = d.Fo, To = d.To;
+  const DwBnBwd* bn = r.bn;
+  if ((long long)d.B * d.C > 0x3fffffffLL || (long long)F * T >= (1 << 28)) return 1;
   // Measured (MI355X, B = 256): the merged kernel wins on the LARGE planes (64x500 -> 32x250: 1.03 vs 1.47 ms, 32x250:
   // 0.35 vs 0.53 ms) and loses on the small late-layer planes, where the whole-plane kernels pack one or two planes per
   // wave with every lane busy (4x32 planes: 0.69 vs 0.35 ms; a wave of this kernel would use 18 of its 64 lanes)
   if (!bn && T <= 128) return 1;                       // (with the BatchNorm backward on load the small planes gain: fewer passes)
-  DwBwdArgs a{dz, x, g, dw, gpart, B, C, F, T, Fo, To, 0, 0, 0, 1, InTf{in_a, in_b, in_act},
-              DzBn{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, 0, 0}, res, gzpart, b16};
-  const bool ppw = per_plane_w != 0;
+  DwBwdArgs a{static_cast<const float*>(r.dz), static_cast<const float*>(r.x), static_cast<float*>(r.g), r.dw, r.gpart,
+              d.B, d.C, F, T, Fo, To, 0, 0, 0, 1, r.tf,
+              DzBn{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, 0, 0}, r.res, r.gzpart, r.store};
+  const bool ppw = r.per_plane_w != 0;
   if (ppw && !bn) return 1;
-  if (bn) a.bn = DzBn{bn->z, bn->a, bn->b, bn->mean, bn->invstd, bn->gscale, bn->gadd, bn->sums, (double)B * Fo * To, bn->act, bn->frozen};
+  if (bn) a.bn = DzBn{static_cast<const float*>(bn->z), bn->a, bn->b, bn->mean, bn->invstd, bn->gscale, bn->gadd, bn->sums,
+                      (double)d.B * Fo * To, bn->act, bn->frozen};
   if (stride == 1 && (Fo != F || To != T)) return 1;
   // 5x5 on planes of <= 4 (output) rows, the last stage of the network: tiles of 4 rows (half the multiply work of RO = 8)
-  if (bn && k == 5 && stride == 1 && F <= 4 && T <= 64) return launch_dw_bwd<5, 1, 4>(a, w, h_inner, s, ppw);
-  if (bn && k == 5 && stride == 2 && Fo <= 4 && T <= 64) return launch_dw_bwd<5, 2, 4>(a, w, h_inner, s, ppw);
-  if (k == 3 && stride == 1) return launch_dw_bwd<3, 1, 8>(a, w, h_inner, s, ppw);      // (RO = 16 needs 246 VGPRs)
-  if (k == 5 && stride == 1) return launch_dw_bwd<5, 1, 8>(a, w, h_inner, s, ppw);
-  if (k == 3 && stride == 2) return launch_dw_bwd<3, 2, 8>(a, w, h_inner, s, ppw);
-  if (k == 5 && stride == 2) return launch_dw_bwd<5, 2, 8>(a, w, h_inner, s, ppw);
+  if (bn && k == 5 && stride == 1 && F <= 4 && T <= 64) return launch_dw_bwd<5, 1, 4>(a, r.w, r.h_inner, r.stream, ppw);
+  if (bn && k == 5 && stride == 2 && Fo <= 4 && T <= 64) return launch_dw_bwd<5, 2, 4>(a, r.w, r.h_inner, r.stream, ppw);
+  if (k == 3 && stride == 1) return launch_dw_bwd<3, 1, 8>(a, r.w, r.h_inner, r.stream, ppw);      // (RO = 16 needs 246 VGPRs)
+  if (k == 5 && stride == 1) return launch_dw_bwd<5, 1, 8>(a, r.w, r.h_inner, r.stream, ppw);
+  if (k == 3 && stride == 2) return launch_dw_bwd<3, 2, 8>(a, r.w, r.h_inner, r.stream, ppw);
+  if (k == 5 && stride == 2) return launch_dw_bwd<5, 2, 8>(a, r.w, r.h_inner, r.stream, ppw);
   return 1;
 }
 
-int dw_tile_dgrad2_try(const float* dz, const float* w, const float* res, float* dx, int B, int C, int F, int T, int Fo,
-                       int To, int k, int per_plane_w, hipStream_t s, const DwEpi* epi_) {
-  if ((long long)B * C > 0x3fffffffLL || (long long)F * T >= (1 << 28)) return 1;
-  const DwEpi epi = epi_ ? *epi_ : DwEpi{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  if (epi.gz && (res || per_plane_w)) return 1;
-  TileDgArgs a{dz, res, dx, B, C, F, T, Fo, To, 0, 0, 0, per_plane_w, epi};
-  if (k == 3) return launch_tile_dgrad2<3>(a, w, s);
-  if (k == 5) return launch_tile_dgrad2<5>(a, w, s);
+int dw_tile_dgrad2_try(const DwDgrad2Req& r) {
+  const DwGeom& d = r.dim;
+  if ((long long)d.B * d.C > 0x3fffffffLL || (long long)d.F * d.T >= (1 << 28)) return 1;
+  const DwEpi epi = r.epi ? *r.epi : DwEpi{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+  if (epi.gz && (r.res || r.per_plane_w)) return 1;
+  TileDgArgs a{r.dz, r.res, r.dx, d.B, d.C, d.F, d.T, d.Fo, d.To, 0, 0, 0, r.per_plane_w, epi};
+  if (d.k == 3) return launch_tile_dgrad2<3>(a, r.w, r.stream);
+  if (d.k == 5) return launch_tile_dgrad2<5>(a, r.w, r.stream);
   return 1;
 }
 

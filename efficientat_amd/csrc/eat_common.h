@@ -109,27 +109,43 @@ int pw_conv_bf16_cat(const float* x1, int c1, const float* x2, int c2, const voi
 int pw_stream_try(const float* x, const void* wp, const float* bias, const float* in_scale, const float* res, float* y,
                   float* pool, int B, int Ci, int Co, int S, int act, int split, int ci_x, hipStream_t s);
 
-int dw_plane_try(const float* x, const float* w, const float* bias, const float* res, float* y, float* pool, int B,
-                 int C, int F, int T, int Fo, int To, int k, int stride, int act, int flip, int per_plane_w, const float* in_a,
-                 const float* in_b, int in_act, hipStream_t s, const DwEpi* epi = nullptr, int b16 = 0);
-int dw_plane_wgrad_try(const float* dz, const float* x, float* dw, int B, int C, int F, int T, int Fo, int To, int k,
-                       int stride, int per_plane, const float* in_a, const float* in_b, int in_act, hipStream_t s);
-// merged depthwise backward (dw_plane.hip): weight gradient + data gradient + activation-derivative epilogue in one pass;
-// returns 1 when switched off (EAT_DW_BWD_MERGED=0) or the geometry is out of range
+// ---- dw_plane.hip: the register-resident depthwise kernels.  Each dispatcher takes one request, filled by field name
+// (value-initialise it: every optional field is then NULL / 0), and returns 1 when no kernel covers it: the caller falls back.
+struct DwGeom { int B, C, F, T, Fo, To, k, stride; };      // conv input planes (F, T), output planes (Fo, To)
+// optional transform of the conv INPUT, evaluated once per loaded element: act(a[c] * x + b[c]); a == NULL: none
+struct InTf { const float* a; const float* b; int act; };
+// storage of the WIDE tensors in HBM (act_io.h) - x, y of the forward; dz, bn->z, x, g of the backward, void* in the requests:
+// all fp32 / all bf16 (the statistics forward and the BatchNorm-on-load backward instances only) / bf16 with the conv INPUT
+// side (x; g of the backward) fp32: a block without expand conv.  Narrow operands are always fp32.
+enum DwStore { kDwF32 = 0, kDwB16 = 1, kDwB16XF32 = 2 };
+
+struct DwFwdReq {
+  DwGeom dim; const void* x; const float* w; const float* bias; const float* res; void* y; float* pool;
+  int act, flip, per_plane_w; InTf tf; const DwEpi* epi; DwStore store; hipStream_t stream;
+};
+int dw_plane_try(const DwFwdReq& r);
+struct DwWgradReq { DwGeom dim; const float* dz; const float* x; float* dw; int per_plane; InTf tf; hipStream_t stream; };
+int dw_plane_wgrad_try(const DwWgradReq& r);
+// merged depthwise backward: weight gradient + data gradient + activation-derivative epilogue in one pass
 // bn != NULL: dz is the gradient w.r.t. the activated BatchNorm output of this conv; the BatchNorm + activation backward is
 // evaluated on load from (dz, bn->z) with the channel sums of the reduce pass (sums[0..C) = sum g, [C..2C) = sum g xhat)
 struct DwBnBwd {
-  const float* z; const float* a; const float* b; const float* mean; const float* invstd;
+  const void* z; const float* a; const float* b; const float* mean; const float* invstd;
   const float* gscale; const float* gadd; const double* sums; int act; int frozen;
 };
-int dw_bwd_try(const float* dz, const float* x, const float* in_a, const float* in_b, int in_act, const float* w, float* g,
-               float* dw, float* gpart, int* h_inner, int B, int C, int F, int T, int Fo, int To, int k, int stride,
-               hipStream_t s, const DwBnBwd* bn = nullptr, int per_plane_w = 0, const float* res = nullptr,
-               float* gzpart = nullptr, int b16 = 0);
-// b16 (dw_plane_try, dw_bwd_try): the wide tensors (x and y; dz, bn->z, x and g) are bf16 in HBM (act_io.h) and the pointers
-// are really bf16_t*: the statistics forward / the BatchNorm-on-load backward instances only, 1 = geometry not covered
-int dw_tile_dgrad2_try(const float* dz, const float* w, const float* res, float* dx, int B, int C, int F, int T, int Fo,
-                       int To, int k, int per_plane_w, hipStream_t s, const DwEpi* epi = nullptr);
+struct DwBwdReq {
+  DwGeom dim; const void* dz; const void* x; InTf tf; const float* w; void* g; float* dw; float* gpart; int* h_inner;
+  const DwBnBwd* bn; int per_plane_w;
+  const float* res;      // per_plane_w: added to g after the partial sums are taken, or NULL
+  float* gzpart;         // per_plane_w: per-tile sums of g * x, layout of gpart, or NULL
+  DwStore store; hipStream_t stream;
+};
+int dw_bwd_try(const DwBwdReq& r);
+// stride-2 data gradient on tiles (dim.stride is 2; epi with gz: the training epilogue)
+struct DwDgrad2Req {
+  DwGeom dim; const float* dz; const float* w; const float* res; float* dx; int per_plane_w; const DwEpi* epi; hipStream_t stream;
+};
+int dw_tile_dgrad2_try(const DwDgrad2Req& r);
 
 }  // namespace eat
 

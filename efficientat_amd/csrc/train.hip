@@ -1,19 +1,12 @@
-// Training-step kernels for gfx950: batch-statistics BatchNorm (forward and backward, with the
-// activation folded in), squeeze-excitation reductions, and the weight/data gradients of the
-// depthwise and pointwise convolutions.
-//   reference semantics: nn.BatchNorm2d(eps=1e-3, momentum=0.01) in train mode
-//   (models/mn/model.py:114-115), nn.Hardswish / nn.ReLU, autograd of F.conv2d
-//   (SURVEY.md Appendix C lists the formulas the reference leaves to autograd).
-// Round-1 structure: every pass is its own streaming kernel over (B, C, S) planes (one workgroup
-// per plane, float4 along the time axis, wave-shuffle + LDS block reduction, per-channel totals
-// accumulated in fp64 atomics so that sums over up to 8M elements do not lose precision).
+// 1x1 (pointwise) weight-gradient and Gram-matrix kernels of the training step for gfx950, their launch plan
+// (wgrad_plan) and entry points: autograd of F.conv2d w.r.t. the weight (SURVEY.md Appendix C lists the formulas the
+// reference leaves to autograd).  The BatchNorm passes are in bn_train.hip, the depthwise / stem gradients in dw_grad.hip.
 #include <cstdlib>
 #include "eat_common.h"
 #include "act_io.h"
 
 namespace {
 
-using eat::Io;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // Optional transform of the x operand of the 1x1 weight gradient: x' = act(a[ci] * x + b[ci]) evaluated on load (training:
@@ -35,557 +28,6 @@ __device__ __forceinline__ float wg_tf(float v, float a, float b, int act) {
   const float lo = act == EAT_ACT_RELU ? 0.0f : -__builtin_huge_valf();
   const float ca = act == EAT_ACT_HSWISH ? (1.0f / 6.0f) : 0.0f, cb = act == EAT_ACT_HSWISH ? 0.5f : 1.0f;
   return fmaxf(u, lo) * __builtin_amdgcn_fmed3f(fmaf(u, ca, cb), 0.0f, 1.0f);
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_grad(float u) {   // d act(u) / du  (PyTorch conventions)
-  if constexpr (ACT == EAT_ACT_RELU) return u > 0.0f ? 1.0f : 0.0f;
-  if constexpr (ACT == EAT_ACT_HSWISH) return u < -3.0f ? 0.0f : (u <= 3.0f ? u * (1.0f / 3.0f) + 0.5f : 1.0f);
-  return 1.0f;
-}
-
-// block-wide sum of two values; result valid in thread 0
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* s_red) {
-  a = eat::wave_sum(a);
-  b = eat::wave_sum(b);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) { s_red[wv] = a; s_red[8 + wv] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int nw = blockDim.x >> 6;
-    float ta = 0.f, tb = 0.f;
-    for (int i = 0; i < nw; ++i) { ta += s_red[i]; tb += s_red[8 + i]; }
-    a = ta; b = tb;
-  }
-}
-
-// ---- per-channel sum / sum of squares of z (B,C,S) -----------------------------------------
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ z, int C, int S,
-                                                       double* __restrict__ sums) {
-  __shared__ float s_red[16];
-  const int plane = blockIdx.x, c = plane % C;
-  const float* p = z + (size_t)plane * S;
-  float s1 = 0.f, s2 = 0.f;
-  if ((S & 3) == 0) {
-#pragma unroll 4
-    for (int i = threadIdx.x * 4; i < S; i += blockDim.x * 4) {
-      const float4 v = *reinterpret_cast<const float4*>(p + i);
-      s1 += (v.x + v.y) + (v.z + v.w);
-      s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-    }
-  } else {
-    for (int i = threadIdx.x; i < S; i += blockDim.x) { const float v = p[i]; s1 += v; s2 += v * v; }
-  }
-  block_sum2(s1, s2, s_red);
-  if (threadIdx.x == 0) {
-    atomicAdd(sums + c, (double)s1);
-    atomicAdd(sums + C + c, (double)s2);
-  }
-}
-
-// Small planes (late stages: 8x63, 4x32 positions): with one block per plane the 2 x B x C fp64 atomics on C addresses
-// are the whole cost (~50 us per launch for 20 MB tensors, 46 launches per step).  Here a block owns PPB samples of ONE
-// channel: the same coalesced float4 reads, PPB times fewer atomics per channel.
-__global__ __launch_bounds__(256) void bn_stats_multi_kernel(const float* __restrict__ z, int B, int C, int S4, int PPB,
-                                                             double* __restrict__ sums) {
-  __shared__ float s_red[16];
-  const int c = blockIdx.x, b0 = blockIdx.y * PPB;
-  const int nb = (B - b0) < PPB ? (B - b0) : PPB;
-  float s1 = 0.f, s2 = 0.f;
-  for (int e = threadIdx.x; e < nb * S4; e += 256) {
-    const int bl = e / S4, i = e - bl * S4;
-    const float4 v = *reinterpret_cast<const float4*>(z + ((size_t)(b0 + bl) * C + c) * (4 * S4) + 4 * i);
-    s1 += (v.x + v.y) + (v.z + v.w);
-    s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-  }
-  block_sum2(s1, s2, s_red);
-  if (threadIdx.x == 0) {
-    atomicAdd(sums + c, (double)s1);
-    atomicAdd(sums + C + c, (double)s2);
-  }
-}
-
-// ---- finalize: batch mean / biased var -> affine (a, b), saved (mean, invstd), running buffers --
-__global__ void bn_finalize_kernel(const double* __restrict__ sums, const float* __restrict__ gamma,
-                                   const float* __restrict__ beta, float* __restrict__ running_mean,
-                                   float* __restrict__ running_var, float momentum, float eps, double n, int C,
-                                   float* __restrict__ a, float* __restrict__ b, float* __restrict__ mean,
-                                   float* __restrict__ invstd) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double mu = sums[c] / n;
-  double var = sums[C + c] / n - mu * mu;
-  if (var < 0.0) var = 0.0;
-  const float is = (float)(1.0 / sqrt(var + (double)eps));
-  const float av = gamma[c] * is;
-  a[c] = av;
-  b[c] = beta[c] - (float)mu * av;
-  mean[c] = (float)mu;
-  invstd[c] = is;
-  if (running_mean) {
-    const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
-    running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mu;
-    running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
-}
-
-// ---- y = act(a_c z + b_c) [+ res]; optional per-(b,c) sums of y (SE squeeze / head pool) ----------
-// ZT / YT: storage types of z / y (act_io.h; bf16 in the bf16-storage plan: the pool sums the values as STORED; ZT = bf16 with
-// YT = float: the project conv's BatchNorm - z_p is stored in bf16, the block output it produces is an fp32 tensor)
-template <int ACT, typename ZT = float, typename YT = ZT>
-__global__ __launch_bounds__(256) void bn_act_fwd_kernel(const ZT* __restrict__ z, const float* __restrict__ a,
-                                                         const float* __restrict__ b, const float* __restrict__ res,
-                                                         YT* __restrict__ y, float* __restrict__ pool, int C, int S,
-                                                         eat::bf16_t* __restrict__ y16 = nullptr) {
-  // y16: optional bf16 COPY of an fp32 y (the block output of the bf16-storage plan: the next block's expand conv reads the
-  // copy - bit-identical to reading y, the conv rounds its operand the same way - at half the operand traffic)
-  __shared__ float s_red[16];
-  const int plane = blockIdx.x, c = plane % C;
-  const float av = a[c], bv = b[c];
-  const size_t base = (size_t)plane * S;
-  float ps = 0.f, dummy = 0.f;
-  if ((S & 3) == 0) {
-#pragma unroll 4
-    for (int i = threadIdx.x * 4; i < S; i += blockDim.x * 4) {
-      const float4 v = Io<ZT>::load4(z + base + i);
-      float4 o = make_float4(eat::activate<ACT>(fmaf(av, v.x, bv)), eat::activate<ACT>(fmaf(av, v.y, bv)),
-                             eat::activate<ACT>(fmaf(av, v.z, bv)), eat::activate<ACT>(fmaf(av, v.w, bv)));
-      if (res) {
-        const float4 r = *reinterpret_cast<const float4*>(res + base + i);
-        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-      }
-      if constexpr (Io<YT>::kBf) { o.x = eat::bf_round(o.x); o.y = eat::bf_round(o.y); o.z = eat::bf_round(o.z); o.w = eat::bf_round(o.w); }
-      if (y) Io<YT>::store4(y + base + i, o);
-      if (y16) Io<eat::bf16_t>::store4(y16 + base + i, o);
-      ps += (o.x + o.y) + (o.z + o.w);
-    }
-  } else {
-    for (int i = threadIdx.x; i < S; i += blockDim.x) {
-      float o = Io<YT>::rnd(eat::activate<ACT>(fmaf(av, Io<ZT>::load1(z + base + i), bv)) + (res ? res[base + i] : 0.0f));
-      if (y) Io<YT>::store1(y + base + i, o);
-      if (y16) Io<eat::bf16_t>::store1(y16 + base + i, o);
-      ps += o;
-    }
-  }
-  if (pool) {
-    block_sum2(ps, dummy, s_red);
-    if (threadIdx.x == 0) pool[plane] = ps;       // one block per plane: plain store, no atomics
-  }
-}
-
-// g = (dy * gscale[b,c] + gadd[b,c]) * act'(a z + b);  xhat = (z - mean) * invstd
-template <int ACT>
-__device__ __forceinline__ float grad_pre(float dy, float zv, float av, float bv, float gs, float ga) {
-  return fmaf(dy, gs, ga) * act_grad<ACT>(fmaf(av, zv, bv));
-}
-
-// ---- backward pass 1: per-channel sum g and sum g*xhat -------------------------------------------------
-template <int ACT, typename ZT = float, typename DT = ZT>
-__global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(
-    const DT* __restrict__ dy, const ZT* __restrict__ z, const float* __restrict__ a,
-    const float* __restrict__ b, const float* __restrict__ mean, const float* __restrict__ invstd,
-    const float* __restrict__ gscale, const float* __restrict__ gadd, int C, int S, double* __restrict__ sums) {
-  __shared__ float s_red[16];
-  const int plane = blockIdx.x, c = plane % C;
-  const float av = a[c], bv = b[c], mu = mean[c], is = invstd[c];
-  const float gs = gscale ? gscale[plane] : 1.0f, ga = gadd ? gadd[plane] : 0.0f;
-  const size_t base = (size_t)plane * S;
-  float s1 = 0.f, s2 = 0.f;
-  if ((S & 3) == 0) {
-#pragma unroll 4
-    for (int i = threadIdx.x * 4; i < S; i += blockDim.x * 4) {
-      const float4 d = Io<DT>::load4(dy + base + i);
-      const float4 v = Io<ZT>::load4(z + base + i);
-      const float g0 = grad_pre<ACT>(d.x, v.x, av, bv, gs, ga), g1 = grad_pre<ACT>(d.y, v.y, av, bv, gs, ga);
-      const float g2 = grad_pre<ACT>(d.z, v.z, av, bv, gs, ga), g3 = grad_pre<ACT>(d.w, v.w, av, bv, gs, ga);
-      s1 += (g0 + g1) + (g2 + g3);
-      s2 += (g0 * (v.x - mu) + g1 * (v.y - mu)) + (g2 * (v.z - mu) + g3 * (v.w - mu));
-    }
-  } else {
-    for (int i = threadIdx.x; i < S; i += blockDim.x) {
-      const float zv = Io<ZT>::load1(z + base + i);
-      const float g = grad_pre<ACT>(Io<DT>::load1(dy + base + i), zv, av, bv, gs, ga);
-      s1 += g;
-      s2 += g * (zv - mu);
-    }
-  }
-  s2 *= is;
-  block_sum2(s1, s2, s_red);
-  if (threadIdx.x == 0) {
-    atomicAdd(sums + c, (double)s1);
-    atomicAdd(sums + C + c, (double)s2);
-  }
-}
-
-// small planes: one block per (channel, PPB samples), see bn_stats_multi_kernel
-template <int ACT, typename ZT = float, typename DT = ZT>
-__global__ __launch_bounds__(256) void bn_act_bwd_reduce_multi_kernel(
-    const DT* __restrict__ dy, const ZT* __restrict__ z, const float* __restrict__ a,
-    const float* __restrict__ b, const float* __restrict__ mean, const float* __restrict__ invstd,
-    const float* __restrict__ gscale, const float* __restrict__ gadd, int B, int C, int S4, int PPB,
-    double* __restrict__ sums) {
-  __shared__ float s_red[16];
-  const int c = blockIdx.x, b0 = blockIdx.y * PPB;
-  const int nb = (B - b0) < PPB ? (B - b0) : PPB;
-  const float av = a[c], bv = b[c], mu = mean[c], is = invstd[c];
-  float s1 = 0.f, s2 = 0.f;
-  for (int e = threadIdx.x; e < nb * S4; e += 256) {
-    const int bl = e / S4, i = e - bl * S4;
-    const size_t plane = (size_t)(b0 + bl) * C + c;
-    const float gs = gscale ? gscale[plane] : 1.0f, ga = gadd ? gadd[plane] : 0.0f;
-    const float4 d = Io<DT>::load4(dy + plane * (4 * S4) + 4 * i);
-    const float4 v = Io<ZT>::load4(z + plane * (4 * S4) + 4 * i);
-    const float g0 = grad_pre<ACT>(d.x, v.x, av, bv, gs, ga), g1 = grad_pre<ACT>(d.y, v.y, av, bv, gs, ga);
-    const float g2 = grad_pre<ACT>(d.z, v.z, av, bv, gs, ga), g3 = grad_pre<ACT>(d.w, v.w, av, bv, gs, ga);
-    s1 += (g0 + g1) + (g2 + g3);
-    s2 += (g0 * (v.x - mu) + g1 * (v.y - mu)) + (g2 * (v.z - mu) + g3 * (v.w - mu));
-  }
-  s2 *= is;
-  block_sum2(s1, s2, s_red);
-  if (threadIdx.x == 0) {
-    atomicAdd(sums + c, (double)s1);
-    atomicAdd(sums + C + c, (double)s2);
-  }
-}
-
-// ---- backward pass 2: dz = a * (g - sum_g/N - xhat * sum_gx/N) ----------------------------------------------
-// DT: storage type of dy AND dz (fp32; bf16: the expand BatchNorm of a DyMN block under the bf16-storage plan, g_e -> dz_e in place)
-template <int ACT, typename ZT = float, typename DT = float>
-__global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
-    const DT* __restrict__ dy, const ZT* __restrict__ z, const float* __restrict__ a,
-    const float* __restrict__ b, const float* __restrict__ mean, const float* __restrict__ invstd,
-    const float* __restrict__ gscale, const float* __restrict__ gadd, const double* __restrict__ sums,
-    DT* __restrict__ dz, int C, int S, double n, eat::bf16_t* __restrict__ dz16 = nullptr) {
-  // dz16: optional bf16 COPY of dz (what the data-gradient 1x1 conv of the bf16-storage plan reads: see bn_act_fwd_kernel)
-  const int plane = blockIdx.x, c = plane % C;
-  const float av = a[c], bv = b[c], mu = mean[c], is = invstd[c];
-  const float m1 = (float)(sums[c] / n), m2 = (float)(sums[C + c] / n);
-  const float gs = gscale ? gscale[plane] : 1.0f, ga = gadd ? gadd[plane] : 0.0f;
-  const size_t base = (size_t)plane * S;
-  auto f = [&](float d, float v) {
-    const float g = grad_pre<ACT>(d, v, av, bv, gs, ga);
-    return av * (g - m1 - (v - mu) * is * m2);
-  };
-  if ((S & 3) == 0) {
-#pragma unroll 4
-    for (int i = threadIdx.x * 4; i < S; i += blockDim.x * 4) {
-      const float4 d = Io<DT>::load4(dy + base + i);
-      const float4 v = Io<ZT>::load4(z + base + i);
-      const float4 o = make_float4(f(d.x, v.x), f(d.y, v.y), f(d.z, v.z), f(d.w, v.w));
-      Io<DT>::store4(dz + base + i, o);
-      if (dz16) Io<eat::bf16_t>::store4(dz16 + base + i, o);
-    }
-  } else {
-    for (int i = threadIdx.x; i < S; i += blockDim.x) {
-      const float o = f(Io<DT>::load1(dy + base + i), Io<ZT>::load1(z + base + i));
-      Io<DT>::store1(dz + base + i, o);
-      if (dz16) Io<eat::bf16_t>::store1(dz16 + base + i, o);
-    }
-  }
-}
-
-// ---- out[b,c] = sum_s u[b,c,s] * v'[b,c,s], v' = v or act(a_c v + b_c) (SE: d scale) ---------------------------------
-template <int ACT>
-__global__ __launch_bounds__(256) void plane_dot_kernel(const float* __restrict__ u, const float* __restrict__ v,
-                                                        const float* __restrict__ a, const float* __restrict__ b,
-                                                        float* __restrict__ out, int C, int S) {
-  __shared__ float s_red[16];
-  const int plane = blockIdx.x, c = plane % C;
-  const float av = a ? a[c] : 1.0f, bv = b ? b[c] : 0.0f;
-  const size_t base = (size_t)plane * S;
-  float s1 = 0.f, dummy = 0.f;
-  for (int i = threadIdx.x; i < S; i += blockDim.x) {
-    float t = v[base + i];
-    if (a) t = eat::activate<ACT>(fmaf(av, t, bv));
-    s1 += u[base + i] * t;
-  }
-  block_sum2(s1, dummy, s_red);
-  if (threadIdx.x == 0) out[plane] = s1;
-}
-
-// ---- depthwise data gradient: dx[c,i,j] = sum_{u,v} w[c,u,v] dz[c,(i+p-u)/s,(j+p-v)/s] (+ res) ----------
-template <int K, int STRIDE>
-__global__ __launch_bounds__(256) void dw_dgrad_kernel(const float* __restrict__ dz, const float* __restrict__ w,
-                                                       const float* __restrict__ res, float* __restrict__ dx,
-                                                       int C, int F, int T, int Fo, int To, int per_plane_w) {
-  constexpr int P = (K - 1) / 2;
-  const int plane = blockIdx.y, c = plane % C;
-  float wr[K * K];
-#pragma unroll
-  for (int i = 0; i < K * K; ++i) wr[i] = w[(size_t)(per_plane_w ? plane : c) * K * K + i];
-  const float* g = dz + (size_t)plane * Fo * To;
-  const size_t base = (size_t)plane * F * T;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < F * T; e += gridDim.x * blockDim.x) {
-    const int i = e / T, j = e - i * T;
-    float acc = res ? res[base + e] : 0.0f;
-#pragma unroll
-    for (int u = 0; u < K; ++u) {
-      const int ii = i + P - u;
-      if (ii < 0 || (ii % STRIDE) != 0) continue;
-      const int io = ii / STRIDE;
-      if (io >= Fo) continue;
-#pragma unroll
-      for (int v = 0; v < K; ++v) {
-        const int jj = j + P - v;
-        if (jj < 0 || (jj % STRIDE) != 0) continue;
-        const int jo = jj / STRIDE;
-        if (jo < To) acc = fmaf(wr[u * K + v], g[(size_t)io * To + jo], acc);
-      }
-    }
-    dx[base + e] = acc;
-  }
-}
-
-// ---- depthwise data gradient, stride 2, sliding form: one thread per dx column j walking down the
-// rows; only the taps whose parity matches contribute (<= ceil(K/2)^2 loads per element instead of
-// K*K predicated iterations), lanes on consecutive j read dz at half stride (coalesced).
-template <int K>
-__global__ __launch_bounds__(256) void dw_dgrad_s2_kernel(const float* __restrict__ dz, const float* __restrict__ w,
-                                                          const float* __restrict__ res, float* __restrict__ dx,
-                                                          int n_planes, int C, int F, int T, int Fo, int To,
-                                                          int per_plane_w) {
-  // Polyphase form: dx[i][j] = sum over the taps (u, v) with (i + P - u), (j + P - v) even of w[u][v] dz[(i+P-u)/2][(j+P-v)/2].
-  // The column parity of a thread is fixed, so its tap columns v = v0 + 2q are selected ONCE into registers (the round-1
-  // kernel indexed the tap array with run-time (u, v) inside the row loop); the rows are walked in pairs (2m, 2m+1), whose
-  // tap rows are compile-time constants, over a sliding window of dz rows m-1, m, m+1 - every dz row is loaded once per
-  // thread, one row ahead of its use.  Writes are coalesced 256-byte row segments per wave.
-  constexpr int P = (K - 1) / 2;
-  constexpr int NV = (K + 1) / 2;
-  const int j = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int plane = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (plane >= n_planes || j >= T) return;
-  const int c = plane % C;
-  const float* wp = w + (size_t)(per_plane_w ? plane : c) * K * K;
-  const int v0 = (j + P) & 1;
-  float ws[K][NV];
-  int jo[NV];
-  bool jok[NV];
-#pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    const int v = v0 + 2 * q;
-    jo[q] = (j + P - v) >> 1;
-    jok[q] = v < K && (j + P - v) >= 0 && jo[q] < To;
-    if (!jok[q]) jo[q] = 0;
-#pragma unroll
-    for (int u = 0; u < K; ++u) ws[u][q] = v < K ? wp[u * K + v] : 0.0f;
-  }
-  const float* g = dz + (size_t)plane * Fo * To;
-  auto load_row = [&](int io, float (&r)[NV]) {
-    const bool rok = io >= 0 && io < Fo;
-    const float* row = g + (size_t)(rok ? io : 0) * To;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) r[q] = (rok && jok[q]) ? row[jo[q]] : 0.0f;
-  };
-  const size_t base = (size_t)plane * F * T + j;
-  float rm[NV], r0[NV], r1[NV], r2[NV];        // dz rows m-1, m, m+1 and the prefetched m+2
-#pragma unroll
-  for (int q = 0; q < NV; ++q) rm[q] = 0.0f;
-  load_row(0, r0);
-  load_row(1, r1);
-  for (int m = 0; 2 * m < F; ++m) {
-    load_row(m + 2, r2);
-    const int ie = 2 * m, io_ = 2 * m + 1;
-    float ae = res ? res[base + (size_t)ie * T] : 0.0f;
-    float ao = (res && io_ < F) ? res[base + (size_t)io_ * T] : 0.0f;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-      if constexpr (K == 3) {
-        ae = fmaf(ws[1][q], r0[q], ae);                                 // row 2m:   u = 1 -> dz row m
-        ao = fmaf(ws[0][q], r1[q], fmaf(ws[2][q], r0[q], ao));          // row 2m+1: u = 0 -> m+1, u = 2 -> m
-      } else {
-        ae = fmaf(ws[0][q], r1[q], fmaf(ws[2][q], r0[q], fmaf(ws[4][q], rm[q], ae)));   // u = 0, 2, 4 -> m+1, m, m-1
-        ao = fmaf(ws[1][q], r1[q], fmaf(ws[3][q], r0[q], ao));                          // u = 1, 3    -> m+1, m
-      }
-    }
-    dx[base + (size_t)ie * T] = ae;
-    if (io_ < F) dx[base + (size_t)io_ * T] = ao;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) { rm[q] = r0[q]; r0[q] = r1[q]; r1[q] = r2[q]; }
-  }
-}
-
-// ---- depthwise / stem weight gradient: dw[c,u,v] = sum_{b,i,j} dz[b,c,i,j] x[b,cx,i*s+u-p,j*s+v-p] -------
-// One block per (channel, batch slice); x has XC channels (XC == C depthwise, XC == 1 stem).
-template <int K, int STRIDE>
-__global__ __launch_bounds__(256) void dw_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ x,
-                                                       float* __restrict__ dw, int B, int C, int XC, int F, int T,
-                                                       int Fo, int To, int b_per_block, int per_sample) {
-  constexpr int P = (K - 1) / 2;
-  __shared__ float s_red[4][K * K];
-  const int c = blockIdx.x, b0 = blockIdx.y * b_per_block;
-  const int b1 = (b0 + b_per_block) < B ? (b0 + b_per_block) : B;
-  float acc[K * K];
-#pragma unroll
-  for (int i = 0; i < K * K; ++i) acc[i] = 0.f;
-  const int plane_o = Fo * To;
-  for (int bb = b0; bb < b1; ++bb) {
-    const float* g = dz + ((size_t)bb * C + c) * plane_o;
-    const float* xp = x + ((size_t)bb * XC + (XC == 1 ? 0 : c)) * F * T;
-    for (int e = threadIdx.x; e < plane_o; e += blockDim.x) {
-      const int i = e / To, j = e - i * To;
-      const float gv = g[e];
-#pragma unroll
-      for (int u = 0; u < K; ++u) {
-        const int fi = i * STRIDE + u - P;
-        const bool rok = fi >= 0 && fi < F;
-#pragma unroll
-        for (int v = 0; v < K; ++v) {
-          const int ti = j * STRIDE + v - P;
-          const float xv = (rok && ti >= 0 && ti < T) ? xp[(size_t)fi * T + ti] : 0.0f;
-          acc[u * K + v] = fmaf(gv, xv, acc[u * K + v]);
-        }
-      }
-    }
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < K * K; ++i) {
-    const float t = eat::wave_sum(acc[i]);
-    if (lane == 0) s_red[wv][i] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < K * K)
-    atomicAdd(dw + ((size_t)(per_sample ? b0 * C : 0) + c) * K * K + threadIdx.x,
-              s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
-}
-
-
-// Stem weight gradient (models/mn/model.py:124-133: 3x3 / stride 2, ONE input channel, C = 16 w output channels):
-// dW[c][u][v] = sum_{b,i,j} dz[b,c,i,j] x[b,0,2i+u-1,2j+v-1].  The generic kernel above walks one channel per block and
-// gathers 9 predicated x values per dz element (710 us at B = 256 for 655 MB: 0.9 TB/s).  Here a thread owns output
-// columns, keeps the 3x3 x window of a position in registers and applies it to 16 channels at once (16 coalesced dz
-// loads per position, the window is loaded once per position and channel group), 144 accumulators per thread; one
-// wave reduction + 144 atomics per block.
-template <int CG>
-__global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ x,
-                                                         float* __restrict__ dw, int C, int F, int T, int Fo, int To,
-                                                         int rows_per_block) {
-  __shared__ float s_red[4][CG * 9];
-  const int b = blockIdx.y;
-  const int i0 = blockIdx.x * rows_per_block;
-  const int i1 = (i0 + rows_per_block) < Fo ? (i0 + rows_per_block) : Fo;
-  const float* xb = x + (size_t)b * F * T;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int c0 = 0; c0 < C; c0 += CG) {
-    float acc[CG][9];
-#pragma unroll
-    for (int c = 0; c < CG; ++c)
-#pragma unroll
-      for (int t = 0; t < 9; ++t) acc[c][t] = 0.0f;
-    const float* gz = dz + ((size_t)b * C + c0) * Fo * To;
-    for (int i = i0; i < i1; ++i) {
-      for (int j = threadIdx.x; j < To; j += 256) {
-        float xw[9];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-          const int fi = 2 * i + u - 1;
-          const bool rok = fi >= 0 && fi < F;
-#pragma unroll
-          for (int v = 0; v < 3; ++v) {
-            const int ti = 2 * j + v - 1;
-            xw[u * 3 + v] = (rok && ti >= 0 && ti < T) ? xb[(size_t)fi * T + ti] : 0.0f;
-          }
-        }
-        const size_t pos = (size_t)i * To + j;
-#pragma unroll
-        for (int c = 0; c < CG; ++c) {
-          const float g = (c0 + c < C) ? gz[(size_t)c * Fo * To + pos] : 0.0f;
-#pragma unroll
-          for (int t = 0; t < 9; ++t) acc[c][t] = fmaf(g, xw[t], acc[c][t]);
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < CG; ++c)
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const float v = eat::wave_sum(acc[c][t]);
-        if (lane == 0) s_red[wv][c * 9 + t] = v;
-      }
-    __syncthreads();
-    for (int e = threadIdx.x; e < CG * 9; e += 256) {
-      const int c = e / 9;
-      if (c0 + c < C) atomicAdd(dw + (size_t)(c0 + c) * 9 + (e - c * 9), s_red[0][e] + s_red[1][e] + s_red[2][e] + s_red[3][e]);
-    }
-    __syncthreads();
-  }
-}
-
-// Column-walking variant (depthwise, XC == C): the kernel above loads K*K predicated 4-byte x values per output
-// element (25 narrow loads for a 5x5) and is bound by the texture unit at ~1.4 TB/s.  Here a thread owns one output
-// column of one (b, c) plane and walks down the rows with the K x K input window in a register ring, as the forward
-// kernel does: K*STRIDE new x values + one dz value per output.  A block = one channel, TY samples x TX columns, and
-// loops over its slice of the batch; the K*K partial sums are reduced once per block (shuffles, LDS, K*K atomics).
-template <int K, int STRIDE>
-__global__ __launch_bounds__(256) void dw_wgrad_col_kernel(const float* __restrict__ dz, const float* __restrict__ x,
-                                                           float* __restrict__ dw, int B, int C, int F, int T, int Fo,
-                                                           int To, int TX, int b_per_block, int per_sample,
-                                                           const float* __restrict__ in_a,
-                                                           const float* __restrict__ in_b, int in_act) {
-  constexpr int P = (K - 1) / 2;
-  constexpr int NSLOT = K;                              // ring of K rows: step R uses slots (u + R*STRIDE) % K
-  __shared__ float s_red[4][K * K];
-  const int tid = threadIdx.x;
-  const int tx = tid % TX, ty = tid / TX, TY = 256 / TX;
-  const int to = blockIdx.x * TX + tx;
-  const int c = blockIdx.y;
-  const int b0 = blockIdx.z * b_per_block;
-  const int b1 = (b0 + b_per_block) < B ? (b0 + b_per_block) : B;
-  float acc[K * K];
-#pragma unroll
-  for (int i = 0; i < K * K; ++i) acc[i] = 0.f;
-  // in_a != NULL: the conv input was act_in(in_a[c] * x + in_b[c]) evaluated on load (eat_dw_conv_fwd_tf)
-  const bool has_tf = in_a != nullptr;
-  const float ia = has_tf ? in_a[c] : 1.0f, ib = has_tf ? in_b[c] : 0.0f;
-  if (to < To) {
-    const int t0 = to * STRIDE - P;
-    bool cok[K];
-#pragma unroll
-    for (int v = 0; v < K; ++v) cok[v] = (t0 + v >= 0) && (t0 + v < T);
-    for (int bb = b0 + ty; bb < b1; bb += TY) {
-      const float* g = dz + ((size_t)bb * C + c) * Fo * To + to;
-      const float* xp = x + ((size_t)bb * C + c) * F * T;
-      float win[NSLOT][K];
-      auto load_row = [&](int fi, float (&dst)[K]) {
-        const bool rok = fi >= 0 && fi < F;
-        const float* src = xp + (size_t)(rok ? fi : 0) * T + t0;
-        if (has_tf) {
-#pragma unroll
-          for (int v = 0; v < K; ++v) dst[v] = (rok && cok[v]) ? eat::activate_rt(fmaf(ia, src[v], ib), in_act) : 0.0f;
-        } else {
-#pragma unroll
-          for (int v = 0; v < K; ++v) dst[v] = (rok && cok[v]) ? src[v] : 0.0f;
-        }
-      };
-#pragma unroll
-      for (int u = 0; u < K - STRIDE; ++u) load_row(u - P, win[u]);      // rows kept from "step -1"
-      for (int fo0 = 0; fo0 < Fo; fo0 += K) {
-#pragma unroll
-        for (int R = 0; R < K; ++R) {                   // K steps = one full rotation of the ring
-          const int fo = fo0 + R;
-          if (fo < Fo) {
-#pragma unroll
-            for (int u = K - STRIDE; u < K; ++u) load_row(fo * STRIDE - P + u, win[(u + R * STRIDE) % NSLOT]);
-            const float gv = g[(size_t)fo * To];
-#pragma unroll
-            for (int u = 0; u < K; ++u)
-#pragma unroll
-              for (int v = 0; v < K; ++v) acc[u * K + v] = fmaf(gv, win[(u + R * STRIDE) % NSLOT][v], acc[u * K + v]);
-          }
-        }
-      }
-    }
-  }
-  const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int i = 0; i < K * K; ++i) {
-    const float t = eat::wave_sum(acc[i]);
-    if (lane == 0) s_red[wv][i] = t;
-  }
-  __syncthreads();
-  if (tid < K * K)
-    atomicAdd(dw + ((size_t)(per_sample ? b0 * C : 0) + c) * K * K + tid,
-              s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid]);
 }
 
 // ---- pointwise weight gradient: dW[co,ci] = sum_{b,s} dz[b,co,s] x[b,ci,s] --------------------------------------
@@ -1457,473 +899,6 @@ static void launch_narrow(const float* dz, const float* x, const float* x_scale,
 }
 
 }  // namespace
-
-#define EAT_PLANES_GRID(B, C) dim3((unsigned)((B) * (C)))
-
-// samples per block of the small-plane reducers: ~2048 blocks; 0 = use the one-block-per-plane kernels
-static int bn_multi_ppb(int B, int C, int S) {
-  if ((S & 3) != 0 || S > 2048 || (long long)B * C <= 4096) return 0;
-  long long ppb = ((long long)B * C + 2047) / 2048;
-  return (int)(ppb > B ? B : ppb);
-}
-
-extern "C" int eat_bn_stats(const float* z, int B, int C, int S, double* sums, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (const int ppb = bn_multi_ppb(B, C, S)) {
-    hipLaunchKernelGGL(bn_stats_multi_kernel, dim3(C, (B + ppb - 1) / ppb), dim3(256), 0, (hipStream_t)stream, z, B, C, S >> 2,
-                       ppb, sums);
-    return eat::check_launch("eat_bn_stats");
-  }
-  hipLaunchKernelGGL(bn_stats_kernel, EAT_PLANES_GRID(B, C), dim3(S >= 1024 ? 256 : 64), 0, (hipStream_t)stream, z, C, S,
-                     sums);
-  return eat::check_launch("eat_bn_stats");
-}
-
-extern "C" int eat_bn_finalize(const double* sums, const float* gamma, const float* beta, float* running_mean,
-                               float* running_var, float momentum, float eps, double n, int C, float* a, float* b,
-                               float* mean, float* invstd, eat_stream_t stream) {
-  eat::clear_stale_error();
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, (hipStream_t)stream, sums, gamma, beta,
-                     running_mean, running_var, momentum, eps, n, C, a, b, mean, invstd);
-  return eat::check_launch("eat_bn_finalize");
-}
-
-extern "C" int eat_bn_act_fwd(const float* z, const float* a, const float* b, const float* res, float* y,
-                              float* pool, int B, int C, int S, int act, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_bn_act_fwd: bad act %d", act);
-  const dim3 blk(S >= 1024 ? 256 : 64);
-  EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_fwd_kernel<ACT>), EAT_PLANES_GRID(B, C), blk, 0, (hipStream_t)stream, z,
-                                           a, b, res, y, pool, C, S));
-  return eat::check_launch("eat_bn_act_fwd");
-}
-
-extern "C" int eat_bn_act_bwd_reduce(const float* dy, const float* z, const float* a, const float* b,
-                                     const float* mean, const float* invstd, const float* gscale, const float* gadd,
-                                     int B, int C, int S, int act, double* sums, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_bn_act_bwd_reduce: bad act %d", act);
-  if (const int ppb = bn_multi_ppb(B, C, S)) {
-    EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_bwd_reduce_multi_kernel<ACT>), dim3(C, (B + ppb - 1) / ppb), dim3(256), 0,
-                                             (hipStream_t)stream, dy, z, a, b, mean, invstd, gscale, gadd, B, C, S >> 2, ppb, sums));
-    return eat::check_launch("eat_bn_act_bwd_reduce");
-  }
-  const dim3 blk(S >= 1024 ? 256 : 64);
-  EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<ACT>), EAT_PLANES_GRID(B, C), blk, 0,
-                                           (hipStream_t)stream, dy, z, a, b, mean, invstd, gscale, gadd, C, S, sums));
-  return eat::check_launch("eat_bn_act_bwd_reduce");
-}
-
-// ---- bf16 copy of a NARROW fp32 tensor of the bf16-storage plan (block input / project-BatchNorm gradient of the widest
-// blocks): the 1x1 conv kernel rounds its fp32 operand to bf16 in any case (same RNE rounding: the conv results are
-// bit-identical), but it stages a bf16 operand at half the L2 -> LDS traffic and with two LDS stages - on the 448 -> 2688
-// expand conv at S = 504, B = 128 that is 324 -> 238 us for a 24 us copy.
-namespace {
-__global__ __launch_bounds__(256) void cast_b16_kernel(const float* __restrict__ x, eat::bf16_t* __restrict__ y, long long n8) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-    const float4 p = reinterpret_cast<const float4*>(x)[2 * i], q = reinterpret_cast<const float4*>(x)[2 * i + 1];
-    uint4 o;
-    o.x = eat::pack_bf2(p.x, p.y); o.y = eat::pack_bf2(p.z, p.w); o.z = eat::pack_bf2(q.x, q.y); o.w = eat::pack_bf2(q.z, q.w);
-    reinterpret_cast<uint4*>(y)[i] = o;
-  }
-}
-}  // namespace
-extern "C" int eat_cast_b16(const float* x, void* y, long long n, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!x || !y || n < 8 || (n & 7)) return eat::fail(EAT_EINVAL, "eat_cast_b16: n=%lld must be a positive multiple of 8", n);
-  const long long n8 = n >> 3;
-  const long long blocks = (n8 + 255) / 256;
-  hipLaunchKernelGGL(cast_b16_kernel, dim3((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16)), dim3(256), 0, (hipStream_t)stream,
-                     x, reinterpret_cast<eat::bf16_t*>(y), n8);
-  return eat::check_launch("eat_cast_b16");
-}
-
-// ---- the two stand-alone BatchNorm passes of the bf16-storage plan (act_io.h; BASELINE configs[2]): the depthwise output
-// z_d and the gradient arriving at it are bf16 in HBM.  Same arithmetic as the fp32 entry points; y (or NULL) is written in
-// bf16 and `pool` sums the ROUNDED values - what the project conv will read.  (S % 4 != 0: element-wise path.)
-extern "C" int eat_bn_act_fwd_b16(const void* z, const float* a, const float* b, const float* res, void* y, int y_b16,
-                                  void* y_copy16, float* pool, int B, int C, int S, int act, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_bn_act_fwd_b16: bad act %d", act);
-  if (!z || B < 1 || C < 1 || S < 1) return eat::fail(EAT_EINVAL, "eat_bn_act_fwd_b16: bad shape");
-  if ((res || y_copy16) && y_b16)
-    return eat::fail(EAT_EINVAL, "eat_bn_act_fwd_b16: a residual / a bf16 copy goes with an fp32 output only");
-  const dim3 blk(S >= 1024 ? 256 : 64);
-  const eat::bf16_t* z16 = reinterpret_cast<const eat::bf16_t*>(z);
-  if (y_b16)
-    EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_fwd_kernel<ACT, eat::bf16_t>), EAT_PLANES_GRID(B, C), blk, 0, (hipStream_t)stream,
-                                             z16, a, b, (const float*)nullptr, reinterpret_cast<eat::bf16_t*>(y), pool, C, S));
-  else
-    EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_fwd_kernel<ACT, eat::bf16_t, float>), EAT_PLANES_GRID(B, C), blk, 0,
-                                             (hipStream_t)stream, z16, a, b, res, reinterpret_cast<float*>(y), pool, C, S,
-                                             reinterpret_cast<eat::bf16_t*>(y_copy16)));
-  return eat::check_launch("eat_bn_act_fwd_b16");
-}
-
-extern "C" int eat_bn_act_bwd_reduce_b16(const void* dy, int dy_b16, const void* z, const float* a, const float* b,
-                                         const float* mean, const float* invstd, const float* gscale, const float* gadd, int B,
-                                         int C, int S, int act, double* sums, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_bn_act_bwd_reduce_b16: bad act %d", act);
-  if (!dy || !z || B < 1 || C < 1 || S < 1) return eat::fail(EAT_EINVAL, "eat_bn_act_bwd_reduce_b16: bad shape");
-  const eat::bf16_t* z16 = reinterpret_cast<const eat::bf16_t*>(z);
-  const int ppb = bn_multi_ppb(B, C, S);
-  const dim3 blk(S >= 1024 ? 256 : 64);
-#define EAT_RED16(DT_, dyp)                                                                                                  \
-  do {                                                                                                                      \
-    if (ppb) {                                                                                                              \
-      EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_bwd_reduce_multi_kernel<ACT, eat::bf16_t, DT_>), dim3(C, (B + ppb - 1) / ppb), \
-                                               dim3(256), 0, (hipStream_t)stream, dyp, z16, a, b, mean, invstd, gscale, gadd, B, C, \
-                                               S >> 2, ppb, sums));                                                         \
-    } else {                                                                                                                \
-      EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<ACT, eat::bf16_t, DT_>), EAT_PLANES_GRID(B, C), blk, 0,   \
-                                               (hipStream_t)stream, dyp, z16, a, b, mean, invstd, gscale, gadd, C, S, sums)); \
-    }                                                                                                                       \
-  } while (0)
-  if (dy_b16) EAT_RED16(eat::bf16_t, reinterpret_cast<const eat::bf16_t*>(dy));
-  else EAT_RED16(float, reinterpret_cast<const float*>(dy));
-#undef EAT_RED16
-  return eat::check_launch("eat_bn_act_bwd_reduce_b16");
-}
-
-// apply pass over a bf16-stored z (the project conv's output z_p in the bf16-storage plan): dy and dz are fp32
-extern "C" int eat_bn_act_bwd_apply_b16(const float* dy, const void* z, const float* a, const float* b, const float* mean,
-                                        const float* invstd, const float* gscale, const float* gadd, const double* sums,
-                                        float* dz, void* dz_copy16, int B, int C, int S, int act, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_bn_act_bwd_apply_b16: bad act %d", act);
-  if (!dy || !z || !dz || B < 1 || C < 1 || S < 1) return eat::fail(EAT_EINVAL, "eat_bn_act_bwd_apply_b16: bad shape");
-  const dim3 blk(S >= 1024 ? 256 : 64);
-  const double n = (double)B * S;
-  EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_bwd_apply_kernel<ACT, eat::bf16_t>), EAT_PLANES_GRID(B, C), blk, 0,
-                                           (hipStream_t)stream, dy, reinterpret_cast<const eat::bf16_t*>(z), a, b, mean, invstd,
-                                           gscale, gadd, sums, dz, C, S, n, reinterpret_cast<eat::bf16_t*>(dz_copy16)));
-  return eat::check_launch("eat_bn_act_bwd_apply_b16");
-}
-
-// ... with dy AND dz in bf16 too (dz may alias dy): the expand BatchNorm of a DyMN block under the bf16-storage plan - g_e, z_e
-// and dz_e are all wide tensors (models/dymn/dy_block.py:313-318 backward)
-extern "C" int eat_bn_bwd_apply_b16(const void* dy, const void* z, const float* a, const float* b, const float* mean,
-                                    const float* invstd, const double* sums, void* dz, int B, int C, int S, int act,
-                                    eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_bn_bwd_apply_b16: bad act %d", act);
-  if (!dy || !z || !dz || !sums || B < 1 || C < 1 || S < 1) return eat::fail(EAT_EINVAL, "eat_bn_bwd_apply_b16: bad arguments");
-  const dim3 blk(S >= 1024 ? 256 : 64);
-  const double n = (double)B * S;
-  EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_bwd_apply_kernel<ACT, eat::bf16_t, eat::bf16_t>), EAT_PLANES_GRID(B, C), blk, 0,
-                                           (hipStream_t)stream, reinterpret_cast<const eat::bf16_t*>(dy),
-                                           reinterpret_cast<const eat::bf16_t*>(z), a, b, mean, invstd, (const float*)nullptr,
-                                           (const float*)nullptr, sums, reinterpret_cast<eat::bf16_t*>(dz), C, S, n,
-                                           (eat::bf16_t*)nullptr));
-  return eat::check_launch("eat_bn_bwd_apply_b16");
-}
-
-extern "C" int eat_bn_act_bwd_apply(const float* dy, const float* z, const float* a, const float* b,
-                                    const float* mean, const float* invstd, const float* gscale, const float* gadd,
-                                    const double* sums, float* dz, int B, int C, int S, int act, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_bn_act_bwd_apply: bad act %d", act);
-  const dim3 blk(S >= 1024 ? 256 : 64);
-  const double n = (double)B * S;
-  EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((bn_act_bwd_apply_kernel<ACT>), EAT_PLANES_GRID(B, C), blk, 0,
-                                           (hipStream_t)stream, dy, z, a, b, mean, invstd, gscale, gadd, sums, dz, C, S, n));
-  return eat::check_launch("eat_bn_act_bwd_apply");
-}
-
-extern "C" int eat_plane_dot(const float* u, const float* v, const float* a, const float* b, float* out, int B,
-                             int C, int S, int act, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_plane_dot: bad act %d", act);
-  const dim3 blk(S >= 1024 ? 256 : 64);
-  EAT_DISPATCH_ACT(act, hipLaunchKernelGGL((plane_dot_kernel<ACT>), EAT_PLANES_GRID(B, C), blk, 0, (hipStream_t)stream, u,
-                                           v, a, b, out, C, S));
-  return eat::check_launch("eat_plane_dot");
-}
-
-static int dw_dgrad_impl(const float* dz, const float* w, const float* res, float* dx, int B, int C, int F, int T,
-                         int Fo, int To, int k, int stride, int per_plane_w, eat_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (stride == 1 && (k == 3 || k == 5)) {
-    return eat::dw_conv_dgrad_s1(dz, w, nullptr, res, dx, B, C, F, T, k, per_plane_w, s);
-  }
-  if (stride == 2 && (k == 3 || k == 5)) {
-    // tile kernel (dw_plane.hip): one dz column per lane, dx row segments as 8-byte stores; 1 = not applicable
-    const int rc = eat::dw_tile_dgrad2_try(dz, w, res, dx, B, C, F, T, Fo, To, k, per_plane_w, s);
-    if (rc != 1) return rc;
-    dim3 g2((T + 63) / 64, (B * C + 3) / 4);
-    if (k == 3) hipLaunchKernelGGL((dw_dgrad_s2_kernel<3>), g2, dim3(256), 0, s, dz, w, res, dx, B * C, C, F, T, Fo, To, per_plane_w);
-    else hipLaunchKernelGGL((dw_dgrad_s2_kernel<5>), g2, dim3(256), 0, s, dz, w, res, dx, B * C, C, F, T, Fo, To, per_plane_w);
-    return eat::check_launch("eat_dw_conv_dgrad");
-  }
-  int gx = (F * T + 255) / 256;
-  if (gx > 64) gx = 64;
-  dim3 grid(gx, B * C);
-#define EAT_DG(KK, SS) hipLaunchKernelGGL((dw_dgrad_kernel<KK, SS>), grid, dim3(256), 0, s, dz, w, res, dx, C, F, T, Fo, To, per_plane_w)
-  if (k == 3 && stride == 1) EAT_DG(3, 1);
-  else if (k == 3 && stride == 2) EAT_DG(3, 2);
-  else if (k == 5 && stride == 1) EAT_DG(5, 1);
-  else if (k == 5 && stride == 2) EAT_DG(5, 2);
-  else return eat::fail(EAT_EINVAL, "eat_dw_conv_dgrad: unsupported k=%d stride=%d", k, stride);
-#undef EAT_DG
-  return eat::check_launch("eat_dw_conv_dgrad");
-}
-
-extern "C" int eat_dw_conv_dgrad(const float* dz, const float* w, const float* res, float* dx, int B, int C, int F,
-                                 int T, int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  return dw_dgrad_impl(dz, w, res, dx, B, C, F, T, Fo, To, k, stride, 0, stream);
-}
-
-// Depthwise data gradient with the backward of the PRECEDING (forward order) BatchNorm + activation started in its
-// epilogue: g = dgrad(dz) * act'(ga[c] * gz + gb[c]) and the per-wave partial sums of g (gpart [b][C][inner]); gz is the
-// pre-BN output of the expand conv (same shape as g).  See train_fuse.hip for what consumes g / gpart.
-extern "C" int eat_dw_conv_dgrad_g(const float* dz, const float* w, const float* gz, const float* ga, const float* gb,
-                                   int gact, float* g, float* gpart, int inner_cap, int* h_inner, int B, int C, int F,
-                                   int T, int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!gz || !ga || !gb || !gpart || !h_inner) return eat::fail(EAT_EINVAL, "eat_dw_conv_dgrad_g: gz, ga, gb, gpart, h_inner are required");
-  if (gact < 0 || gact > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_dgrad_g: bad act %d", gact);
-  if (inner_cap < eat_dw_partials_inner(F, T, Fo, To, k, stride, 1))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dgrad_g: partial buffer too small (inner_cap %d)", inner_cap);
-  hipStream_t s = (hipStream_t)stream;
-  if ((k == 3 || k == 5) && (stride == 1 || stride == 2)) {
-    int inner = 1;
-    const eat::DwEpi epi{nullptr, gz, ga, gb, gact, gpart, &inner};
-    const int rc = stride == 1 ? eat::dw_conv_dgrad_s1(dz, w, nullptr, nullptr, g, B, C, F, T, k, 0, s, &epi)
-                               : eat::dw_tile_dgrad2_try(dz, w, nullptr, g, B, C, F, T, Fo, To, k, 0, s, &epi);
-    if (rc != 1) { *h_inner = inner; return rc; }
-  }
-  const int rc = dw_dgrad_impl(dz, w, nullptr, g, B, C, F, T, Fo, To, k, stride, 0, stream);
-  if (rc != 0) return rc;
-  *h_inner = 1;
-  return eat::act_grad_sum(g, gz, ga, gb, gact, g, gpart, B, C, F * T, s);
-}
-
-extern "C" int eat_dw_conv_dyn_dgrad(const float* dz, const float* w_bc, const float* res, float* dx, int B, int C,
-                                     int F, int T, int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  return dw_dgrad_impl(dz, w_bc, res, dx, B, C, F, T, Fo, To, k, stride, 1, stream);
-}
-
-static int dw_wgrad_impl(const float* dz, const float* x, float* dw, int B, int C, int XC, int F, int T, int Fo, int To,
-                         int k, int stride, int per_sample, eat_stream_t stream, const float* in_a = nullptr,
-                         const float* in_b = nullptr, int in_act = 0) {
-  if (XC != C && XC != 1) return eat::fail(EAT_EINVAL, "eat_dw_conv_wgrad: x must have C or 1 channels");
-  if (in_a && XC != C) return eat::fail(EAT_EINVAL, "eat_dw_conv_wgrad_tf: needs the column-walking kernel");
-  if (XC == C) {
-    // register-resident kernels (dw_plane.hip): every element loaded once; 1 = geometry not instantiated
-    const int rc = eat::dw_plane_wgrad_try(dz, x, dw, B, C, F, T, Fo, To, k, stride, per_sample, in_a, in_b, in_act,
-                                           (hipStream_t)stream);
-    if (rc != 1) return rc;
-  }
-  if (XC == C && !per_sample && (k == 3 || k == 5) && (stride == 1 || stride == 2)) {
-    // column-walking kernel: block = (column tile, channel, batch slice)
-    const int TX = To > 32 ? 64 : 32, TY = 256 / TX;
-    const int ct = (To + TX - 1) / TX;
-    int bpb = per_sample ? 1 : B;
-    if (!per_sample) {
-      // ~2048 blocks, but every thread should walk several planes before the block-wide reduction
-      long long want = (2048 + (long long)C * ct - 1) / ((long long)C * ct);
-      if (want < 1) want = 1;
-      bpb = (int)((B + want - 1) / want);
-      if (bpb < 4 * TY) bpb = 4 * TY < B ? 4 * TY : B;
-    }
-    dim3 grid(ct, C, (B + bpb - 1) / bpb);
-    hipStream_t s = (hipStream_t)stream;
-#define EAT_WGC(KK, SS) hipLaunchKernelGGL((dw_wgrad_col_kernel<KK, SS>), grid, dim3(256), 0, s, dz, x, dw, B, C, F, T, Fo, To, TX, bpb, per_sample, in_a, in_b, in_act)
-    if (k == 3 && stride == 1) EAT_WGC(3, 1);
-    else if (k == 3 && stride == 2) EAT_WGC(3, 2);
-    else if (k == 5 && stride == 1) EAT_WGC(5, 1);
-    else EAT_WGC(5, 2);
-#undef EAT_WGC
-    return eat::check_launch("eat_dw_conv_wgrad");
-  }
-  if (XC == 1 && k == 3 && stride == 2 && !per_sample) {
-    // ~2048 blocks: (row chunks) x (samples)
-    int rpb = (int)(((long long)Fo * B + 2047) / 2048);
-    if (rpb < 1) rpb = 1;
-    hipLaunchKernelGGL(stem_wgrad_kernel<16>, dim3((Fo + rpb - 1) / rpb, B), dim3(256), 0, (hipStream_t)stream, dz, x, dw, C, F, T,
-                       Fo, To, rpb);
-    return eat::check_launch("eat_dw_conv_wgrad(stem)");
-  }
-  // enough blocks to fill the chip: split the batch when there are few channels
-  int splits = (2048 + C - 1) / C;
-  if (splits > B || per_sample) splits = B;
-  const int bpb = (B + splits - 1) / splits;
-  dim3 grid(C, (B + bpb - 1) / bpb);
-  hipStream_t s = (hipStream_t)stream;
-#define EAT_WG(KK, SS) hipLaunchKernelGGL((dw_wgrad_kernel<KK, SS>), grid, dim3(256), 0, s, dz, x, dw, B, C, XC, F, T, Fo, To, bpb, per_sample)
-  if (k == 3 && stride == 1) EAT_WG(3, 1);
-  else if (k == 3 && stride == 2) EAT_WG(3, 2);
-  else if (k == 5 && stride == 1) EAT_WG(5, 1);
-  else if (k == 5 && stride == 2) EAT_WG(5, 2);
-  else return eat::fail(EAT_EINVAL, "eat_dw_conv_wgrad: unsupported k=%d stride=%d", k, stride);
-#undef EAT_WG
-  return eat::check_launch("eat_dw_conv_wgrad");
-}
-
-extern "C" int eat_dw_conv_wgrad(const float* dz, const float* x, float* dw, int B, int C, int XC, int F, int T,
-                                 int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  return dw_wgrad_impl(dz, x, dw, B, C, XC, F, T, Fo, To, k, stride, 0, stream);
-}
-
-extern "C" int eat_dw_conv_wgrad_tf(const float* dz, const float* x, const float* in_a, const float* in_b, int in_act,
-                                    float* dw, int B, int C, int F, int T, int Fo, int To, int k, int stride,
-                                    eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!in_a || !in_b) return eat::fail(EAT_EINVAL, "eat_dw_conv_wgrad_tf: in_a and in_b are required");
-  if (in_act < 0 || in_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_wgrad_tf: bad in_act %d", in_act);
-  return dw_wgrad_impl(dz, x, dw, B, C, C, F, T, Fo, To, k, stride, 0, stream, in_a, in_b, in_act);
-}
-
-// Backward of the depthwise conv of an inverted-residual block in ONE pass (autograd of models/mn/block_types.py:150-162
-// + the first half of the backward of the expand conv's BatchNorm + activation): from dz (B,C,Fo,To) and the pre-BN expand
-// output x (B,C,F,T) with its BN affine (in_a, in_b) and activation in_act
-//   dw (C,k,k) += weight gradient w.r.t. the conv input act(in_a x + in_b)            [dw zeroed by the caller]
-//   g (B,C,F,T) = dgrad(dz) * act'(in_a x + in_b),   gpart [B][C][inner] = per-tile sums of g
-// = eat_dw_conv_wgrad_tf + eat_dw_conv_dgrad_g with dz and x read once.  inner_cap >= eat_dw_bwd_partials_inner(...)
-// AND >= eat_dw_partials_inner(..., 1) (the two-kernel fallback writes its own layout); *h_inner receives inner.
-extern "C" int eat_dw_conv_bwd_g(const float* dz, const float* x, const float* in_a, const float* in_b, int in_act,
-                                 const float* w, float* g, float* dw, float* gpart, int inner_cap, int* h_inner, int B,
-                                 int C, int F, int T, int Fo, int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!in_a || !in_b || !gpart || !h_inner) return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_g: in_a, in_b, gpart, h_inner are required");
-  if (in_act < 0 || in_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_g: bad act %d", in_act);
-  if (inner_cap < eat_dw_bwd_partials_inner(F, T, Fo, To, k, stride) || inner_cap < eat_dw_partials_inner(F, T, Fo, To, k, stride, 1))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_g: partial buffer too small (inner_cap %d)", inner_cap);
-  if ((k == 3 || k == 5) && (stride == 1 || stride == 2)) {
-    const int rc = eat::dw_bwd_try(dz, x, in_a, in_b, in_act, w, g, dw, gpart, h_inner, B, C, F, T, Fo, To, k, stride,
-                                   (hipStream_t)stream);
-    if (rc != 1) return rc;
-  }
-  int rc = dw_wgrad_impl(dz, x, dw, B, C, C, F, T, Fo, To, k, stride, 0, stream, in_a, in_b, in_act);
-  if (rc != 0) return rc;
-  return eat_dw_conv_dgrad_g(dz, w, x, in_a, in_b, in_act, g, gpart, inner_cap, h_inner, B, C, F, T, Fo, To, k, stride, stream);
-}
-
-// The same with the BatchNorm + activation backward of THIS conv's output evaluated on load (dw_plane.hip, DzBn): dy is the
-// gradient w.r.t. act(BN(z)) (times gscale[b,c] plus gadd[b,c] for a squeeze-excitation block), sums the fp64 channel sums
-// of eat_bn_act_bwd_reduce / eat_se_bn_bwd_combine.  Blocks without an expand conv: in_a = 1, in_b = 0, in_act = none,
-// gpart may be NULL.  Only the geometries of the merged kernel:
-// eat_dw_bwd_merged_ok(...) != 0, else EAT_EINVAL.
-static int dw_bwd_bn_geometry_ok(int B, int C, int F, int T, int Fo, int To, int k, int stride) {
-  if ((long long)B * C > 0x3fffffffLL || (long long)F * T >= (1 << 28)) return 0;
-  if (!((k == 3 || k == 5) && (stride == 1 || stride == 2))) return 0;
-  if (stride == 1 && (Fo != F || To != T)) return 0;
-  if ((long long)4 * C * F * T * 4 >= 0x7fffffffLL) return 0;         // lane-group offsets inside a wave's samples are 32-bit
-  return 1;
-}
-
-// Host helper: 1 where eat_dw_conv_bwd_bn_g runs AND is the faster plan (EAT_DW_BN_K5=0: 5x5 convs keep the apply pass +
-// eat_dw_conv_bwd_g - their on-load instances sit at 240 registers and gain 4 % only).
-extern "C" int eat_dw_bwd_merged_ok(int B, int C, int F, int T, int Fo, int To, int k, int stride) {
-  return dw_bwd_bn_geometry_ok(B, C, F, T, Fo, To, k, stride);
-}
-
-extern "C" int eat_dw_conv_bwd_bn_g(const float* dy, const float* z, const float* bn_a, const float* bn_b,
-                                    const float* bn_mean, const float* bn_invstd, const float* gscale, const float* gadd,
-                                    const double* sums, int bn_act, int frozen, const float* x, const float* in_a,
-                                    const float* in_b, int in_act, const float* w, float* g, float* dw,
-                                    float* gpart, int inner_cap, int* h_inner, int B, int C, int F, int T, int Fo, int To,
-                                    int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!dy || !z || !bn_a || !bn_b || !bn_mean || !bn_invstd || !sums || !in_a || !in_b)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g: missing operand");
-  if (in_act < 0 || in_act > 2 || bn_act < 0 || bn_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g: bad act");
-  if (!dw_bwd_bn_geometry_ok(B, C, F, T, Fo, To, k, stride))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g: geometry not covered by the merged kernel (F=%d T=%d k=%d stride=%d)", F, T, k, stride);
-  if (gpart && inner_cap < eat_dw_bwd_partials_inner(F, T, Fo, To, k, stride))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g: partial buffer too small (inner_cap %d)", inner_cap);
-  const eat::DwBnBwd bn{z, bn_a, bn_b, bn_mean, bn_invstd, gscale, gadd, sums, bn_act, frozen};
-  const int rc = eat::dw_bwd_try(dy, x, in_a, in_b, in_act, w, g, dw, gpart, h_inner, B, C, F, T, Fo, To, k, stride,
-                                 (hipStream_t)stream, &bn);
-  if (rc == 1) return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g: merged kernel unavailable");
-  return rc;
-}
-
-// The same over bf16-stored dy, z, x and g (act_io.h; the bf16-storage plan of BASELINE configs[2]): every wide tensor the
-// backward of a block touches is 16-bit in HBM (x_b16 = 0: x and g are fp32 - the first block, whose conv input is the stem
-// output); coefficients, channel sums, taps, dw and the partial sums (taken of the g values as stored) are fp32 / fp64.
-extern "C" int eat_dw_conv_bwd_bn_g_b16(const void* dy, const void* z, const float* bn_a, const float* bn_b,
-                                        const float* bn_mean, const float* bn_invstd, const float* gscale, const float* gadd,
-                                        const double* sums, int bn_act, int frozen, const void* x, int x_b16, const float* in_a,
-                                        const float* in_b, int in_act, const float* w, void* g, float* dw, float* gpart,
-                                        int inner_cap, int* h_inner, int B, int C, int F, int T, int Fo, int To, int k,
-                                        int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!dy || !z || !bn_a || !bn_b || !bn_mean || !bn_invstd || !sums || !x || !in_a || !in_b || !w || !g || !dw)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g_b16: missing operand");
-  if (in_act < 0 || in_act > 2 || bn_act < 0 || bn_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g_b16: bad act");
-  if (!dw_bwd_bn_geometry_ok(B, C, F, T, Fo, To, k, stride) || (F * T) % 2 != 0 || (Fo * To) % 2 != 0)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g_b16: geometry not covered by the merged kernel (F=%d T=%d k=%d stride=%d)", F, T, k, stride);
-  if (gpart && inner_cap < eat_dw_bwd_partials_inner(F, T, Fo, To, k, stride))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g_b16: partial buffer too small (inner_cap %d)", inner_cap);
-  const eat::DwBnBwd bn{reinterpret_cast<const float*>(z), bn_a, bn_b, bn_mean, bn_invstd, gscale, gadd, sums, bn_act, frozen};
-  const int rc = eat::dw_bwd_try(reinterpret_cast<const float*>(dy), reinterpret_cast<const float*>(x), in_a, in_b, in_act, w,
-                                 reinterpret_cast<float*>(g), dw, gpart, h_inner, B, C, F, T, Fo, To, k, stride,
-                                 (hipStream_t)stream, &bn, 0, nullptr, nullptr, x_b16 ? 1 : 2);
-  if (rc == 1) return eat::fail(EAT_EINVAL, "eat_dw_conv_bwd_bn_g_b16: merged kernel unavailable");
-  return rc;
-}
-
-// The same for DyMN's dynamic depthwise conv (per-(b,c) taps w_bc (B, C, k*k), models/dymn/dy_block.py:103-131 backward):
-// dw_bc (B, C, k*k) receives the per-plane tap gradients (zero-filled by the caller: planes of several tiles are added),
-// res (shape of g) or NULL is added to g after the partial sums are taken (the skip connection of a block without expand
-// conv), gzpart (layout of gpart) or NULL receives the per-tile sums of g * x (x raw): with gpart the two sums the
-// BatchNorm backward of the expand conv needs - no reduce pass over (g, x).
-extern "C" int eat_dw_conv_dyn_bwd_bn_g(const float* dy, const float* z, const float* bn_a, const float* bn_b,
-                                        const float* bn_mean, const float* bn_invstd, const double* sums, int bn_act,
-                                        int frozen, const float* x, const float* in_a, const float* in_b, int in_act,
-                                        const float* w_bc, const float* res, float* g, float* dw_bc, float* gpart,
-                                        float* gzpart, int inner_cap, int* h_inner, int B, int C, int F, int T, int Fo,
-                                        int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!dy || !z || !bn_a || !bn_b || !bn_mean || !bn_invstd || !sums || !in_a || !in_b || !w_bc || !g || !dw_bc)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g: missing operand");
-  if (in_act < 0 || in_act > 2 || bn_act < 0 || bn_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g: bad act");
-  if (!dw_bwd_bn_geometry_ok(B, C, F, T, Fo, To, k, stride))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g: geometry not covered by the merged kernel (F=%d T=%d k=%d stride=%d)", F, T, k, stride);
-  if ((gpart || gzpart) && inner_cap < eat_dw_bwd_partials_inner(F, T, Fo, To, k, stride))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g: partial buffer too small (inner_cap %d)", inner_cap);
-  const eat::DwBnBwd bn{z, bn_a, bn_b, bn_mean, bn_invstd, nullptr, nullptr, sums, bn_act, frozen};
-  const int rc = eat::dw_bwd_try(dy, x, in_a, in_b, in_act, w_bc, g, dw_bc, gpart, h_inner, B, C, F, T, Fo, To, k, stride,
-                                 (hipStream_t)stream, &bn, 1, res, gzpart);
-  if (rc == 1) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g: merged kernel unavailable");
-  return rc;
-}
-
-// ... over bf16-stored dy, z (and x, g when x_b16 != 0; x_b16 = 0: the block without expand conv - x is the fp32 block input, g
-// the fp32 input gradient, res its skip gradient): the DyMN blocks of the bf16-storage plan.  res needs x_b16 = 0.
-extern "C" int eat_dw_conv_dyn_bwd_bn_g_b16(const void* dy, const void* z, const float* bn_a, const float* bn_b,
-                                            const float* bn_mean, const float* bn_invstd, const double* sums, int bn_act,
-                                            int frozen, const void* x, int x_b16, const float* in_a, const float* in_b, int in_act,
-                                            const float* w_bc, const float* res, void* g, float* dw_bc, float* gpart,
-                                            float* gzpart, int inner_cap, int* h_inner, int B, int C, int F, int T, int Fo,
-                                            int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (!dy || !z || !bn_a || !bn_b || !bn_mean || !bn_invstd || !sums || !x || !in_a || !in_b || !w_bc || !g || !dw_bc)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g_b16: missing operand");
-  if (in_act < 0 || in_act > 2 || bn_act < 0 || bn_act > 2) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g_b16: bad act");
-  if (res && x_b16) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g_b16: the skip gradient goes with an fp32 g (x_b16 = 0)");
-  if (!dw_bwd_bn_geometry_ok(B, C, F, T, Fo, To, k, stride) || (F * T) % 2 != 0 || (Fo * To) % 2 != 0)
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g_b16: geometry not covered by the merged kernel (F=%d T=%d k=%d stride=%d)", F, T, k, stride);
-  if ((gpart || gzpart) && inner_cap < eat_dw_bwd_partials_inner(F, T, Fo, To, k, stride))
-    return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g_b16: partial buffer too small (inner_cap %d)", inner_cap);
-  const eat::DwBnBwd bn{reinterpret_cast<const float*>(z), bn_a, bn_b, bn_mean, bn_invstd, nullptr, nullptr, sums, bn_act, frozen};
-  const int rc = eat::dw_bwd_try(reinterpret_cast<const float*>(dy), reinterpret_cast<const float*>(x), in_a, in_b, in_act, w_bc,
-                                 reinterpret_cast<float*>(g), dw_bc, gpart, h_inner, B, C, F, T, Fo, To, k, stride,
-                                 (hipStream_t)stream, &bn, 1, res, gzpart, x_b16 ? 1 : 2);
-  if (rc == 1) return eat::fail(EAT_EINVAL, "eat_dw_conv_dyn_bwd_bn_g_b16: no instance for F=%d T=%d k=%d stride=%d x_b16=%d", F, T, k, stride, x_b16);
-  return rc;
-}
-
-extern "C" int eat_dw_conv_dyn_wgrad(const float* dz, const float* x, float* dw_bc, int B, int C, int F, int T, int Fo,
-                                     int To, int k, int stride, eat_stream_t stream) {
-  eat::clear_stale_error();
-  return dw_wgrad_impl(dz, x, dw_bc, B, C, C, F, T, Fo, To, k, stride, 1, stream);
-}
 
 // Launch plan of the 1x1 weight gradient: which kernel, how the k range is cut (also exported through
 // eat_pw_wgrad_slots so that a caller can size a one-slot-per-block workspace)

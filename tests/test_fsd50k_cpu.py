@@ -1,7 +1,6 @@
 """CPU checks of FSD50K fine-tuning: the host draws against a transcription of the reference's call sequence, the float64
 reference of tests/fsd50k_ref.py against the reference's own float32 transforms, the draw validation, the ragged bank reader,
 the program's defaults and the new library symbol."""
-import ctypes
 import importlib.util
 import io
 import os
@@ -259,11 +258,9 @@ def test_program_defaults_are_ex_fsd50ks():
 
 
 def test_library_exports_the_ragged_symbol():
+    """(that the library exports what the header declares: tests/test_host_cpu.py, which names this symbol)"""
     from efficientat_amd import build
     assert "eat_wave_augment_ragged" in _lib.exported_symbols()
-    header = open(os.path.join(ROOT, "include", "eat_hip.h")).read()
-    h = ctypes.CDLL(build.build())
-    assert "eat_wave_augment_ragged(" in header and hasattr(h, "eat_wave_augment_ragged")
     assert "ragged.hip" in build.SOURCES
 
 

@@ -39,6 +39,47 @@ def test_library_exports_every_declared_symbol(libpath):
         assert hasattr(h, name), f"{name} declared in include/eat_hip.h but not exported"
     assert declared == set(_lib.exported_symbols())
     assert h.eat_version() >= 100
+    # the fine-tuning entry points (tests/test_openmic_cpu.py, tests/test_fsd50k_cpu.py) by name
+    assert {"eat_masked_bce_fwd_bwd", "eat_openmic_targets", "eat_rank_metrics_masked", "eat_wave_augment_ragged"} <= declared
+
+
+_VOCABULARY = {ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong}
+
+
+def test_ctypes_signatures_are_parsed_from_the_header(libpath):
+    """_lib has no signature table of its own: argtypes / restype of every symbol come from include/eat_hip.h."""
+    P, I, F, D, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
+    with open(os.path.join(ROOT, "include", "eat_hip.h")) as f:
+        protos = _lib.parse_prototypes(f.read())
+    assert len(protos) == 136 and protos == _lib.PROTOTYPES
+    assert _lib.SIGNATURES == {name: args for name, (_, args) in protos.items()}
+    for name, (restype, args) in protos.items():
+        assert set(args) <= _VOCABULARY and restype in (I, LL, ctypes.c_char_p), name
+    assert os.path.realpath(_lib.LIB_PATH) == os.path.realpath(libpath)
+    h = _lib.lib()
+    for name, (restype, args) in protos.items():
+        fn = getattr(h, name)
+        assert list(fn.argtypes) == args and fn.restype is restype, name
+    # order-sensitive literals, written from the header by hand: a parser that drops or swaps a parameter cannot agree
+    assert protos["eat_adam_multi"] == (I, [P, I, P, D, P, F, D, D, D, D, I, D, P])
+    assert protos["eat_wave_augment"] == (I, [P, P, P, LL, I, I, P, P, P, P, P, P, I, P])
+    assert protos["eat_rank_metrics_ws_bytes"] == (LL, [I, I])
+    assert protos["eat_last_error_string"] == (ctypes.c_char_p, [])
+    assert protos["eat_version"] == (I, []) and protos["eat_pw_stream_mode"] == (I, [I])
+
+
+@pytest.mark.parametrize("proto", [
+    "int eat_x(const float* a, unsigned n, eat_stream_t stream);",      # parameter type outside the vocabulary
+    "int eat_x(long n);",
+    "int eat_x(size_t n);",
+    "float eat_x(int n);",                                              # return type outside the vocabulary
+    "char* eat_x(void);",
+])
+def test_header_parser_refuses_a_type_outside_its_vocabulary(proto):
+    with pytest.raises(_lib.EatHipError, match="eat_x"):
+        _lib.parse_prototypes("/* a header */\n#define EAT_OK 0\nint eat_fine(int a, long long b, const char* c);\n" + proto)
+    assert _lib.parse_prototypes("int eat_fine(int a, long long, double* c);  // " + proto) == \
+        {"eat_fine": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p])}
 
 
 def test_mel_basis_is_bit_identical_to_oracle_and_banded():

@@ -1,6 +1,5 @@
 """CPU checks of OpenMIC fine-tuning: the float64 references of tests/openmic_ref.py against the reference's own torch
 expressions and sklearn, the host draws, the bank reader, the program's defaults and the new library symbols."""
-import ctypes
 import importlib.util
 import inspect
 import io
@@ -271,13 +270,9 @@ def test_program_defaults_are_ex_openmics():
 
 
 def test_library_exports_the_openmic_symbols():
-    from efficientat_amd import build, metrics
-    new = {"eat_masked_bce_fwd_bwd", "eat_openmic_targets", "eat_rank_metrics_masked"}
-    assert new <= set(_lib.exported_symbols())
-    header = open(os.path.join(ROOT, "include", "eat_hip.h")).read()
-    h = ctypes.CDLL(build.build())
-    for name in new:
-        assert f"{name}(" in header and hasattr(h, name)
+    """(that the library exports what the header declares: tests/test_host_cpu.py, which names these three)"""
+    from efficientat_amd import metrics
+    assert {"eat_masked_bce_fwd_bwd", "eat_openmic_targets", "eat_rank_metrics_masked"} <= set(_lib.exported_symbols())
     for fn in (metrics.ap_auc, metrics.average_precision, metrics.roc_auc):
         assert inspect.signature(fn).parameters["sample_weight"].default is None
 
