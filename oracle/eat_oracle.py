@@ -174,7 +174,8 @@ class emulate_bf16_pointwise:
     backward - the one arriving at the project conv's input and g = dL/d(BN output of the expand conv)."""
 
     def __init__(self, storage=False):
-        # storage: False, True (every block), or - DyMN - the collection of block indices that run on bf16 storage
+        # storage: False, True (every block), or the collection of block indices that run on bf16 storage (MN: indices into
+        # features[1:-1]; DyMN: into layers)
         self.storage = storage
 
     def __enter__(self):
@@ -234,12 +235,14 @@ def _concurrent_se(sd, prefix, x, se_dims, se_agg):
             "min": lambda t: t.min(dim=0)[0]}[se_agg](st)
 
 
-def _inverted_residual(sd, prefix, x, c, train, stats, use_se=True, se_dims=(1,), se_agg="max"):
-    """block_types.py:120-181: [expand] -> depthwise -> [SE] -> project (+ residual)."""
+def _inverted_residual(sd, prefix, x, c, train, stats, use_se=True, se_dims=(1,), se_agg="max", index=None):
+    """block_types.py:120-181: [expand] -> depthwise -> [SE] -> project (+ residual).  index: the block's position in
+    `features[1:-1]` for the bf16-storage emulation of a per-block plan (`_st16`); None: any truthy ST_BF16 stores the block."""
     inp, j = x, 0
     a = "hs" if c["hs"] else "re"
     dil = c.get("dil", 1)
-    st16 = ST_BF16 and train       # (a block without expand conv: z_d, y_d and the project conv's data gradient only)
+    # (a block without expand conv: z_d, y_d and the project conv's data gradient only)
+    st16 = bool(train and (ST_BF16 if index is None else _st16(index)))
     if c["cexp"] != c["cin"]:
         x = _cna(sd, f"{prefix}.block.{j}", x, train, stats, 1, 1, 1, a, store="expand" if st16 else None)
         j += 1
@@ -300,7 +303,7 @@ def mn_forward(sd, x, width_mult=1.0, strides=(2, 2, 2, 2), train=False, stats=N
     x = _cna(sd, "features.0", x, train, stats, 3, 2, 1, "hs")
     fmaps.append(x)
     for i, c in enumerate(blocks):
-        x = _inverted_residual(sd, f"features.{i + 1}", x, c, train, stats, se_dims=se_dims, se_agg=se_agg)
+        x = _inverted_residual(sd, f"features.{i + 1}", x, c, train, stats, se_dims=se_dims, se_agg=se_agg, index=i)
         fmaps.append(x)
     x = _cna(sd, "features.16", x, train, stats, 1, 1, 1, "hs")
     fmaps.append(x)
@@ -340,7 +343,7 @@ class _DynPwBf16(torch.autograd.Function):
 
 
 def _st16(i):
-    """bf16-storage emulation of dynamic block i: ST_BF16 is True (every block) or the collection of the block indices that
+    """bf16-storage emulation of block i: ST_BF16 is True (every block) or the collection of the block indices that
     run on bf16 storage (the HIP plan keeps fp32 storage for geometries its kernels do not cover)."""
     return ST_BF16 is True or (ST_BF16 is not False and ST_BF16 is not None and i in ST_BF16)
 
