@@ -22,7 +22,10 @@ namespace {
 // fp32 products and accumulation - round 5; the round-3 form multiplied on the vector ALUs, 4 outputs per thread, which at
 // mn40's widths - 3840 x 960 gates, a 3840 -> 5120 -> 527 head - ran at 14 TFLOP/s: 2.1 + 0.65 ms of a 46 ms step).  The k
 // axis goes through LDS in chunks of 64 (one LDS stage of 2 x 64 x 33 floats SHARED by the tile functions of a kernel:
-// 16.9 KB per block, 8 waves per SIMD.  History, same-box microbenchmarks at mn40's head 3840 -> 5120 -> 527, B = 128:
+// 16.9 KB per block; 8 waves per SIMD until round 7 - the four-chunk register ring below takes the kernels to 124 - 144
+// VGPRs, 3 waves per SIMD, no scratch: the grids of the step are 1 - 5 blocks per CU, so the LDS stage was never what
+// filled a CU; at mn40's widths the occupancy was measured through the whole-leg time only
+// (profiles/small_kernels_before_after.md).  History, same-box microbenchmarks at mn40's head 3840 -> 5120 -> 527, B = 128:
 // chunks of 128 with one pair of arrays PER INSTANTIATION of this template - 68.6 KB, two blocks per CU - 442 us; one shared
 // stage 257 us; chunks of 64 236 us.  Chunks of 32 at two blocks per CU had left the kernel waiting on one memory latency
 // per 32 k: 55 us for K = 960.)
@@ -35,8 +38,24 @@ __device__ __forceinline__ tile_lds_t* tile_lds() {
   __shared__ float s_tiles[2][kKC][33];
   return s_tiles;
 }
+// Operand loads (round 7).  The loaders return RAW values (a float, or dq_raw for the gate's ds * s * (1 - s)) from an
+// address clamped into the operand - an unconditional load, so the 16 loads per thread and chunk issue back to back (as
+// `in range ? load : 0` each load sat in its own exec-masked branch and waited for the one before: a chunk cost 16
+// dependent memory latencies).  fin() turns a raw value into the operand at LDS-store time, so that nothing between the
+// issue of a chunk's loads and its turn in the ring waits for them.
+struct dq_raw { float d, s; };
+__device__ __forceinline__ float fin(float v) { return v; }
+__device__ __forceinline__ float fin(dq_raw r) { return r.d * r.s * (1.0f - r.s); }
+__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+
+// chunks in flight: the loads of the first kNS chunks of a tile's k range are issued before the first wait (K <= 256 - every
+// contraction over the batch and every k slice - is all of them: one memory latency per tile); on a longer range chunk
+// c + kNS is fetched into the registers of chunk c as soon as chunk c sits in LDS.
+constexpr int kNS = 4;
+
 template <bool A_MFAST, class FA, class FB, class FS>
-__device__ __forceinline__ void gemm_tile(int M, int N, int K, int m0, int n0, FA a_at, FB b_at, FS store, int k_lo = 0) {
+__device__ __forceinline__ void gemm_tile(int M, int N, int K, int m0, int n0, FA a_at, FB b_at, FS store, int k_lo = 0,
+                                          float b_scale = 1.0f) {
   tile_lds_t* const lds = tile_lds();
   tile_lds_t& sA = lds[0];                           // sA[k][m]
   tile_lds_t& sB = lds[1];                           // sB[k][n]
@@ -45,36 +64,63 @@ __device__ __forceinline__ void gemm_tile(int M, int N, int K, int m0, int n0, F
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int l15 = lane & 15, kq = lane >> 4;
   const int ms = 16 * (wv >> 1), ns = 16 * (wv & 1);                 // this wave's quadrant of the tile
+  constexpr int NI = kKC / 8, KQ = kKC / 32;            // loads per thread and operand; 32-wide k groups of a chunk
+  using RA = decltype(a_at(0, 0));
+  using RB = decltype(b_at(0, 0));
+  RA av[kNS][NI];
+  RB bv[kNS][NI];
+  // A: fast index tx, slow index ty + 8 i over (m: 32) x (k: kKC); B: (k: ty + 8 i, n: tx)
+  auto a_pos = [&](int i, int& mm, int& kk) {
+    if (A_MFAST) { mm = tx; kk = ty + 8 * i; }
+    else { kk = tx + 32 * (i % KQ); mm = ty + 8 * (i / KQ); }
+  };
+  auto fetch = [&](int k0, RA (&a)[NI], RB (&b)[NI]) {
+    const int nb = imin(n0 + tx, N - 1);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      int mm, kk;
+      a_pos(i, mm, kk);
+      a[i] = a_at(imin(m0 + mm, M - 1), imin(k0 + kk, K - 1));
+      b[i] = b_at(imin(k0 + ty + 8 * i, K - 1), nb);
+    }
+  };
+  const int n_chunks = (K - k_lo + kKC - 1) / kKC;
+#pragma unroll
+  for (int s = 0; s < kNS; ++s)
+    if (s < n_chunks) fetch(k_lo + s * kKC, av[s], bv[s]);
   f32x4 acc{0.f, 0.f, 0.f, 0.f};
-  for (int k0 = k_lo; k0 < K; k0 += kKC) {
-    constexpr int NI = kKC / 8, KQ = kKC / 32;          // loads per thread and operand; 32-wide k groups of a chunk
-    float av[NI], bv[NI];
+  for (int cb = 0; cb < n_chunks; cb += kNS) {
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      // A: fast index tx, slow index ty + 8 i over (m: 32) x (k: kKC)
-      int mm, kk;
-      if (A_MFAST) { mm = tx; kk = ty + 8 * i; }
-      else { kk = tx + 32 * (i % KQ); mm = ty + 8 * (i / KQ); }
-      av[i] = (m0 + mm < M && k0 + kk < K) ? a_at(m0 + mm, k0 + kk) : 0.0f;
-      const int kb = ty + 8 * i;
-      bv[i] = (k0 + kb < K && n0 + tx < N) ? b_at(k0 + kb, n0 + tx) : 0.0f;
-    }
+    for (int s = 0; s < kNS; ++s) {
+      if (cb + s < n_chunks) {                          // (block-uniform)
+        const int k0 = k_lo + (cb + s) * kKC;
 #pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      int mm, kk;
-      if (A_MFAST) { mm = tx; kk = ty + 8 * i; }
-      else { kk = tx + 32 * (i % KQ); mm = ty + 8 * (i / KQ); }
-      sA[kk][mm] = av[i];
-      sB[ty + 8 * i][tx] = bv[i];
+        for (int i = 0; i < NI; ++i) {
+          int mm, kk;
+          a_pos(i, mm, kk);
+          sA[kk][mm] = (m0 + mm < M && k0 + kk < K) ? fin(av[s][i]) : 0.0f;
+          const int kb = ty + 8 * i;
+          sB[kb][tx] = (k0 + kb < K && n0 + tx < N) ? fin(bv[s][i]) * b_scale : 0.0f;
+        }
+        // (the slot's registers are free once its LDS stores are issued: the refetch runs under this chunk's MFMAs too)
+        if (cb + s + kNS < n_chunks) fetch(k0 + kNS * kKC, av[s], bv[s]);
+        __syncthreads();
+        // rows of the chunk beyond K were stored as zeros: whole 4-k steps
+        const int kn = (K - k0) < kKC ? ((K - k0 + 3) & ~3) : kKC;
+        // A operand: lane (m = l15, k = kq); B operand: lane (k = kq, n = l15); D: lane holds rows 4 kq + r of column l15
+        // (a full chunk as straight-line code: its 32 LDS reads are issued ahead of the 16 MFMAs.  As a loop - the compiler
+        //  does not unroll one with this trip count - every MFMA waited for its own pair of reads: ~1 us per chunk)
+        if (kn == kKC) {
+#pragma unroll
+          for (int kk = 0; kk < kKC; kk += 4)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sA[kk + kq][ms + l15], sB[kk + kq][ns + l15], acc, 0, 0, 0);
+        } else {
+          for (int kk = 0; kk < kn; kk += 4)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sA[kk + kq][ms + l15], sB[kk + kq][ns + l15], acc, 0, 0, 0);
+        }
+        __syncthreads();
+      }
     }
-    __syncthreads();
-    // rows of the chunk beyond K were stored as zeros: whole 4-k steps
-    const int kn = (K - k0) < kKC ? ((K - k0 + 3) & ~3) : kKC;
-    // A operand: lane (m = l15, k = kq); B operand: lane (k = kq, n = l15); D: lane holds rows 4 kq + r of column l15
-#pragma unroll 4
-    for (int kk = 0; kk < kn; kk += 4)
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sA[kk + kq][ms + l15], sB[kk + kq][ns + l15], acc, 0, 0, 0);
-    __syncthreads();
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -83,14 +129,23 @@ __device__ __forceinline__ void gemm_tile(int M, int N, int K, int m0, int n0, F
   }
 }
 
-// column sums out[n] = sum_m f(m, n) for 32 columns per block: 8 row groups x 32 columns, LDS reduction
+// column sums out[n] = sum_m f(m, n) for 32 columns per block: 8 row groups x 32 columns, LDS reduction.  A row group
+// loads 16 of its rows at a time (clamped addresses: unconditional, back to back) and adds them in row order.
 template <class F>
 __device__ __forceinline__ void col_sum_tile(int M, int N, int n0, F f, float* __restrict__ out) {
   tile_lds_t& s_cs = tile_lds()[0];                  // (8 rows of it)
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  constexpr int U = 16;
+  const int nn = imin(n0 + tx, N - 1);
   float s = 0.0f;
-  if (n0 + tx < N)
-    for (int m = ty; m < M; m += 8) s += f(m, n0 + tx);
+  for (int mb = ty; mb < M; mb += 8 * U) {
+    decltype(f(0, 0)) v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = f(imin(mb + 8 * u, M - 1), nn);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (mb + 8 * u < M) s += fin(v[u]);
+  }
   s_cs[ty][tx] = s;
   __syncthreads();
   if (ty == 0 && n0 + tx < N) {
@@ -108,7 +163,10 @@ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 // one slice of k, the slices are stored side by side ([slice][M][N]) and added in index order by slice_sum_kernel - no
 // atomics, bit-reproducible.  Slices of 256 from K = 512 (same-box: slices of 512 from K = 1024 left mn10's 960 -> 240 gate at
 // 55 us, now 33 us; mn40's 3840 -> 960 gate 120 -> 112 us); one slice (no extra launch) below.
-__host__ __device__ __forceinline__ int k_slices(int K) { return K >= 512 ? (K + 255) / 256 : 1; }
+// Round 7: the cut moved from 512 to above 1024 - with kNS chunks of loads in flight mn10's gates (C <= 960) run their
+// contraction in one block and two launches; the head's H = 1280 measured slower unsplit (stage 2: 27 -> 41 us, 240 blocks
+// of 20 chunks against 1200 of 4) and keeps its slices, as do mn40's 3840 / 5120.
+__host__ __device__ __forceinline__ int k_slices(int K) { return K > 1024 ? (K + 255) / 256 : 1; }
 __host__ __device__ __forceinline__ int k_slice_len(int K) { const int n = k_slices(K); return ((K + n - 1) / n + 3) & ~3; }
 
 // out[i] = (gate == NULL || gate[i] > 0) * sum over slices of part[s][i]
@@ -126,7 +184,7 @@ __global__ __launch_bounds__(256) void se_bwd_stage1_kernel(const float* __restr
                                                             const float* __restrict__ h, const float* __restrict__ W2,
                                                             float* __restrict__ dW2, float* __restrict__ db2,
                                                             float* __restrict__ dh, int B, int C, int Cr) {
-  auto dq = [&](int b, int c) { const float s = sc[(size_t)b * C + c]; return ds[(size_t)b * C + c] * s * (1.0f - s); };
+  auto dq = [&](int b, int c) { return dq_raw{ds[(size_t)b * C + c], sc[(size_t)b * C + c]}; };     // fin(): d s (1 - s)
   const int tA_n = cdiv(Cr, 32), nA = cdiv(C, 32) * tA_n;
   const int ks = k_slices(C), kl = k_slice_len(C);
   const int tB_n = cdiv(Cr, 32), nB1 = cdiv(B, 32) * tB_n, nB = nB1 * ks;
@@ -163,8 +221,8 @@ __global__ __launch_bounds__(256) void se_bwd_stage2_kernel(const float* __restr
   int id = blockIdx.x;
   if (id < nC) {                      // dW1 (Cr x C): A(m = r, k = b) = dh[b, r], B(k = b, n = c) = pool[b, c] / S
     gemm_tile<true>(Cr, C, B, (id / tC_n) * 32, (id % tC_n) * 32, [&](int m, int k) { return dh[(size_t)k * Cr + m]; },
-                    [&](int k, int n) { return pool[(size_t)k * C + n] * inv_s; },
-                    [&](int m, int n, float v) { dW1[(size_t)m * C + n] = v; });
+                    [&](int k, int n) { return pool[(size_t)k * C + n]; },
+                    [&](int m, int n, float v) { dW1[(size_t)m * C + n] = v; }, 0, inv_s);
     return;
   }
   id -= nC;

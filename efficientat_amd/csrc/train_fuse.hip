@@ -473,19 +473,26 @@ __device__ __forceinline__ void wcat_store(void* __restrict__ wp, int MT, int i,
 
 using wc_f32x4 = __attribute__((ext_vector_type(4))) float;
 
-template <int KIND>
-__global__ __launch_bounds__(256) void expand_bwd_wcat_kernel(const float* __restrict__ W, const float* __restrict__ a,
-                                                              const float* __restrict__ e2, const float* __restrict__ e1,
-                                                              int Co, int Ci, int MT, int Kpad, void* __restrict__ wp,
-                                                              float* __restrict__ c0) {
-  __shared__ float s_acc[3][4][64];
-  __shared__ float s_c0[16][16];
+// Round 7: 16 waves per M tile (before: 4).  The waves split the Co / 4 k-steps, each has at most 16 of them and loads them
+// all before its first MFMA (Co = 960: 15 steps per wave, ONE round of loads - before 60 steps per wave in rounds of 8); the
+// 16 partial tiles are added through LDS in wave order.  c0's column walk is spread over 4 row groups per wave the same way.
+// WAVES = 4 where that already gives one round (Co <= 256: at most 16 steps per wave) - 16 waves there only added twelve
+// empty partial tiles to the combine (smallest layer 4.7 -> 6.1 us).
+__host__ __device__ constexpr int wcat_waves(int Co) { return Co <= 256 ? 4 : 16; }
+template <int KIND, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void expand_bwd_wcat_kernel(const float* __restrict__ W, const float* __restrict__ a,
+                                                                        const float* __restrict__ e2, const float* __restrict__ e1,
+                                                                        int Co, int Ci, int MT, int Kpad, void* __restrict__ wp,
+                                                                        float* __restrict__ c0) {
+  constexpr int kThreads = 64 * WAVES, kRG = 4 * WAVES;                 // kRG: c0's row groups of 16 lanes
+  __shared__ float s_acc[WAVES - 1][4][64];
+  __shared__ float s_c0[kRG][16];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int n_tiles = MT * MT;
   if ((int)blockIdx.x >= n_tiles) {
     // ---- elementwise part: WaT and the zero padding of the k axis
     const int I16 = MT * 16;
-    const long long e = (long long)(blockIdx.x - n_tiles) * 256 + tid;
+    const long long e = (long long)(blockIdx.x - n_tiles) * kThreads + tid;
     const int kidx = (int)(e / I16), i = (int)(e - (long long)kidx * I16);
     const int n_k = Co + (Kpad - Co - Ci);
     if (kidx >= n_k) return;
@@ -494,17 +501,17 @@ __global__ __launch_bounds__(256) void expand_bwd_wcat_kernel(const float* __res
     wcat_store<KIND>(wp, MT, i, k, v);
     return;
   }
-  // ---- one 16 x 16 tile of M: four waves split the reduction over the Co channels
+  // ---- one 16 x 16 tile of M: the waves split the reduction over the Co channels
   const int it = blockIdx.x / MT, jt = blockIdx.x - it * MT;
   const int i = it * 16 + (lane & 15), j = jt * 16 + (lane & 15), kq = lane >> 4;
   const bool iv = i < Ci, jv = j < Ci;
-  const int steps = (Co + 3) / 4, per = (steps + 3) / 4;
+  const int steps = (Co + 3) / 4, per = (steps + WAVES - 1) / WAVES;
   const int s0 = wv * per, s1 = (s0 + per) < steps ? (s0 + per) : steps;
   wc_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int sb = s0; sb < s1; sb += 8) {                                   // 8 k-steps of loads in flight per round
-    float av[8], bv[8];
+  for (int sb = s0; sb < s1; sb += 16) {                                  // 16 k-steps of loads in flight per round
+    float av[16], bv[16];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
+    for (int u = 0; u < 16; ++u) {
       const int c = (sb + u) * 4 + kq;
       const bool ok = (sb + u) < s1 && c < Co;
       const int cc = ok ? c : 0;
@@ -513,32 +520,45 @@ __global__ __launch_bounds__(256) void expand_bwd_wcat_kernel(const float* __res
       bv[u] = (ok && jv) ? wj : 0.0f;
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
+    for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
   }
   if (wv > 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) s_acc[wv - 1][r][lane] = acc[r];
   }
-  // c0 of this row tile (first column tile only): 16 row groups x 16 columns
-  float pc = 0.0f;
+  // c0 of this row tile (first column tile only): kRG row groups x 16 columns, 16 rows in flight per group
   if (jt == 0) {
     const int ci = it * 16 + (tid & 15), rg = tid >> 4;
-    if (ci < Ci)
-      for (int c = rg; c < Co; c += 16) pc = fmaf(e1[c], W[(size_t)c * Ci + ci], pc);
+    const int cic = ci < Ci ? ci : Ci - 1;
+    float pc = 0.0f;
+    for (int cb = rg; cb < Co; cb += kRG * 16) {
+      float ev[16], wvv[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int c = cb + kRG * u, cc = c < Co ? c : Co - 1;
+        ev[u] = e1[cc];
+        wvv[u] = W[(size_t)cc * Ci + cic];
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (cb + kRG * u < Co) pc = fmaf(ev[u], wvv[u], pc);
+    }
     s_c0[rg][tid & 15] = pc;
   }
   __syncthreads();
   if (jt == 0 && tid < 16) {
     float t = 0.0f;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) t += s_c0[r][tid];
+    for (int r = 0; r < kRG; ++r) t += s_c0[r][tid];
     if (it * 16 + tid < Ci) c0[it * 16 + tid] = t;
   }
   if (wv != 0) return;
   // C / D layout of the MFMA: lane (kq, n) holds rows 4 kq + r of column n
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float v = acc[r] + s_acc[0][r][lane] + s_acc[1][r][lane] + s_acc[2][r][lane];
+    float v = acc[r];
+#pragma unroll
+    for (int w = 0; w < WAVES - 1; ++w) v += s_acc[w][r][lane];
     const int mi = it * 16 + kq * 4 + r, mj = jt * 16 + (lane & 15);
     if (mj < Ci) wcat_store<KIND>(wp, MT, mi, Co + mj, (mi < Ci) ? -v : 0.0f);
   }
@@ -759,10 +779,18 @@ extern "C" int eat_expand_bwd_wcat(const float* W, const float* a, const float* 
   const int MT = (Ci + 15) / 16;
   const int Kpad = kind == 0 ? Co + Ci : ((Co + Ci + 31) / 32) * 32;
   const long long ew = (long long)MT * 16 * (Co + (Kpad - Co - Ci));
-  const unsigned grid = (unsigned)(MT * MT + (ew + 255) / 256);
+  const int threads = 64 * wcat_waves(Co);
+  const dim3 grid((unsigned)(MT * MT + (ew + threads - 1) / threads)), block((unsigned)threads);
   hipStream_t s = (hipStream_t)stream;
-  if (kind == 0) hipLaunchKernelGGL(expand_bwd_wcat_kernel<0>, dim3(grid), dim3(256), 0, s, W, a, e2, e1, Co, Ci, MT, Kpad, wp, c0);
-  else if (kind == 1) hipLaunchKernelGGL(expand_bwd_wcat_kernel<1>, dim3(grid), dim3(256), 0, s, W, a, e2, e1, Co, Ci, MT, Kpad, wp, c0);
-  else hipLaunchKernelGGL(expand_bwd_wcat_kernel<2>, dim3(grid), dim3(256), 0, s, W, a, e2, e1, Co, Ci, MT, Kpad, wp, c0);
+  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, W, a, e2, e1, Co, Ci, MT, Kpad, wp, c0); };
+  if (threads == 256) {
+    if (kind == 0) launch(expand_bwd_wcat_kernel<0, 4>);
+    else if (kind == 1) launch(expand_bwd_wcat_kernel<1, 4>);
+    else launch(expand_bwd_wcat_kernel<2, 4>);
+  } else {
+    if (kind == 0) launch(expand_bwd_wcat_kernel<0, 16>);
+    else if (kind == 1) launch(expand_bwd_wcat_kernel<1, 16>);
+    else launch(expand_bwd_wcat_kernel<2, 16>);
+  }
   return eat::check_launch("eat_expand_bwd_wcat");
 }
