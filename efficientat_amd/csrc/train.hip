@@ -684,12 +684,18 @@ __global__ __launch_bounds__(512) void pw_wgrad_wide_kernel(const float* __restr
     }
 }
 
+// units of one wave in registers (one being multiplied, the others in flight) for a block tile of `tiles` operand row
+// tiles (8 VGPRs of raw data each), as measured at B = 256 (profiles/thin_wgrad_before_after.md): a third unit pays on
+// the five-tile blocks (64 x 16 @ 32000: 446 vs 460 us), deeper rings cost the small blocks their occupancy (1024 blocks
+// want four resident per CU) and gained nothing; seven tiles hold two units in 256 VGPRs (two blocks per CU, no scratch)
+constexpr int narrow_ring(int tiles) { return tiles <= 1 ? 4 : tiles == 5 ? 3 : 2; }
+
 // Narrow layers (one side <= 16 channels, the other <= 64: mn10 block 1 and the expand of block 2, planes of 32000
 // positions): dW is a single 64 x 64 wave tile and the gradient is a pure streaming reduction over k.  Here the direct,
 // LDS-free form wins: the 4 waves of a block split the k range, every lane loads the 8 consecutive k of its row straight
-// from HBM (one full 128-byte line per row and unit).  Round 3: the tile counts are compile-time (a 16 x 16 product keeps
-// 8, not 128, operand registers), the loads of the NEXT unit are issued before the MFMAs of the current one (the loop
-// was latency-bound: 1.7 TB/s on the 16 x 16 layers), and SAME (dz == x: the Gram matrix of train_fuse.hip) loads once.
+// from HBM (one full 128-byte line per row and unit).  The tile counts are compile-time (a 16 x 16 product keeps 8, not
+// 128, operand registers), the raw rows of the next 1 - 3 units are in flight behind the MFMAs of the current one, and
+// SAME (dz == x: the Gram matrix of train_fuse.hip) loads once.
 template <int MTN, int NTN, bool SAME>
 __global__ __launch_bounds__(256, 2) void pw_wgrad_x3_narrow_kernel(const float* __restrict__ dz, const float* __restrict__ x,
                                                                     const float* __restrict__ xscale, float* __restrict__ dW,
@@ -720,79 +726,95 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_x3_narrow_kernel(const float*
   for (int i = 0; i < MTN; ++i)
 #pragma unroll
     for (int j = 0; j < NTN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float sc[NTN], tfa[NTN], tfb[NTN], actr[MTN];
+  // No load of this kernel depends on a per-lane condition: rows and positions are clamped to valid addresses and what
+  // lies outside the matrix / plane is zeroed by a select at conversion time.  A load inside a conditional block
+  // (`ok ? load : 0`) makes the compiler's wait-count pass fall back to vmcnt(0) at its use, which drains every unit in flight.
+  const float* tfa_p = tf.a ? tf.a : x;                         // (x holds >= Ci, dz >= Co floats: stand-ins, selected away)
+  const float* tfb_p = tf.a ? tf.b : x;
+  const float* actr_p = tf.actr ? tf.actr : dz;
+  const float* sc_p = xscale ? xscale : x;
+  float tfa[NTN], tfb[NTN], actr[MTN];
+  size_t xoff[SAME ? 1 : NTN], zoff[MTN];                       // clamped row * S
+  int xrow[SAME ? 1 : NTN];
+  bool xok[NTN], zok[MTN];
 #pragma unroll
   for (int j = 0; j < NTN; ++j) {
-    sc[j] = 1.0f;
-    const int row = n0 + 16 * j + r;
-    tfa[j] = (tf.a && row < Ci) ? tf.a[row] : 1.0f;
-    tfb[j] = (tf.a && row < Ci) ? tf.b[row] : 0.0f;
+    const int row = n0 + 16 * j + r, rc = row < Ci ? row : Ci - 1;
+    xok[j] = row < Ci;
+    if constexpr (!SAME) { xrow[j] = rc; xoff[j] = (size_t)rc * S; }
+    const float ta = tfa_p[rc], tb = tfb_p[rc];
+    tfa[j] = (tf.a && row < Ci) ? ta : 1.0f;
+    tfb[j] = (tf.a && row < Ci) ? tb : 0.0f;
   }
 #pragma unroll
   for (int i = 0; i < MTN; ++i) {
-    const int row = m0 + 16 * i + r;
-    actr[i] = (tf.actr && row < Co) ? tf.actr[row] : 0.0f;
+    const int row = m0 + 16 * i + r, rc = row < Co ? row : Co - 1;
+    zok[i] = row < Co;
+    zoff[i] = (size_t)rc * S;
+    const float tc = actr_p[rc];
+    actr[i] = (tf.actr && row < Co) ? tc : 0.0f;
   }
-  int b_sc = -1;
+  // (the coefficient loads must be back - and known to the compiler to be back - before the loop: a wait placed at their
+  //  first use inside it would be a full drain per step; the empty asm statements read the registers)
+#pragma unroll
+  for (int j = 0; j < NTN; ++j) asm volatile("" ::"v"(tfa[j]), "v"(tfb[j]));
+#pragma unroll
+  for (int i = 0; i < MTN; ++i) asm volatile("" ::"v"(actr[i]));
 
-  auto load = [&](int u, float (&av)[MTN][8], float (&bv)[SAME ? 1 : NTN][8]) {
-    const bool live = u < u1;                                   // wave-uniform
-    const int uu = live ? u : u0;
-    const int b = uu / sps, st = uu - b * sps;
+  // one unit of one wave: the raw 2 x 16 bytes per row tile, the SE scale of the unit's sample (requested with the unit,
+  // RING - 1 steps before its use) and the lane's first position
+  struct Unit { float4 a[MTN][2]; float4 b[SAME ? 1 : NTN][2]; float sc[SAME ? 1 : NTN]; int s; };
+  auto load = [&](int u, Unit& q) {
+    const int b = u / sps, st = u - b * sps;                    // (u < u1, wave-uniform)
     const int s = st * 32 + 8 * kg;
+    const int s0 = s < S - 4 ? s : S - 4, s1 = s + 4 < S - 4 ? s + 4 : S - 4;   // (S % 4 == 0, S >= 4)
+    q.s = s;
+    const float* zb = dz + (size_t)b * Co * S;
 #pragma unroll
     for (int i = 0; i < MTN; ++i) {
-      const int row = m0 + 16 * i + r;
-      const float* p = dz + ((size_t)b * Co + (row < Co ? row : Co - 1)) * S + s;
-      const bool ok0 = live && row < Co && s < S, ok1 = ok0 && s + 4 < S;
-      const float4 t0 = ok0 ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 t1 = ok1 ? *reinterpret_cast<const float4*>(p + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const float c0 = ok0 ? actr[i] : 0.0f, c1 = ok1 ? actr[i] : 0.0f;      // (0 without centring: elements unchanged)
-      av[i][0] = t0.x + c0; av[i][1] = t0.y + c0; av[i][2] = t0.z + c0; av[i][3] = t0.w + c0;
-      av[i][4] = t1.x + c1; av[i][5] = t1.y + c1; av[i][6] = t1.z + c1; av[i][7] = t1.w + c1;
+      q.a[i][0] = *reinterpret_cast<const float4*>(zb + zoff[i] + s0);
+      q.a[i][1] = *reinterpret_cast<const float4*>(zb + zoff[i] + s1);
     }
     if constexpr (!SAME) {
+      const float* xb = x + (size_t)b * Ci * S;
+      const float* sb = sc_p + (xscale ? (size_t)b * Ci : (size_t)0);
 #pragma unroll
       for (int j = 0; j < NTN; ++j) {
-        const int row = n0 + 16 * j + r;
-        const float* p = x + ((size_t)b * Ci + (row < Ci ? row : Ci - 1)) * S + s;
-        const bool ok0 = live && row < Ci && s < S, ok1 = ok0 && s + 4 < S;
-        const float4 t0 = ok0 ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 t1 = ok1 ? *reinterpret_cast<const float4*>(p + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        bv[j][0] = t0.x; bv[j][1] = t0.y; bv[j][2] = t0.z; bv[j][3] = t0.w;
-        bv[j][4] = t1.x; bv[j][5] = t1.y; bv[j][6] = t1.z; bv[j][7] = t1.w;
-        if (tf.a) {                                               // block-uniform; invalid elements stay 0
-#pragma unroll
-          for (int e = 0; e < 8; ++e) bv[j][e] = (e < 4 ? ok0 : ok1) ? wg_tf(bv[j][e], tfa[j], tfb[j], tf.act) : 0.0f;
-        }
+        q.b[j][0] = *reinterpret_cast<const float4*>(xb + xoff[j] + s0);
+        q.b[j][1] = *reinterpret_cast<const float4*>(xb + xoff[j] + s1);
+        q.sc[j] = sb[xrow[j]];
       }
     }
   };
-  auto compute = [&](int u, const float (&av)[MTN][8], const float (&bv)[SAME ? 1 : NTN][8]) {
-    if (u >= u1) return;                                        // wave-uniform
-    if (!SAME && xscale) {
-      const int b = u / sps;
-      if (b != b_sc) {
-#pragma unroll
-        for (int j = 0; j < NTN; ++j) {
-          const int row = n0 + 16 * j + r;
-          sc[j] = row < Ci ? xscale[(size_t)b * Ci + row] : 0.0f;
-        }
-        b_sc = b;
-      }
-    }
+  auto compute = [&](const Unit& q) {
+    const bool k0 = q.s < S, k1 = q.s + 4 < S;
     bf16x8_t ah[MTN], al[MTN];
 #pragma unroll
-    for (int i = 0; i < MTN; ++i) split8(av[i], ah[i], al[i]);
+    for (int i = 0; i < MTN; ++i) {
+      const bool ok0 = zok[i] && k0, ok1 = zok[i] && k1;
+      const float c0 = ok0 ? actr[i] : 0.0f, c1 = ok1 ? actr[i] : 0.0f;      // (0 without centring: elements unchanged)
+      const float4 t0 = q.a[i][0], t1 = q.a[i][1];
+      const float av[8] = {(ok0 ? t0.x : 0.0f) + c0, (ok0 ? t0.y : 0.0f) + c0, (ok0 ? t0.z : 0.0f) + c0, (ok0 ? t0.w : 0.0f) + c0,
+                           (ok1 ? t1.x : 0.0f) + c1, (ok1 ? t1.y : 0.0f) + c1, (ok1 ? t1.z : 0.0f) + c1, (ok1 ? t1.w : 0.0f) + c1};
+      split8(av, ah[i], al[i]);
+    }
 #pragma unroll
     for (int j = 0; j < NTN; ++j) {
       bf16x8_t bh, bl;
       if constexpr (SAME) {
         bh = ah[j]; bl = al[j];                                 // host: MTN == NTN
       } else {
-        float t[8];
+        const bool ok0 = xok[j] && k0, ok1 = xok[j] && k1;
+        const float4 t0 = q.b[j][0], t1 = q.b[j][1];
+        float t[8] = {ok0 ? t0.x : 0.0f, ok0 ? t0.y : 0.0f, ok0 ? t0.z : 0.0f, ok0 ? t0.w : 0.0f,
+                      ok1 ? t1.x : 0.0f, ok1 ? t1.y : 0.0f, ok1 ? t1.z : 0.0f, ok1 ? t1.w : 0.0f};
+        if (tf.a) {                                             // block-uniform; invalid elements stay 0
 #pragma unroll
-        for (int e = 0; e < 8; ++e) t[e] = bv[j][e] * sc[j];
+          for (int e = 0; e < 8; ++e) t[e] = (e < 4 ? ok0 : ok1) ? wg_tf(t[e], tfa[j], tfb[j], tf.act) : 0.0f;
+        }
+        const float scj = xscale ? (xok[j] ? q.sc[j] : 0.0f) : 1.0f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) t[e] *= scj;
         split8(t, bh, bl);
       }
 #pragma unroll
@@ -804,13 +826,29 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_x3_narrow_kernel(const float*
     }
   };
 
-  float a0[MTN][8], a1[MTN][8], b0[SAME ? 1 : NTN][8], b1[SAME ? 1 : NTN][8];
-  load(u0 + wv, a0, b0);
-  for (int u = u0 + wv; u < u1; u += 8) {
-    load(u + 4, a1, b1);
-    compute(u, a0, b0);
-    load(u + 8, a0, b0);
-    compute(u + 4, a1, b1);
+  // a ring of RING units per wave, RING - 1 of them in flight behind the one being multiplied; a wave still takes its
+  // units in the order u0 + wv, + 4, + 8, ... (the sum order of a block's tile does not depend on RING).  The main loop
+  // runs while all of its loads are inside the range: no condition around a load or a unit's MFMAs, counted waits.  The
+  // first RING - 1 requests and the last <= 2 RING - 2 units sit behind wave-uniform range checks instead of re-fetching
+  // a clamped unit: the 16-unit blocks of the 40-channel Gram launches are all head and tail, and fetching the last unit
+  // again for every slot past the range cost them 3 - 7 us of 37.
+  constexpr int RING = narrow_ring(MTN + (SAME ? 0 : NTN));
+  Unit ring[RING];
+  int u = u0 + wv;
+#pragma unroll
+  for (int k = 0; k + 1 < RING; ++k)
+    if (u + 4 * k < u1) load(u + 4 * k, ring[k]);
+  for (; u + 4 * (2 * RING - 2) < u1; u += 4 * RING) {
+#pragma unroll
+    for (int k = 0; k < RING; ++k) {
+      load(u + 4 * (k + RING - 1), ring[(k + RING - 1) % RING]);
+      compute(ring[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 2 * RING - 2; ++k) {
+    if (u + 4 * (k + RING - 1) < u1) load(u + 4 * (k + RING - 1), ring[(k + RING - 1) % RING]);
+    if (u + 4 * k < u1) compute(ring[k % RING]);
   }
   // the four waves add their tiles in a FIXED order (wave 0, 1, 2, 3): with one slot per block the result is then
   // bit-reproducible from run to run - needed for the Gram matrix, whose round-off reaches the BatchNorm statistics
@@ -886,14 +924,24 @@ __global__ __launch_bounds__(256) void wgrad_slot_reduce4_kernel(const float* __
   }
 }
 
+// (row tiles per block) pairs the streaming kernel is instantiated for
+// (the x side carries the SE scale / BatchNorm transform and costs more registers per tile: <= 3 tiles there, <= 4 on the dz side)
+// plus 5 x 2 / 2 x 5: 72 x 24 and 24 x 72 as ONE row group (both operands read once, no zero tiles)
+constexpr bool thin_pair(int m, int n) {
+  return (m >= 1 && m <= 4 && n >= 1 && n <= 3) || (m == 5 && n == 2) || (m == 2 && n == 5);
+}
 template <int MTN, int NTN>
 static void launch_narrow(const float* dz, const float* x, const float* x_scale, float* dW, int B, int Co, int Ci, int S,
                           int sps, int upb, unsigned nz, int n_slots, hipStream_t s, WgTf tf, int mg, int ng, bool gram,
                           int ps_spl = 0) {
-  if (gram && MTN == NTN)
-    hipLaunchKernelGGL((pw_wgrad_x3_narrow_kernel<MTN, (MTN == NTN ? NTN : 1), (MTN == NTN)>), dim3(1, 1, nz), dim3(256), 0, s, dz,
-                       x, x_scale, dW, B, Co, Ci, S, sps, upb, n_slots, tf, 0);
-  else
+  if constexpr (MTN == NTN) {                                  // Gram matrix (dz == x, Co == Ci): the operand is loaded once
+    if (gram) {
+      hipLaunchKernelGGL((pw_wgrad_x3_narrow_kernel<MTN, NTN, true>), dim3(1, 1, nz), dim3(256), 0, s, dz, x, x_scale, dW, B,
+                         Co, Ci, S, sps, upb, n_slots, tf, 0);
+      return;
+    }
+  }
+  if constexpr (MTN * NTN < 16)                                // (4 x 4 exists in the Gram form only)
     hipLaunchKernelGGL((pw_wgrad_x3_narrow_kernel<MTN, NTN, false>), dim3(mg, ng, nz), dim3(256), 0, s, dz, x, x_scale, dW, B,
                        Co, Ci, S, sps, upb, n_slots, tf, ps_spl);
 }
@@ -907,9 +955,6 @@ struct WgPlan { int kind; int upb; unsigned nz; int sps; int bpb; int mtb, ntb, 
 // kind: 0 LDS-free streaming kernel (thin matrices), 1 LDS-staged x3, 2 exact fp32, 3 wide-tile LDS ring (pw_wgrad_wide_kernel);
 // mtb / ntb: row tiles per block, mg / ng groups; w_*: tile rows, tile counts, ring depth and operand order of kind 3
 
-// (row tiles per block) pairs the streaming kernel is instantiated for
-// (the x side carries the SE scale / BatchNorm transform and costs more registers per tile: <= 3 tiles there, <= 4 on the dz side)
-static bool thin_pair(int m, int n) { return m >= 1 && m <= 4 && n >= 1 && n <= 3; }
 // Tile shape of the wide-tile kernel for a (Co, Ci) matrix, and whether the plan uses it (EAT_WGRAD_WIDE: bit 0 = instead of
 // the 128 x 128-tile kernel, bit 1 = also instead of the streaming kernel where that re-reads an operand; default 3).
 // Measured (tools/bench_kernels.py wgrad): the producers' fixed cost per unit (13 load instructions, one barrier) loses on
@@ -979,12 +1024,17 @@ static WgPlan wgrad_plan(int B, int Co, int Ci, int S, int per_sample, int exact
         thin = true; p.mtb = p.ntb = mtn; p.mg = p.ng = 1; p.gram = true;
       } else if (Co <= 64 && Ci <= 64 && (Co <= 16 || Ci <= 16)) {
         thin = true; p.mtb = mtn; p.ntb = ntn; p.mg = p.ng = 1;
-      } else if (total * 32 >= (1 << 19)) {
-        // a long k axis (>= 512 k positions) over few rows: groups of <= 4 row tiles per block, at most 4 groups (the other
-        // operand is re-read once per group, from L2)
-        const int mg = (mtn + 3) / 4, ng = (ntn + 2) / 3;
+      } else {
+        // few rows over a long k axis: groups of <= 4 x 3 row tiles per block, at most 4 groups (the other operand is re-read
+        // once per group, from L2); 72 x 24 / 24 x 72 as one 5 x 2 / 2 x 5 group (both operands read once, no zero tiles:
+        // measured faster at B = 256, profiles/thin_wgrad_before_after.md).  "Long": each of a row group's 1024 / groups
+        // blocks gets >= 512 k positions (16 units, 4 per wave) to stream in front of its tile's atomics.
+        const bool one52 = (mtn == 5 && ntn == 2) || (mtn == 2 && ntn == 5);
+        const int mg = one52 ? 1 : (mtn + 3) / 4, ng = one52 ? 1 : (ntn + 2) / 3;
         const int mtb = (mtn + mg - 1) / mg, ntb = (ntn + ng - 1) / ng;
-        if (mg * ng <= 4 && thin_pair(mtb, ntb)) { thin = true; p.mtb = mtb; p.ntb = ntb; p.mg = mg; p.ng = ng; }
+        if (mg * ng <= 4 && thin_pair(mtb, ntb) && total * 32 * (mg * ng) >= (1 << 19)) {
+          thin = true; p.mtb = mtb; p.ntb = ntb; p.mg = mg; p.ng = ng;
+        }
         // more than one row group = the other operand is read once per group: the wide-tile kernel reads it once
         if (thin && mg * ng > 1 && wide_shape(Co, Ci, per_sample, same, no_wide, has_xscale, has_tf).ok) thin = false;
       }
@@ -1073,6 +1123,7 @@ static int pw_wgrad_impl(const float* dz, const float* x, const float* x_scale, 
     EAT_NARROW(2, 1); EAT_NARROW(3, 1); EAT_NARROW(4, 1);
     EAT_NARROW(2, 2); EAT_NARROW(3, 3); EAT_NARROW(4, 4);       // (2,2), (4,4): Gram mode only (dz == x, Co == Ci)
     EAT_NARROW(2, 3); EAT_NARROW(3, 2); EAT_NARROW(4, 2); EAT_NARROW(4, 3);
+    EAT_NARROW(5, 2); EAT_NARROW(2, 5);
 #undef EAT_NARROW
     if (use_ws)
       hipLaunchKernelGGL(wgrad_slot_reduce_kernel, dim3((Co * Ci + 63) / 64), dim3(256), 0, hs, ws, dW, Co * Ci, slots);

@@ -96,6 +96,31 @@ if "wgrad" in what:
                 t = timeit(lambda: ops.pw_conv_wgrad(dz, x, x_scale=sc, tf=(a, b, ops.ACT_HSWISH)), n=20)
             mb = (Co + Ci) * S * B * 4 / 1e6
             print("wgrad_tf %4d x %4d @ %5d  %7.1f us  %6.0f MB alg  %5.2f TB/s" % (Co, Ci, S, t, mb, mb / t))
+        # the streaming kernel's launches of the mn10 step (thin early layers, small Gram matrices) and the two S = 2000
+        # project convs next to its long-k rule; kind = eat_pw_wgrad_kernel_kind (streaming: 10 * (1000 mtb + 10 ntb + gram))
+        from efficientat_amd import _lib
+        thin = [(64, 16, 32000, None, False), (72, 24, 8000, None, False), (24, 72, 8000, ops.ACT_RELU, False),
+                (16, 16, 32000, ops.ACT_HSWISH, False), (24, 64, 8000, ops.ACT_RELU, False),
+                (40, 72, 2000, ops.ACT_RELU, True), (40, 120, 2000, ops.ACT_HSWISH, True)]
+        for (Co, Ci, S, act, se) in thin:
+            dz, x = torch.randn(B, Co, S, 1, device=dev), torch.randn(B, Ci, S, 1, device=dev)
+            a, b = torch.rand(Ci, device=dev) + 0.5, torch.randn(Ci, device=dev) * 0.3
+            sc = torch.rand(B, Ci, device=dev) if se else None
+            tf = None if act is None else (a, b, act)
+            kind = _lib.lib().eat_pw_wgrad_kernel_kind(B, Co, Ci, S, 0, 0, 1 if se else 0, 0 if tf is None else 1)
+            with ops.zero_arena.scope("k"):
+                t = timeit(lambda: ops.pw_conv_wgrad(dz, x, x_scale=sc, tf=tf), n=20)
+            mb = (Co + Ci) * S * B * 4 / 1e6
+            print("wgrad_thin%s %4d x %4d @ %5d  kind %6d  %7.1f us  %6.0f MB alg  %5.2f TB/s"
+                  % ("" if tf is None else ("_tf_sc" if se else "_tf"), Co, Ci, S, kind, t, mb, mb / t))
+        for (C, S) in [(16, 32000), (24, 8000), (40, 2000)]:
+            x = torch.randn(B, C, S, 1, device=dev) + 0.5
+            sx = x.sum(dim=(0, 2, 3))
+            kind = _lib.lib().eat_pw_wgrad_kernel_kind(B, C, C, S, 0, 1, 0, 0)
+            with ops.zero_arena.scope("k"):
+                t = timeit(lambda: ops.gram(x, sx=sx), n=20)
+            mb = C * S * B * 4 / 1e6
+            print("gram_centered %4d @ %5d  kind %6d  %7.1f us  %6.0f MB alg  %5.2f TB/s" % (C, S, kind, t, mb, mb / t))
 if "mixstyle" in what:
     # frequency-wise MixStyle of a DCASE20 batch (64 log-mels of 10 s) next to the torch-op restatement of the same maths
     # (dropin/helpers/utils.py `mixstyle` past its draws); bytes: x read twice (statistics, apply) + out written once
