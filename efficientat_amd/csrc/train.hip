@@ -1,9 +1,13 @@
-// 1x1 (pointwise) weight-gradient and Gram-matrix kernels of the training step for gfx950, their launch plan
-// (wgrad_plan) and entry points: autograd of F.conv2d w.r.t. the weight (SURVEY.md Appendix C lists the formulas the
-// reference leaves to autograd).  The BatchNorm passes are in bn_train.hip, the depthwise / stem gradients in dw_grad.hip.
-#include <cstdlib>
+// 1x1 (pointwise) weight-gradient and Gram-matrix kernels of the training step for gfx950 and their entry points: autograd
+// of F.conv2d w.r.t. the weight (SURVEY.md Appendix C lists the formulas the reference leaves to autograd).  Which kernel a
+// shape runs on and how its k range is cut is decided in wgrad_plan.h (host-only, one request -> one plan); the host layer at
+// the end of this file turns a plan into launches.  The BatchNorm passes are in bn_train.hip, the depthwise / stem gradients
+// in dw_grad.hip.
 #include "eat_common.h"
 #include "act_io.h"
+#include "wgrad_plan.h"
+
+namespace wg = eat::wg;
 
 namespace {
 
@@ -924,166 +928,71 @@ __global__ __launch_bounds__(256) void wgrad_slot_reduce4_kernel(const float* __
   }
 }
 
-// (row tiles per block) pairs the streaming kernel is instantiated for
-// (the x side carries the SE scale / BatchNorm transform and costs more registers per tile: <= 3 tiles there, <= 4 on the dz side)
-// plus 5 x 2 / 2 x 5: 72 x 24 and 24 x 72 as ONE row group (both operands read once, no zero tiles)
-constexpr bool thin_pair(int m, int n) {
-  return (m >= 1 && m <= 4 && n >= 1 && n <= 3) || (m == 5 && n == 2) || (m == 2 && n == 5);
-}
+// One instance of the streaming kernel; false where the pair has no instance of the asked form (4 x 4 exists in the Gram form only)
 template <int MTN, int NTN>
-static void launch_narrow(const float* dz, const float* x, const float* x_scale, float* dW, int B, int Co, int Ci, int S,
-                          int sps, int upb, unsigned nz, int n_slots, hipStream_t s, WgTf tf, int mg, int ng, bool gram,
-                          int ps_spl = 0) {
+static bool launch_narrow(const float* dz, const float* x, const float* x_scale, float* dW, int B, int Co, int Ci, int S,
+                          const wg::WgPlan& p, int n_slots, hipStream_t s, WgTf tf) {
   if constexpr (MTN == NTN) {                                  // Gram matrix (dz == x, Co == Ci): the operand is loaded once
-    if (gram) {
-      hipLaunchKernelGGL((pw_wgrad_x3_narrow_kernel<MTN, NTN, true>), dim3(1, 1, nz), dim3(256), 0, s, dz, x, x_scale, dW, B,
-                         Co, Ci, S, sps, upb, n_slots, tf, 0);
-      return;
+    if (p.gram) {
+      hipLaunchKernelGGL((pw_wgrad_x3_narrow_kernel<MTN, NTN, true>), dim3(1, 1, p.nz), dim3(256), 0, s, dz, x, x_scale, dW, B,
+                         Co, Ci, S, p.sps, p.upb, n_slots, tf, 0);
+      return true;
     }
   }
-  if constexpr (MTN * NTN < 16)                                // (4 x 4 exists in the Gram form only)
-    hipLaunchKernelGGL((pw_wgrad_x3_narrow_kernel<MTN, NTN, false>), dim3(mg, ng, nz), dim3(256), 0, s, dz, x, x_scale, dW, B,
-                       Co, Ci, S, sps, upb, n_slots, tf, ps_spl);
+  if constexpr (MTN * NTN < 16) {
+    hipLaunchKernelGGL((pw_wgrad_x3_narrow_kernel<MTN, NTN, false>), dim3(p.mg, p.ng, p.nz), dim3(256), 0, s, dz, x, x_scale,
+                       dW, B, Co, Ci, S, p.sps, p.upb, n_slots, tf, p.ps_spl);
+    return true;
+  }
+  return false;
+}
+
+// One launch of pw_wgrad_wide_kernel: the kernel's arguments by name (what a launch does not use stays at its default)
+struct WideArgs {
+  const char* who;                       // entry point, for the error message
+  hipStream_t stream;
+  const float* dz; const float* x; const float* x_scale;
+  float* out;                            // nz copies of dW (per-sample: see ps_ns)
+  int B, Co, Ci, S, sps, upb; unsigned nz;
+  wg::WideShape w;
+  const float* radd = nullptr;           // RADD: additive constant per x row (centred Gram matrix)
+  int same = 0;
+  const float* tf_a = nullptr; const float* tf_b = nullptr; int tf_act = 0;   // PTF
+  int ps_ns = 0;                         // per-sample launch: k-slices per sample
+};
+template <int NPROD, bool SWAP, bool SCALE, bool RADD, bool P16 = false, bool PTF = false>
+static int launch_wide(const WideArgs& a) {
+  auto kern = pw_wgrad_wide_kernel<NPROD, SWAP, SCALE, RADD, P16, PTF>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, wg::wide_lds_limit) != hipSuccess)
+      return eat::fail(EAT_ELAUNCH, "%s: hipFuncSetAttribute(160 KB of LDS) failed", a.who);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kern, dim3(a.w.ptn, a.w.qtn, a.nz), dim3(512), (size_t)wg::wide_lds_bytes(a.w), a.stream, a.dz, a.x,
+                     a.x_scale, a.out, a.B, a.Co, a.Ci, a.S, a.sps, a.upb, a.w.ptr, a.w.qtr, a.radd, a.same, a.tf_a, a.tf_b,
+                     a.tf_act, a.ps_ns);
+  return EAT_OK;
+}
+// <SWAP, SCALE> from the run-time operand order and SE scale.  A bf16-stored dz as P (P16, not SWAP) has neither SE scale nor
+// transform (the entry points refuse them): those instances do not exist
+template <int NPROD, bool P16 = false, bool PTF = false>
+static int launch_wide_sw_sc(const WideArgs& a) {
+  if (a.w.swap) return a.x_scale ? launch_wide<NPROD, true, true, false, P16, PTF>(a) : launch_wide<NPROD, true, false, false, P16, PTF>(a);
+  if constexpr (PTF) return eat::fail(EAT_EINVAL, "%s: internal: the on-load transform belongs to the x operand as P", a.who);
+  else if constexpr (P16) return launch_wide<NPROD, false, false, false, true>(a);
+  else return a.x_scale ? launch_wide<NPROD, false, true, false>(a) : launch_wide<NPROD, false, false, false>(a);
 }
 
 }  // namespace
 
-// Launch plan of the 1x1 weight gradient: which kernel, how the k range is cut (also exported through
-// eat_pw_wgrad_slots so that a caller can size a one-slot-per-block workspace)
-struct WgPlan { int kind; int upb; unsigned nz; int sps; int bpb; int mtb, ntb, mg, ng; bool gram; int ps_spl;
-                int w_ptr = 0, w_qtr = 0, w_ptn = 0, w_qtn = 0, w_depth = 0; bool w_swap = false; };
-// kind: 0 LDS-free streaming kernel (thin matrices), 1 LDS-staged x3, 2 exact fp32, 3 wide-tile LDS ring (pw_wgrad_wide_kernel);
-// mtb / ntb: row tiles per block, mg / ng groups; w_*: tile rows, tile counts, ring depth and operand order of kind 3
-
-// Tile shape of the wide-tile kernel for a (Co, Ci) matrix, and whether the plan uses it (EAT_WGRAD_WIDE: bit 0 = instead of
-// the 128 x 128-tile kernel, bit 1 = also instead of the streaming kernel where that re-reads an operand; default 3).
-// Measured (tools/bench_kernels.py wgrad): the producers' fixed cost per unit (13 load instructions, one barrier) loses on
-// tiles of fewer than ~20 pieces (160 rows of P + Q), and the on-load transform makes the producers the pole.
-struct WideShape { bool ok; bool swap; int ptr, qtr, ptn, qtn; };
-static WideShape wide_shape(int Co, int Ci, bool per_sample, bool same, bool no_wide, bool has_xscale, bool has_tf) {
-  constexpr int wide_min = 20;
-  WideShape w{false, Ci > Co, 0, 0, 0, 0};
-  if (per_sample || no_wide || has_tf || (has_xscale && (Ci & 3) != 0)) return w;
-  if (same) {
-    // Gram matrix (dz == x, train_fuse.hip): ONE operand, loaded once - P = x, the Q fragments are read from P's rows.  Above
-    // the streaming kernel's range (C > 64) up to what one consumer quartet holds (10 column tiles); 80 x 80 at 504
-    // positions x 256 clips: 62 us on the 128 x 128-tile kernel for 41 MB of input
-    if (Co != Ci || Co <= 64 || Co > 160 || has_xscale) return w;
-    w.swap = true;
-    w.ptn = w.qtn = 1;
-    w.ptr = w.qtr = (Co + 15) / 16 * 16;
-    w.ok = true;
-    return w;
-  }
-  const int PR = w.swap ? Ci : Co, QR = w.swap ? Co : Ci;
-  // (tile limits measured: P <= 192 / 128 rows per block instead of 256: 672 x 112 147 -> 157 / 198 us, mn10 step +0.3 ms;
-  //  384 blocks instead of one per CU: +0.3 ms; minimum of 14 / 30 pieces instead of 20: +0.1 ms)
-  w.ptn = (PR + 255) / 256;
-  w.ptr = ((PR + w.ptn - 1) / w.ptn + 15) / 16 * 16;
-  w.qtn = (QR + 159) / 160;                                  // rows of Q per block: 4 producers x 5 pieces of 8 rows
-  w.qtr = ((QR + w.qtn - 1) / w.qtn + 15) / 16 * 16;
-  w.ok = (w.ptn - 1) * w.ptr < PR && (w.qtn - 1) * w.qtr < QR && w.ptr / 8 + w.qtr / 8 >= wide_min;
-  return w;
-}
-static WgPlan wgrad_plan(int B, int Co, int Ci, int S, int per_sample, int exact_fp32, bool same, bool has_scale_or_tf,
-                         bool has_xscale = false, bool no_wide = false,
-                         bool has_tf = false) {
-  static const bool env_fp32 = getenv("EAT_WGRAD_FP32") && atoi(getenv("EAT_WGRAD_FP32")) != 0;
-  const bool force_fp32 = env_fp32 || exact_fp32 == 1;      // exact_fp32: 0 = bf16x3, 1 = exact fp32, 2 = plain bf16
-  const bool ps_x3 = per_sample && Co >= 64 && Ci >= 64;
-  WgPlan p{2, 0, 0, (S + 31) / 32, 0, 0, 0, 1, 1, false, 0};
-  if (!force_fp32 && (S & 3) == 0) {
-    const int sps = p.sps;
-    const int mtn = (Co + 15) / 16, ntn = (Ci + 15) / 16;
-    if (per_sample && !ps_x3 && sps >= 32) {
-      // per-sample gradients of the thin early-layer matrices (one side < 64 channels, planes of >= 1024 positions):
-      // the same streaming kernel, a few blocks per sample adding into the sample's own matrix
-      const int mg = (mtn + 3) / 4, ng = (ntn + 2) / 3;
-      const int mtb = (mtn + mg - 1) / mg, ntb = (ntn + ng - 1) / ng;
-      if (mg * ng <= 4 && thin_pair(mtb, ntb)) {
-        int spl = 1024 / (mg * ng * B);
-        if (spl > sps / 16) spl = sps / 16;
-        if (spl < 1) spl = 1;
-        p.kind = 0; p.mtb = mtb; p.ntb = ntb; p.mg = mg; p.ng = ng;
-        p.upb = (sps + spl - 1) / spl;
-        p.ps_spl = (sps + p.upb - 1) / p.upb;
-        p.nz = (unsigned)(B * p.ps_spl);
-        return p;
-      }
-    }
-  }
-  if (!force_fp32 && (!per_sample || ps_x3) && (S & 3) == 0) {
-    const int sps = p.sps;
-    const int tiles = ((Co + 127) / 128) * ((Ci + 127) / 128);
-    const long long total = (long long)B * sps;
-    const bool gram = same && Co == Ci && !has_scale_or_tf;
-    const int mtn = (Co + 15) / 16, ntn = (Ci + 15) / 16;
-    bool thin = false;
-    if (!per_sample) {
-      if (gram && Co <= 64) {                                  // Gram matrix: the operand is loaded once
-        thin = true; p.mtb = p.ntb = mtn; p.mg = p.ng = 1; p.gram = true;
-      } else if (Co <= 64 && Ci <= 64 && (Co <= 16 || Ci <= 16)) {
-        thin = true; p.mtb = mtn; p.ntb = ntn; p.mg = p.ng = 1;
-      } else {
-        // few rows over a long k axis: groups of <= 4 x 3 row tiles per block, at most 4 groups (the other operand is re-read
-        // once per group, from L2); 72 x 24 / 24 x 72 as one 5 x 2 / 2 x 5 group (both operands read once, no zero tiles:
-        // measured faster at B = 256, profiles/thin_wgrad_before_after.md).  "Long": each of a row group's 1024 / groups
-        // blocks gets >= 512 k positions (16 units, 4 per wave) to stream in front of its tile's atomics.
-        const bool one52 = (mtn == 5 && ntn == 2) || (mtn == 2 && ntn == 5);
-        const int mg = one52 ? 1 : (mtn + 3) / 4, ng = one52 ? 1 : (ntn + 2) / 3;
-        const int mtb = (mtn + mg - 1) / mg, ntb = (ntn + ng - 1) / ng;
-        if (mg * ng <= 4 && thin_pair(mtb, ntb) && total * 32 * (mg * ng) >= (1 << 19)) {
-          thin = true; p.mtb = mtb; p.ntb = ntb; p.mg = mg; p.ng = ng;
-        }
-        // more than one row group = the other operand is read once per group: the wide-tile kernel reads it once
-        if (thin && mg * ng > 1 && wide_shape(Co, Ci, per_sample, same, no_wide, has_xscale, has_tf).ok) thin = false;
-      }
-    }
-    if (thin) {
-      long long splits = (1024 / (p.mg * p.ng)) < total ? (1024 / (p.mg * p.ng)) : total;
-      p.kind = 0;
-      p.upb = (int)((total + splits - 1) / splits);
-      p.nz = (unsigned)((total + p.upb - 1) / p.upb);
-      return p;
-    }
-    {
-      const WideShape w = wide_shape(Co, Ci, per_sample, same, no_wide, has_xscale, has_tf);
-      if (w.ok) {
-        p.w_swap = w.swap; p.w_ptr = w.ptr; p.w_qtr = w.qtr; p.w_ptn = w.ptn; p.w_qtn = w.qtn;
-        const int wtiles = w.ptn * w.qtn;
-        constexpr int wtarget = 256;                           // one block per CU
-        long long splits = wtiles >= wtarget ? 1 : wtarget / wtiles;
-        if (splits > total / 16) splits = total / 16;
-        if (splits < 1) splits = 1;
-        p.kind = 3;
-        p.upb = (int)((total + splits - 1) / splits);
-        p.nz = (unsigned)((total + p.upb - 1) / p.upb);
-        return p;
-      }
-    }
-    p.kind = 1;
-    p.upb = sps;                                             // per-sample gradients: one sample per block
-    if (!per_sample) {
-      // ~512 blocks, but at least 16 units (512 k) of MFMA work in front of a block's Co x Ci atomics
-      // (512 = one round of two resident blocks per CU; 1024 measured 0.26 ms slower per mn10 step: the second round pays
-      // prologue, tail and the Co x Ci atomics again)
-      constexpr int target = 512;
-      // never MORE than `target` blocks: 516 blocks (6 tiles x 86 slices, the 672 x 112 layers) ran as a full round of 512
-      // resident blocks plus a second round of 4 (183 -> 158 us with 510)
-      long long splits = tiles >= target ? 1 : target / tiles;
-      if (splits > total / 16) splits = total / 16;
-      if (splits < 1) splits = 1;
-      p.upb = (int)((total + splits - 1) / splits);
-    }
-    p.nz = (unsigned)((total + p.upb - 1) / p.upb);
-    return p;
-  }
-  const int tiles = ((Co + 31) / 32) * ((Ci + 31) / 32);
-  int splits = (1024 + tiles - 1) / tiles;
-  if (splits > B || per_sample) splits = B;
-  p.bpb = (B + splits - 1) / splits;
-  p.nz = (unsigned)((B + p.bpb - 1) / p.bpb);
-  return p;
+static wg::WgReq wg_req(int B, int Co, int Ci, int S, bool per_sample, int exact_fp32, bool same, bool x_scale, wg::Xf xf,
+                        int ws_slots) {
+  wg::WgReq r{};
+  r.B = B; r.Co = Co; r.Ci = Ci; r.S = S;
+  r.per_sample = per_sample; r.arith = wg::arith_of(exact_fp32); r.same = same; r.x_scale = x_scale; r.xf = xf;
+  r.ws_slots = ws_slots;
+  return r;
 }
 
 static int pw_wgrad_impl(const float* dz, const float* x, const float* x_scale, float* dW, int B, int Co, int Ci, int S,
@@ -1092,74 +1001,47 @@ static int pw_wgrad_impl(const float* dz, const float* x, const float* x_scale, 
   // default: split-operand bf16 MFMA kernel (fp32-class accuracy); exact_fp32 (the caller's precision choice),
   // EAT_WGRAD_FP32=1 (process-wide debug override) or S % 4 != 0: exact fp32 MFMA kernel.
   // per-sample gradients (DyMN: K = one plane, B x Co x Ci outputs): the bf16x3 kernel with one block per (tile, sample)
-  // and plain stores from Co, Ci >= 64 on (EAT_DYN_WGRAD_X3=0 restores the 32 x 32-tile fp32 kernel).
+  // and plain stores from Co, Ci >= 64 on.
   // ws / n_slots (zero-filled, n_slots * Co * Ci floats): the blocks' atomics go to copy blockIdx.z % n_slots and a
   // second kernel adds the copies into dW in a fixed order; n_slots >= eat_pw_wgrad_slots(...) gives every block its own
   // copy (bit-reproducible result).  The LDS-staged and exact kernels use the workspace only in that one-per-block form.
-  // (a centring transform - tf.actr set - keeps the Gram plan: both operands are the same centred rows)
   // centring form of the Gram launches (eat_gram_centered): a = 1, b = actr = -mean, no activation - an additive row constant
-  const bool centring = dz == x && tf.actr != nullptr && tf.act == EAT_ACT_NONE;
-  WgPlan p = wgrad_plan(B, Co, Ci, S, per_sample, exact_fp32, dz == x, x_scale != nullptr || (tf.a != nullptr && !tf.actr),
-                        x_scale != nullptr, tf.actr != nullptr && !centring, tf.a != nullptr && !centring);
-  // the wide-tile kernel stores one copy of dW per k-slice: it needs the workspace (eat_pw_conv_wgrad_ws with
-  // n_slots >= eat_pw_wgrad_slots) and 16-byte aligned rows; without them the plan is the one without it
-  // A caller that DID bring a workspace sized it with eat_pw_wgrad_slots / eat_pw_wgrad_kernel_kind and - for this kernel -
-  // left it uninitialised: too few copies means the two plans diverged, and the atomic kernels of the fallback plan would
-  // add into garbage.  Fail instead of falling back.
-  if (p.kind == 3 && ws != nullptr && (Ci & 3) == 0 && n_slots < (int)p.nz)
+  const wg::Xf xf = tf.a == nullptr ? wg::Xf::none : tf.actr != nullptr && tf.act == EAT_ACT_NONE ? wg::Xf::centre : wg::Xf::bn_act;
+  // (a workspace pointer with no copy behind it is refused where the stored-slice kernel wants one: < 0, not "no workspace")
+  const wg::Planned pl = wg::plan(wg_req(B, Co, Ci, S, per_sample != 0, exact_fp32, dz == x, x_scale != nullptr, xf,
+                                         ws == nullptr ? 0 : n_slots != 0 ? n_slots : -1));
+  if (pl.ws_short)
     return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad_ws: workspace of %d copies, the stored-slice kernel needs %u "
-                     "(eat_pw_wgrad_slots)", n_slots, p.nz);
-  if (p.kind == 3 && !(ws != nullptr && n_slots >= (int)p.nz && (Ci & 3) == 0))
-    p = wgrad_plan(B, Co, Ci, S, per_sample, exact_fp32, dz == x, x_scale != nullptr || (tf.a != nullptr && !tf.actr),
-                   x_scale != nullptr, true, tf.a != nullptr && !centring);
+                     "(eat_pw_wgrad_slots)", n_slots, pl.wide_nz);
+  const wg::WgPlan& p = pl.p;
   hipStream_t hs = (hipStream_t)stream;
-  const bool priv = ws != nullptr && !per_sample && n_slots >= (int)p.nz;     // one copy per block
   if (p.kind == 0) {
     const bool use_ws = ws != nullptr && n_slots > 1;
     float* target = use_ws ? ws : dW;
     const int slots = use_ws ? (n_slots < (int)p.nz ? n_slots : (int)p.nz) : 1;
-#define EAT_NARROW(M_, N_) if (p.mtb == M_ && p.ntb == N_) launch_narrow<M_, N_>(dz, x, x_scale, target, B, Co, Ci, S, p.sps, p.upb, p.nz, slots, hs, tf, p.mg, p.ng, p.gram, p.ps_spl)
-    EAT_NARROW(1, 1); EAT_NARROW(1, 2); EAT_NARROW(1, 3); EAT_NARROW(1, 4);
-    EAT_NARROW(2, 1); EAT_NARROW(3, 1); EAT_NARROW(4, 1);
-    EAT_NARROW(2, 2); EAT_NARROW(3, 3); EAT_NARROW(4, 4);       // (2,2), (4,4): Gram mode only (dz == x, Co == Ci)
-    EAT_NARROW(2, 3); EAT_NARROW(3, 2); EAT_NARROW(4, 2); EAT_NARROW(4, 3);
-    EAT_NARROW(5, 2); EAT_NARROW(2, 5);
+    bool launched = false;
+#define EAT_NARROW(M_, N_) if (p.mtb == M_ && p.ntb == N_) launched = launch_narrow<M_, N_>(dz, x, x_scale, target, B, Co, Ci, S, p, slots, hs, tf);
+    EAT_WG_THIN_PAIRS(EAT_NARROW)
 #undef EAT_NARROW
+    if (!launched) return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad: internal: no streaming instance for %d x %d", p.mtb, p.ntb);
     if (use_ws)
       hipLaunchKernelGGL(wgrad_slot_reduce_kernel, dim3((Co * Ci + 63) / 64), dim3(256), 0, hs, ws, dW, Co * Ci, slots);
     return eat::check_launch("eat_pw_conv_wgrad");
   }
+  const bool priv = ws != nullptr && !per_sample && n_slots >= (int)p.nz;     // one copy per block
   float* target = priv ? ws : dW;
   const int slots = priv ? (int)p.nz : 0;
   if (p.kind == 3) {
-    const size_t smem = (size_t)(p.w_ptr / 8 + p.w_qtr / 8) * 2 * 1024;     // two slots of converted fragments
-    dim3 grid(p.w_ptn, p.w_qtn, p.nz);
-    // (the phase-decomposition switches of the round-4 measurement builds - no epilogue stores, no MFMAs, no loads, no
-    //  conversion: DESIGN 3.15 - are not in the shipped kernel)
-#define EAT_WIDE(NP_, SW_, SC_, RA_)                                                                                      \
-    do {                                                                                                                  \
-      auto kern = pw_wgrad_wide_kernel<NP_, SW_, SC_, RA_>;                                                               \
-      static bool attr_set = false;                                                                                       \
-      if (!attr_set) {                                                                                                    \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-          return eat::fail(EAT_ELAUNCH, "eat_pw_conv_wgrad: hipFuncSetAttribute(160 KB of LDS) failed");                  \
-        attr_set = true;                                                                                                  \
-      }                                                                                                                   \
-      hipLaunchKernelGGL(kern, grid, dim3(512), smem, hs, dz, x, x_scale, target, B, Co, Ci, S, p.sps, p.upb, p.w_ptr,    \
-                         p.w_qtr, centring ? tf.b : (const float*)nullptr, dz == x ? 1 : 0, (const float*)nullptr, \
-                         (const float*)nullptr, 0, 0);                                                                   \
-    } while (0)
-#define EAT_WIDE_SC(NP_, SW_) do { if (x_scale) EAT_WIDE(NP_, SW_, true, false); else EAT_WIDE(NP_, SW_, false, false); } while (0)
-#define EAT_WIDE_SW(NP_)                                                                                                  \
-    do {                                                                                                                  \
-      if (centring) EAT_WIDE(NP_, true, false, true);                /* Gram matrices: P = x, no SE scale */                \
-      else if (p.w_swap) EAT_WIDE_SC(NP_, true);                                                                          \
-      else EAT_WIDE_SC(NP_, false);                                                                                       \
-    } while (0)
-    if (exact_fp32 == 2) EAT_WIDE_SW(1); else EAT_WIDE_SW(3);
-#undef EAT_WIDE_SC
-#undef EAT_WIDE_SW
-#undef EAT_WIDE
+    WideArgs a{"eat_pw_conv_wgrad", hs, dz, x, x_scale, target, B, Co, Ci, S, p.sps, p.upb, p.nz, p.w};
+    a.same = dz == x ? 1 : 0;
+    int rc;
+    if (xf == wg::Xf::centre) {                                // Gram matrices: P = x, no SE scale
+      a.radd = tf.b;
+      rc = exact_fp32 == 2 ? launch_wide<1, true, false, true>(a) : launch_wide<3, true, false, true>(a);
+    } else {
+      rc = exact_fp32 == 2 ? launch_wide_sw_sc<1>(a) : launch_wide_sw_sc<3>(a);
+    }
+    if (rc != EAT_OK) return rc;
   } else if (p.kind == 1) {
     dim3 grid((Co + 127) / 128, (Ci + 127) / 128, p.nz);
     if (exact_fp32 == 2)
@@ -1180,27 +1062,23 @@ static int pw_wgrad_impl(const float* dz, const float* x, const float* x_scale, 
   return eat::check_launch("eat_pw_conv_wgrad");
 }
 
-// Number of workspace copies that gives every block of eat_pw_conv_wgrad_ws its own (bit-reproducible result); `same`: the
-// two operands are the same tensor (Gram matrix).  Host helper.
-static int eat_pw_wgrad_kernel_kind_nowide(int B, int Co, int Ci, int S, int exact_fp32, int same, int has_scale, int has_tf) {
-  const WgPlan p = wgrad_plan(B, Co, Ci, S, 0, exact_fp32, same != 0, has_scale != 0 || has_tf != 0, has_scale != 0, true,
-                              has_tf != 0);
+// Which kernel family eat_pw_conv_wgrad[_ws|_tf] launches for a shape when the caller brings the workspace the plan asks for
+// (host helper for bench.py's byte models and the profiles): 0 = pw_wgrad_x3_narrow_kernel<mtb, ntb> (returned as
+// 1000 * mtb + 10 * ntb + gram), 1 = pw_wgrad_x3_kernel, 2 = pw_wgrad_kernel (exact fp32), 3 = pw_wgrad_wide_kernel; encoded as
+// kind + 10 * detail.
+extern "C" int eat_pw_wgrad_kernel_kind(int B, int Co, int Ci, int S, int exact_fp32, int same, int has_scale, int has_tf) {
+  const wg::WgPlan p = wg::plan(wg_req(B, Co, Ci, S, false, exact_fp32, same != 0, has_scale != 0,
+                                       has_tf != 0 ? wg::Xf::bn_act : wg::Xf::none, wg::ws_enough)).p;
   return p.kind == 0 ? 10 * (1000 * p.mtb + 10 * p.ntb + (p.gram ? 1 : 0)) : p.kind;
 }
-// Which kernel family eat_pw_conv_wgrad[_ws|_tf] launches for a shape (host helper for bench.py's byte models and the
-// profiles): 0 = pw_wgrad_x3_narrow_kernel<mtb, ntb> (returned as 1000 * mtb + 10 * ntb + gram), 1 = pw_wgrad_x3_kernel,
-// 2 = pw_wgrad_kernel (exact fp32), 3 = pw_wgrad_wide_kernel; encoded as kind + 10 * detail.
-extern "C" int eat_pw_wgrad_kernel_kind(int B, int Co, int Ci, int S, int exact_fp32, int same, int has_scale, int has_tf) {
-  const WgPlan p = wgrad_plan(B, Co, Ci, S, 0, exact_fp32, same != 0, has_scale != 0 || has_tf != 0, has_scale != 0, false,
-                              has_tf != 0);
-  if (p.kind == 3 && (Ci & 3) != 0)                           // (the wide-tile kernel needs 16-byte aligned rows of dW)
-    return eat_pw_wgrad_kernel_kind_nowide(B, Co, Ci, S, exact_fp32, same, has_scale, has_tf);
-  if (p.kind == 0) return 10 * (1000 * p.mtb + 10 * p.ntb + (p.gram ? 1 : 0));
-  return p.kind;
-}
 
+// Number of workspace copies that gives every block of eat_pw_conv_wgrad_ws its own (bit-reproducible result); `same`: the
+// two operands are the same tensor (Gram matrix).  Host helper.  It has no argument for an SE scale or an operand transform
+// and assumes neither, and where the plan prefers the stored-slice kernel it answers for that kernel whether or not the rows
+// of dW are 16-byte aligned: callers ask eat_pw_wgrad_kernel_kind first.
 extern "C" int eat_pw_wgrad_slots(int B, int Co, int Ci, int S, int exact_fp32, int same) {
-  return (int)wgrad_plan(B, Co, Ci, S, 0, exact_fp32, same != 0, false).nz;
+  const wg::Planned pl = wg::plan(wg_req(B, Co, Ci, S, false, exact_fp32, same != 0, false, wg::Xf::none, wg::ws_enough));
+  return (int)(pl.wide_nz ? pl.wide_nz : pl.p.nz);
 }
 
 extern "C" int eat_pw_conv_wgrad(const float* dz, const float* x, const float* x_scale, float* dW, int B, int Co,
@@ -1235,32 +1113,8 @@ extern "C" int eat_pw_conv_wgrad_tf(const float* dz, const float* x, const float
 // gradient, ex_pl_audioset.py:287-293).  Always the wide-tile producer / consumer kernel with the bf16 operand as P (its
 // fragments need no conversion); ws: >= eat_pw_wgrad_b16_slots(...) * Co * Ci floats (no zero fill), dW is added to (zeroed by
 // the caller).  S % 4 == 0, Ci % 4 == 0.
-struct WgB16Plan { WideShape w; int upb; unsigned nz; int sps; };
-static WgB16Plan wgrad_b16_plan(int B, int Co, int Ci, int S, int x_b16) {
-  // x_b16: 1 = x is the bf16 (wide) operand, 0 = dz is; 2 = BOTH operands fp32 (the per-sample gradients of the fp32-storage
-  // DyMN plan on the same kernel, split-operand products): P = the operand with more rows
-  WgB16Plan p{};
-  p.sps = (S + 31) / 32;
-  WideShape& w = p.w;
-  w.swap = x_b16 == 2 ? Ci > Co : x_b16 != 0;
-  const int PR = w.swap ? Ci : Co, QR = w.swap ? Co : Ci;
-  w.ptn = (PR + 255) / 256;
-  w.ptr = ((PR + w.ptn - 1) / w.ptn + 15) / 16 * 16;
-  w.qtn = (QR + 159) / 160;
-  w.qtr = ((QR + w.qtn - 1) / w.qtn + 15) / 16 * 16;
-  w.ok = (w.ptn - 1) * w.ptr < PR && (w.qtn - 1) * w.qtr < QR;
-  const long long total = (long long)B * p.sps;
-  const int wtiles = w.ptn * w.qtn;
-  long long splits = wtiles >= 256 ? 1 : 256 / wtiles;                // one block per CU
-  if (splits > total / 16) splits = total / 16;
-  if (splits < 1) splits = 1;
-  p.upb = (int)((total + splits - 1) / splits);
-  p.nz = (unsigned)((total + p.upb - 1) / p.upb);
-  return p;
-}
-
 extern "C" int eat_pw_wgrad_b16_slots(int B, int Co, int Ci, int S, int x_b16) {
-  return (int)wgrad_b16_plan(B, Co, Ci, S, x_b16).nz;
+  return (int)wg::plan_b16(B, Co, Ci, S, x_b16).nz;
 }
 
 extern "C" int eat_pw_conv_wgrad_b16(const void* dz, int dz_b16, const void* x, int x_b16, const float* tf_a,
@@ -1273,34 +1127,17 @@ extern "C" int eat_pw_conv_wgrad_b16(const void* dz, int dz_b16, const void* x, 
     return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad_b16: Ci=%d and S=%d must be multiples of 4", Ci, S);
   if ((tf_a == nullptr) != (tf_b == nullptr) || tf_act < 0 || tf_act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad_b16: bad transform");
   if (dz_b16 && (tf_a || x_scale)) return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad_b16: transform / scale belong to a bf16 x operand");
-  const WgB16Plan p = wgrad_b16_plan(B, Co, Ci, S, x_b16);
+  const wg::WgB16Plan p = wg::plan_b16(B, Co, Ci, S, x_b16);
   if (!p.w.ok) return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad_b16: internal tiling error (%d x %d)", Co, Ci);
   if (n_slots < (int)p.nz) return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad_b16: workspace of %d copies, %u needed", n_slots, p.nz);
   if ((long long)(x_b16 ? Ci : Co) * S * 2 > 0x7fffffffLL || (long long)(x_b16 ? Co : Ci) * S * 4 > 0x7fffffffLL)
     return eat::fail(EAT_EINVAL, "eat_pw_conv_wgrad_b16: a sample exceeds the 32-bit row offsets");
   hipStream_t hs = (hipStream_t)stream;
-  const size_t smem = (size_t)(p.w.ptr / 8 + p.w.qtr / 8) * 2 * 1024;
-  dim3 grid(p.w.ptn, p.w.qtn, p.nz);
-  const float* fdz = reinterpret_cast<const float*>(dz);
-  const float* fx = reinterpret_cast<const float*>(x);
-#define EAT_WIDE16(SW_, SC_, TF_)                                                                                          \
-  do {                                                                                                                    \
-    auto kern = pw_wgrad_wide_kernel<1, SW_, SC_, false, true, TF_>;                                                      \
-    static bool attr_set = false;                                                                                         \
-    if (!attr_set) {                                                                                                      \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-        return eat::fail(EAT_ELAUNCH, "eat_pw_conv_wgrad_b16: hipFuncSetAttribute(160 KB of LDS) failed");                \
-      attr_set = true;                                                                                                    \
-    }                                                                                                                     \
-    hipLaunchKernelGGL(kern, grid, dim3(512), smem, hs, fdz, fx, x_scale, ws, B, Co, Ci, S, p.sps, p.upb, p.w.ptr, p.w.qtr,    \
-                       (const float*)nullptr, 0, tf_a, tf_b, tf_act, 0);                                                  \
-  } while (0)
-  if (!x_b16) EAT_WIDE16(false, false, false);
-  else if (tf_a && x_scale) EAT_WIDE16(true, true, true);
-  else if (tf_a) EAT_WIDE16(true, false, true);
-  else if (x_scale) EAT_WIDE16(true, true, false);
-  else EAT_WIDE16(true, false, false);
-#undef EAT_WIDE16
+  WideArgs a{"eat_pw_conv_wgrad_b16", hs, reinterpret_cast<const float*>(dz), reinterpret_cast<const float*>(x), x_scale, ws,
+             B, Co, Ci, S, p.sps, p.upb, p.nz, p.w};
+  a.tf_a = tf_a; a.tf_b = tf_b; a.tf_act = tf_act;
+  const int rc = tf_a ? launch_wide_sw_sc<1, true, true>(a) : launch_wide_sw_sc<1, true>(a);
+  if (rc != EAT_OK) return rc;
   hipLaunchKernelGGL(wgrad_slot_reduce4_kernel, dim3((Co * Ci + 255) / 256), dim3(256), 0, hs, ws, dW, Co * Ci, (int)p.nz);
   return eat::check_launch("eat_pw_conv_wgrad_b16");
 }
@@ -1308,21 +1145,11 @@ extern "C" int eat_pw_conv_wgrad_b16(const void* dz, int dz_b16, const void* x, 
 // Per-sample weight gradients of a dynamic 1x1 conv under the bf16-storage plan (autograd of the grouped F.conv2d of
 // models/dymn/dy_block.py:120-127): dW_b (B, Co, Ci) = dz[b] x[b]^T with exactly one bf16 operand (the wide tensor), plain bf16
 // products, fp32 accumulation.  The wide-tile kernel of eat_pw_conv_wgrad_b16 with one k-slice per SAMPLE: slice b is stored as
-// dW_b[b] - every element of dW_b is written, no zero fill, no reduction.  S % 4 == 0, Ci % 4 == 0.
-// k-slices per sample: a sample's reduction is cut into several blocks where B x (tiles of dW) alone would leave CUs idle - the
-// early layers (thin matrices, planes of thousands of positions: 128 one-tile blocks walking 1000 units each ran at 1.9 TB/s)
-static int dyn_wgrad_b16_slices(const WgB16Plan& p, int B) {
-  const long long blocks = (long long)p.w.ptn * p.w.qtn * B;
-  int ns = 1;
-  while (ns < 8 && blocks * ns < 1024 && p.sps / (2 * ns) >= 8) ns *= 2;
-  while (ns > 1 && (ns - 1) * ((p.sps + ns - 1) / ns) >= p.sps) --ns;    // every slice must own at least one unit
-  return ns;
-}
-
+// dW_b[b] - every element of dW_b is written, no zero fill, no reduction - or wg::dyn_b16_slices(...) k-slices per sample.
+// S % 4 == 0, Ci % 4 == 0.
 extern "C" int eat_pw_dyn_wgrad_b16_slices(int B, int Co, int Ci, int S, int x_b16) {
-  const WgB16Plan p = wgrad_b16_plan(B, Co, Ci, S, x_b16);
-  if (!p.w.ok || (S & 3) != 0 || (Ci & 3) != 0) return 0;               // (0: this shape does not run on the wide-tile kernel)
-  return dyn_wgrad_b16_slices(p, B);
+  const wg::WgB16Plan p = wg::plan_b16(B, Co, Ci, S, x_b16);
+  return p.w.ok && (S & 3) == 0 && (Ci & 3) == 0 ? wg::dyn_b16_slices(p, B) : 0;   // (0: not on the wide-tile kernel)
 }
 
 extern "C" int eat_pw_conv_dyn_wgrad_b16(const void* dz, int dz_b16, const void* x, int x_b16, float* dW_b, int n_slices, int B,
@@ -1333,47 +1160,18 @@ extern "C" int eat_pw_conv_dyn_wgrad_b16(const void* dz, int dz_b16, const void*
   if (B < 1 || Co < 1 || Ci < 4 || (Ci & 3) != 0 || S < 4 || (S & 3) != 0)
     return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_wgrad_b16: Ci=%d and S=%d must be multiples of 4", Ci, S);
   const bool f32 = !dz_b16 && !x_b16;                                  // both fp32: split-operand (bf16x3) products
-  WgB16Plan p = wgrad_b16_plan(B, Co, Ci, S, f32 ? 2 : x_b16);
+  const wg::WgB16Plan p = wg::plan_b16(B, Co, Ci, S, f32 ? 2 : x_b16);
   if (!p.w.ok) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_wgrad_b16: internal tiling error (%d x %d)", Co, Ci);
   if ((long long)(Ci > Co ? Ci : Co) * S * 4 > 0x7fffffffLL)
     return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_wgrad_b16: a sample exceeds the 32-bit row offsets");
-  const int ns = dyn_wgrad_b16_slices(p, B);
+  const int ns = wg::dyn_b16_slices(p, B);
   if (n_slices < ns) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_wgrad_b16: dW_b holds %d copies, %d needed (eat_pw_dyn_wgrad_b16_slices)", n_slices, ns);
-  p.upb = (p.sps + ns - 1) / ns;                                       // ns k-slices per sample
-  p.nz = (unsigned)(B * ns);
   hipStream_t hs = (hipStream_t)stream;
-  const size_t smem = (size_t)(p.w.ptr / 8 + p.w.qtr / 8) * 2 * 1024;
-  dim3 grid(p.w.ptn, p.w.qtn, p.nz);
-  const float* fdz = reinterpret_cast<const float*>(dz);
-  const float* fx = reinterpret_cast<const float*>(x);
-#define EAT_WIDE16D(SW_)                                                                                                  \
-  do {                                                                                                                    \
-    auto kern = pw_wgrad_wide_kernel<1, SW_, false, false, true, false>;                                                  \
-    static bool attr_set = false;                                                                                         \
-    if (!attr_set) {                                                                                                      \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-        return eat::fail(EAT_ELAUNCH, "eat_pw_conv_dyn_wgrad_b16: hipFuncSetAttribute(160 KB of LDS) failed");            \
-      attr_set = true;                                                                                                    \
-    }                                                                                                                     \
-    hipLaunchKernelGGL(kern, grid, dim3(512), smem, hs, fdz, fx, (const float*)nullptr, dW_b, B, Co, Ci, S, p.sps, p.upb,  \
-                       p.w.ptr, p.w.qtr, (const float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr, 0, ns);  \
-  } while (0)
-#define EAT_WIDE32D(SW_)                                                                                                  \
-  do {                                                                                                                    \
-    auto kern = pw_wgrad_wide_kernel<3, SW_, false, false>;                                                               \
-    static bool attr_set = false;                                                                                         \
-    if (!attr_set) {                                                                                                      \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-        return eat::fail(EAT_ELAUNCH, "eat_pw_conv_dyn_wgrad_b16: hipFuncSetAttribute(160 KB of LDS) failed");            \
-      attr_set = true;                                                                                                    \
-    }                                                                                                                     \
-    hipLaunchKernelGGL(kern, grid, dim3(512), smem, hs, fdz, fx, (const float*)nullptr, dW_b, B, Co, Ci, S, p.sps, p.upb,  \
-                       p.w.ptr, p.w.qtr, (const float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr, 0, ns);  \
-  } while (0)
-  if (f32) { if (p.w.swap) EAT_WIDE32D(true); else EAT_WIDE32D(false); }
-  else if (!x_b16) EAT_WIDE16D(false); else EAT_WIDE16D(true);
-#undef EAT_WIDE16D
-#undef EAT_WIDE32D
+  WideArgs a{"eat_pw_conv_dyn_wgrad_b16", hs, reinterpret_cast<const float*>(dz), reinterpret_cast<const float*>(x), nullptr,
+             dW_b, B, Co, Ci, S, p.sps, (p.sps + ns - 1) / ns, (unsigned)(B * ns), p.w};   // ns k-slices per sample
+  a.ps_ns = ns;
+  const int rc = f32 ? launch_wide_sw_sc<3>(a) : launch_wide_sw_sc<1, true>(a);
+  if (rc != EAT_OK) return rc;
   if (ns > 1) {                                                        // copy 0 (B, Co, Ci) += copies 1 .. ns - 1, fixed order
     const long long n = (long long)B * Co * Ci;
     if (n > 0x7fffffffLL) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_wgrad_b16: B*Co*Ci exceeds the 32-bit index of the slice reduction");
@@ -1382,9 +1180,10 @@ extern "C" int eat_pw_conv_dyn_wgrad_b16(const void* dz, int dz_b16, const void*
   return eat::check_launch("eat_pw_conv_dyn_wgrad_b16");
 }
 
-// 1 where eat_pw_conv_dyn_wgrad adds into dW_b (the caller zero-fills it), 0 where it stores.  Host helper.
+// 1 where eat_pw_conv_dyn_wgrad adds into dW_b (the caller zero-fills it), 0 where it stores.  Host helper.  (The plan of ONE
+// sample: the batch size moves only the streaming kernel's blocks per sample, never the choice of kernel.)
 extern "C" int eat_pw_dyn_wgrad_accumulates(int Co, int Ci, int S) {
-  return wgrad_plan(1, Co, Ci, S, 1, 0, false, false).kind == 1 ? 0 : 1;
+  return wg::plan(wg_req(1, Co, Ci, S, true, 0, false, false, wg::Xf::none, 0)).p.kind == 1 ? 0 : 1;
 }
 
 // Centred Gram matrix Gc = sum (x - m)(x - m)^T, m = sx * inv_n (see include/eat_hip.h): both operands are centred on

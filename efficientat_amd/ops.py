@@ -548,6 +548,25 @@ def pw_conv_cat(x1, x2, wp, bias, Co, act, res=None):
     return y
 
 
+def _wgrad_ws(B, Co, Ci, S, mode, same, x_scale, tf, reproducible):
+    """Workspace of `eat_pw_conv_wgrad_ws` / `_tf` / `eat_gram_centered`: (copies of dW, zero-filled?), (0, False) = none.
+    The stored-slice (wide-tile) kernel wants one copy per k-slice and writes every element of them: no zero fill.  The atomic
+    kernels add into their copies: `reproducible` asks for one zeroed copy per block (`eat_pw_wgrad_slots`); otherwise the
+    streaming kernel of the small matrices spreads its atomics over 8 zeroed copies (same-address atomics serialise in L2) and
+    the other kernels take none."""
+    h = _lib.lib()
+    if not reproducible and Co <= 64 and Ci <= 64 and S % 4 == 0 and mode != 1:
+        return 8, True
+    stored = tf is None and h.eat_pw_wgrad_kernel_kind(B, Co, Ci, S, mode, 1 if same else 0, 1 if x_scale else 0, 0) == 3
+    if reproducible or stored:
+        return int(h.eat_pw_wgrad_slots(B, Co, Ci, S, mode, 1 if same else 0)), not stored
+    return 0, False
+
+
+def _ws_alloc(n_floats, zeroed, dev):
+    return zero_arena.zeros((n_floats,), torch.float32, dev) if zeroed else torch.empty((n_floats,), dtype=torch.float32, device=dev)
+
+
 def gram(x, exact=False, sx=None, plain_bf16=False):
     """G (C, C) = sum_{b,s} x x^T, bit-reproducible from run to run: every block of the weight-gradient kernel adds into
     its own zeroed copy and the copies are summed in a fixed order (the BatchNorm statistics of the expand conv follow
@@ -560,27 +579,24 @@ def gram(x, exact=False, sx=None, plain_bf16=False):
     S = x.numel() // (B * C)
     mode = 1 if exact else (2 if plain_bf16 else 0)
     # (64 < C <= 160: the wide-tile kernel STORES its per-slice copies - no zero fill needed for them)
-    stored = _lib.lib().eat_pw_wgrad_kernel_kind(B, C, C, S, mode, 1, 0, 0) == 3
-    if sx is not None:
-        slots = int(_lib.lib().eat_pw_wgrad_slots(B, C, C, S, mode, 1))
-        G = zero_arena.zeros((C, C), torch.float32, x.device)
-        n_ws = 2 * C + slots * C * C
-        ws = torch.empty((n_ws,), dtype=torch.float32, device=x.device) if stored else zero_arena.zeros((n_ws,), torch.float32, x.device)
+    slots, zeroed = _wgrad_ws(B, C, C, S, mode, True, False, None, reproducible=True)
+    G = zero_arena.zeros((C, C), torch.float32, x.device)
+    if sx is not None:                                      # (the workspace holds the 2 C centring coefficients first)
+        ws = _ws_alloc(2 * C + slots * C * C, zeroed, x.device)
         _lib.call("eat_gram_centered", _dev(x, "x"), _dev(sx, "sx"), 1.0 / (B * S), G.data_ptr(), ws.data_ptr(), slots, B, C,
                   S, mode, _stream())
-        return G
-    slots = int(_lib.lib().eat_pw_wgrad_slots(B, C, C, S, mode, 1))
-    G = zero_arena.zeros((C, C), torch.float32, x.device)
-    ws = torch.empty((slots, C, C), dtype=torch.float32, device=x.device) if stored else zero_arena.zeros((slots, C, C), torch.float32, x.device)
-    _lib.call("eat_pw_conv_wgrad_ws", _dev(x, "x"), _dev(x, "x"), None, G.data_ptr(), ws.data_ptr(), slots, B, C, C, S, mode,
-              _stream())
+    else:
+        ws = _ws_alloc(slots * C * C, zeroed, x.device)
+        _lib.call("eat_pw_conv_wgrad_ws", _dev(x, "x"), _dev(x, "x"), None, G.data_ptr(), ws.data_ptr(), slots, B, C, C, S,
+                  mode, _stream())
     return G
 
 
 def pw_conv_wgrad(dz, x, x_scale=None, exact=None, tf=None, out=None):
     """dW (Co, Ci) = sum_b dz[b] (Co,S) . (x[b] * x_scale[b])^T.  exact=True: fp32 MFMA kernel; False: split-operand
     bf16x3 kernel (fp32-class); None: follow the active `precision` context ('fp32' -> exact, 'bf16' -> plain bf16
-    operands with fp32 accumulation, as autocast does to the conv weight gradient; otherwise bf16x3)."""
+    operands with fp32 accumulation, as autocast does to the conv weight gradient; otherwise bf16x3).
+    tf = (a, b, act): the x operand is act(a[ci] x + b[ci]), evaluated on load (`eat_pw_conv_wgrad_tf`)."""
     mode = 1 if exact else 0
     if exact is None:
         mode = {"fp32": 1, "bf16": 2}.get(precision.mode, 0)
@@ -589,29 +605,18 @@ def pw_conv_wgrad(dz, x, x_scale=None, exact=None, tf=None, out=None):
     S = dz.numel() // (B * Co)
     # out: ZERO-FILLED (Co, Ci) memory to accumulate into (dp.GradReducer.alloc: the gradient is produced inside its bucket)
     dW = out if out is not None else zero_arena.zeros((Co, Ci), torch.float32, dz.device)
+    n, zeroed = _wgrad_ws(B, Co, Ci, S, mode, dz.data_ptr() == x.data_ptr(), x_scale is not None, tf, reproducible=False)
+    ws = _ws_alloc(n * Co * Ci, zeroed, dz.device) if n else None
     if tf is not None:
-        ws = zero_arena.zeros((8, Co, Ci), torch.float32, dz.device) if (Co <= 64 and Ci <= 64 and S % 4 == 0 and mode != 1) else None
         _lib.call("eat_pw_conv_wgrad_tf", _dev(dz, "dz"), _dev(x, "x"), tf[0].data_ptr(), tf[1].data_ptr(), tf[2],
-                  _opt(x_scale, "x_scale"), dW.data_ptr(), None if ws is None else ws.data_ptr(), 0 if ws is None else 8,
-                  B, Co, Ci, S, mode, _stream())
-        return dW
-    if Co <= 64 and Ci <= 64 and S % 4 == 0 and mode != 1:
-        # small matrices, long reductions: the streaming kernel spreads its atomics over 8 copies of dW (csrc/train.hip)
-        ws = zero_arena.zeros((8, Co, Ci), torch.float32, dz.device)
-        _lib.call("eat_pw_conv_wgrad_ws", _dev(dz, "dz"), _dev(x, "x"), _opt(x_scale, "x_scale"), dW.data_ptr(),
-                  ws.data_ptr(), 8, B, Co, Ci, S, mode, _stream())
-        return dW
-    h = _lib.lib()
-    if h.eat_pw_wgrad_kernel_kind(B, Co, Ci, S, mode, 1 if dz.data_ptr() == x.data_ptr() else 0, 0 if x_scale is None else 1, 0) == 3:
-        # late-layer shapes: the wide-tile kernel stores one copy of dW per k-slice (no atomics, bit-reproducible); the copies
-        # need no zero fill
-        n = int(h.eat_pw_wgrad_slots(B, Co, Ci, S, mode, 0))
-        ws = torch.empty((n, Co, Ci), device=dz.device, dtype=torch.float32)
+                  _opt(x_scale, "x_scale"), dW.data_ptr(), None if ws is None else ws.data_ptr(), n, B, Co, Ci, S, mode,
+                  _stream())
+    elif ws is not None:
         _lib.call("eat_pw_conv_wgrad_ws", _dev(dz, "dz"), _dev(x, "x"), _opt(x_scale, "x_scale"), dW.data_ptr(),
                   ws.data_ptr(), n, B, Co, Ci, S, mode, _stream())
-        return dW
-    _lib.call("eat_pw_conv_wgrad", _dev(dz, "dz"), _dev(x, "x"), _opt(x_scale, "x_scale"), dW.data_ptr(), B, Co, Ci,
-              S, mode, _stream())
+    else:
+        _lib.call("eat_pw_conv_wgrad", _dev(dz, "dz"), _dev(x, "x"), _opt(x_scale, "x_scale"), dW.data_ptr(), B, Co, Ci,
+                  S, mode, _stream())
     return dW
 
 

@@ -219,6 +219,33 @@ def test_pw_wgrad_wide_tile_random_shapes(B, Co, Ci, S, sc):
     assert torch.equal(got, again)
 
 
+@pytest.mark.parametrize("B,Co,Ci,S", [(2, 96, 64, 64), (3, 96, 64, 512)])      # the smallest wide-tile shape (1 copy); 3 copies
+def test_pw_wgrad_ws_refuses_a_workspace_one_copy_short(B, Co, Ci, S):
+    """eat_pw_conv_wgrad_ws where the plan is the stored-slice (wide-tile) kernel: with one copy fewer than eat_pw_wgrad_slots
+    says it returns EAT_EINVAL, names the count and leaves dW bit for bit as it was (the fallback kernels would add into the
+    caller's uninitialised copies); with exactly that many uninitialised copies it matches fp64."""
+    from efficientat_amd import _lib
+    h = _lib.lib()
+    assert h.eat_pw_wgrad_kernel_kind(B, Co, Ci, S, 0, 0, 0, 0) == 3
+    n = h.eat_pw_wgrad_slots(B, Co, Ci, S, 0, 0)
+    dz, x = _rand(B, Co, S, 1, seed=1), _rand(B, Ci, S, 1, seed=2)
+    ref = torch.einsum("bos,bis->oi", dz[..., 0].double(), x[..., 0].double())
+    dzd, xd = dz.to(DEV), x.to(DEV)
+    pattern = (torch.arange(Co * Ci, dtype=torch.float32) * 0.37 - 11.0).reshape(Co, Ci)
+    dW = pattern.to(DEV)
+    ws = torch.full((n, Co, Ci), float("nan"), device=DEV)
+    args = (dzd.data_ptr(), xd.data_ptr(), None, dW.data_ptr(), ws.data_ptr())
+    rc = h.eat_pw_conv_wgrad_ws(*args, n - 1, B, Co, Ci, S, 0, torch.cuda.current_stream().cuda_stream)
+    assert rc == -1                                                    # EAT_EINVAL
+    msg = h.eat_last_error_string().decode()
+    assert f"workspace of {n - 1} copies" in msg and f"needs {n} " in msg, msg
+    torch.cuda.synchronize()
+    assert torch.equal(dW.cpu().view(torch.int32), pattern.view(torch.int32))
+    dW.zero_()
+    _lib.call("eat_pw_conv_wgrad_ws", *args, n, B, Co, Ci, S, 0, torch.cuda.current_stream().cuda_stream)
+    assert _rel(dW, ref) < 2e-5
+
+
 # SURVEY 8(c): whole-network gradients at rel-L2 <= 1e-2 per tensor.  What stands in the way is not arithmetic but activation
 # kinks: ONE element crossing ReLU's 0 / Hardswish's +-3 between two evaluations moves every tensor upstream through the
 # BatchNorm mean terms - a BatchNorm scale / shift or the conv in front of it in the first 7 blocks, whose gradient is a sum
