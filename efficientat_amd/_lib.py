@@ -1,4 +1,4 @@
-"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h).
+"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h and include/eat_tag.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EAT_LIB") or os.path.join(_HERE, "libeat_hip.so")
 # the one declaration of the C ABI: the ctypes signatures below are parsed from it
 HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_hip.h")
+# the long-recording tagger's entry points (efficientat_amd/tagger.py): same library, same conventions, their own header
+TAG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_tag.h")
 
 
 class EatHipError(RuntimeError):
@@ -61,6 +63,8 @@ def parse_prototypes(text):
 with open(HEADER_PATH) as _f:
     PROTOTYPES = parse_prototypes(_f.read())                           # every entry point the header declares
 SIGNATURES = {name: args for name, (_, args) in PROTOTYPES.items()}    # name -> argtypes
+with open(TAG_HEADER_PATH) as _f:
+    TAG_PROTOTYPES = parse_prototypes(_f.read())                       # bound by lib() as well; not part of PROTOTYPES
 
 _lib = None
 
@@ -74,7 +78,7 @@ def lib():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU/PyTorch fallback). "
                 "Build it with `python -m efficientat_amd.build`.")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -24,6 +24,7 @@
 //     aligned to even bins) and walks only as many pairs as the widest band of the lane group
 //     needs (low mel filters are 2-6 bins wide, the top ones 24): ~35 instead of 96 LDS reads.
 #include "eat_common.h"
+#include "../../include/eat_tag.h"
 
 namespace {
 
@@ -69,11 +70,19 @@ __device__ __forceinline__ float lane_read(float v, int src_lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
 }
 
+// kWindows selects the sample source of row b = blockIdx.y:
+//   false  row b of the contiguous (B, L) batch `wave` (eat_mel_fwd; the descriptor arguments are unused);
+//   true   the L samples from wave[win_start[b]] of a flat buffer of n_wave samples, of which the first win_valid[b] are
+//          read and the rest are 0.0 (eat_mel_windows_fwd; no masks).  The descriptors are clamped to the buffer here,
+//          so no descriptor makes the kernel read outside [wave, wave + n_wave).
+// Both sources feed the same explicitly rounded arithmetic, so a window gives the bits of the same samples as a row.
+template <bool kWindows>
 __global__ __launch_bounds__(256) void mel_fwd_kernel(
     const float* __restrict__ wave, int L, const float* __restrict__ window, int win_length, int hop,
     const float2* __restrict__ twiddle, const float2* __restrict__ band_w2,
     const int* __restrict__ band_start, const int* __restrict__ band_cnt, int n_mels, int band_pairs,
-    float* __restrict__ out, int T, int mf0, int mf1, int mt0, int mt1) {
+    float* __restrict__ out, int T, int mf0, int mf1, int mt0, int mt1,
+    long long n_wave, const long long* __restrict__ win_start, const int* __restrict__ win_valid) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* s_buf = reinterpret_cast<float2*>(smem);                         // [4][512]  swizzled exchange buffers
   float2* s_bw = s_buf + kWavesPerBlock * kHalf;                           // [band_pairs][n_mels] weight pairs
@@ -109,6 +118,13 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(
   __syncthreads();
 
   const float* x = wave + (size_t)b * L;
+  int valid = L;         // a window: its samples that exist in memory, x[valid .. L) reads as 0.0
+  if constexpr (kWindows) {
+    const long long s0 = win_start[b];
+    const long long room = s0 < 0 ? 0 : n_wave - s0;
+    valid = static_cast<int>(min(static_cast<long long>(max(min(win_valid[b], L), 0)), max(room, 0LL)));
+    x = wave + (valid > 0 ? s0 : 0);
+  }
   const int Lp = L - 1;  // length of the pre-emphasised signal
   float2* buf = s_buf + wv * kHalf;
   float* pw = reinterpret_cast<float*>(buf);     // power spectrum aliases the wave's FFT buffer
@@ -122,7 +138,8 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(
   const int x_odd = static_cast<int>(reinterpret_cast<size_t>(x) >> 2) & 1;   // x sits on an odd 4-byte word
   auto load_frame = [&](int t, float (&raw)[8][3]) -> bool {
     const int q0 = t * hop - kNfft / 2;        // padded-signal origin of this frame, in pre[] indices
-    if (q0 >= 0 && q0 + kNfft <= Lp && ((q0 + x_odd) & 1) == 0) {
+    // reads x[q0 .. q0 + kNfft]: inside the row and, of a window, below `valid`
+    if (q0 >= 0 && q0 + kNfft <= Lp && (!kWindows || q0 + kNfft < valid) && ((q0 + x_odd) & 1) == 0) {
       const float* xf = x + q0 + 2 * lane;
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
@@ -140,7 +157,12 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(
         j = j < 0 ? -j : j;
         j = j >= Lp ? 2 * (Lp - 1) - j : j;
         j = j < 0 ? 0 : (j > Lp - 1 ? Lp - 1 : j);   // only reachable where the window is zero
-        pv[e] = __fsub_rn(x[j + 1], __fmul_rn(0.97f, x[j]));
+        if constexpr (kWindows) {
+          const float x0 = j < valid ? x[j] : 0.0f, x1 = j + 1 < valid ? x[j + 1] : 0.0f;
+          pv[e] = __fsub_rn(x1, __fmul_rn(0.97f, x0));
+        } else {
+          pv[e] = __fsub_rn(x[j + 1], __fmul_rn(0.97f, x[j]));
+        }
       }
       raw[r][0] = pv[0]; raw[r][1] = pv[1]; raw[r][2] = 0.0f;
     }
@@ -238,7 +260,7 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(
             acc = fmaf(w.y, p.y, fmaf(w.x, p.x, acc));
           }
           float v = logf(acc + 0.00001f);
-          if ((m >= mf0 && m < mf1) || (t >= mt0 && t < mt1)) v = 0.0f;
+          if (!kWindows && ((m >= mf0 && m < mf1) || (t >= mt0 && t < mt1))) v = 0.0f;
           if (m < n_mels) s_out[m * (kFramesPerBlock + 1) + fl] = (v + 4.5f) / 5.0f;
         }
       }
@@ -255,30 +277,50 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(
   }
 }
 
+// The checks and the launch shared by the two entry points (`who` names the entry point in the messages).
+template <bool kWindows>
+int mel_launch(const char* who, const float* wave, long long n_wave, const long long* win_start, const int* win_valid,
+               int B, int L, const float* window, int win_length, int n_fft, int hop, const float* twiddle,
+               const float* band_w2, const int* band_start, const int* band_cnt, int n_mels, int band_pairs, float* out,
+               int T, int mask_f0, int mask_f1, int mask_t0, int mask_t1, eat_stream_t stream) {
+  eat::clear_stale_error();
+  if (n_fft != kNfft) return eat::fail(EAT_EINVAL, "%s: only n_fft=1024 is implemented (got %d)", who, n_fft);
+  if (win_length < 1 || win_length > n_fft || hop < 1 || B < 1 || n_mels < 1 || band_pairs < 1)
+    return eat::fail(EAT_EINVAL, "%s: bad geometry", who);
+  if (kWindows && (B > 65535 || n_wave < 0))
+    return eat::fail(EAT_EINVAL, "%s: N=%d windows in one call (at most 65535), n_wave=%lld", who, B, n_wave);
+  if (n_mels > 64 * kMaxRounds) return eat::fail(EAT_EINVAL, "%s: n_mels=%d > %d", who, n_mels, 64 * kMaxRounds);
+  if (L - 1 <= n_fft / 2) return eat::fail(EAT_EINVAL, "%s: clip too short for reflect padding (L=%d)", who, L);
+  if (T != 1 + (L - 1) / hop) return eat::fail(EAT_EINVAL, "%s: T=%d does not match L=%d hop=%d", who, T, L, hop);
+  size_t smem = sizeof(float2) * (kWavesPerBlock * kHalf + (size_t)band_pairs * n_mels + 7 * 8 + 7 * 64) + sizeof(float) * kNfft +
+                sizeof(int) * n_mels + sizeof(float) * (size_t)n_mels * (kFramesPerBlock + 1);
+  if (smem > 160 * 1024) return eat::fail(EAT_EINVAL, "%s: mel table too large for LDS (%zu B)", who, smem);
+  if (smem > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mel_fwd_kernel<kWindows>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return eat::fail(EAT_ELAUNCH, "%s: cannot reserve %zu B of LDS: %s", who, smem, hipGetErrorString(e));
+  }
+  dim3 grid((T + kFramesPerBlock * kGroupsPerBlock - 1) / (kFramesPerBlock * kGroupsPerBlock), B);
+  hipLaunchKernelGGL(mel_fwd_kernel<kWindows>, grid, dim3(256), smem, (hipStream_t)stream, wave, L, window, win_length,
+                     hop, reinterpret_cast<const float2*>(twiddle), reinterpret_cast<const float2*>(band_w2), band_start,
+                     band_cnt, n_mels, band_pairs, out, T, mask_f0, mask_f1, mask_t0, mask_t1, n_wave, win_start, win_valid);
+  return eat::check_launch(who);
+}
+
 }  // namespace
 
 extern "C" int eat_mel_fwd(const float* wave, int B, int L, const float* window, int win_length,
                            int n_fft, int hop, const float* twiddle, const float* band_w2,
                            const int* band_start, const int* band_cnt, int n_mels, int band_pairs, float* out,
                            int T, int mask_f0, int mask_f1, int mask_t0, int mask_t1, eat_stream_t stream) {
-  eat::clear_stale_error();
-  if (n_fft != kNfft) return eat::fail(EAT_EINVAL, "eat_mel_fwd: only n_fft=1024 is implemented (got %d)", n_fft);
-  if (win_length < 1 || win_length > n_fft || hop < 1 || B < 1 || n_mels < 1 || band_pairs < 1)
-    return eat::fail(EAT_EINVAL, "eat_mel_fwd: bad geometry");
-  if (n_mels > 64 * kMaxRounds) return eat::fail(EAT_EINVAL, "eat_mel_fwd: n_mels=%d > %d", n_mels, 64 * kMaxRounds);
-  if (L - 1 <= n_fft / 2) return eat::fail(EAT_EINVAL, "eat_mel_fwd: clip too short for reflect padding (L=%d)", L);
-  if (T != 1 + (L - 1) / hop) return eat::fail(EAT_EINVAL, "eat_mel_fwd: T=%d does not match L=%d hop=%d", T, L, hop);
-  size_t smem = sizeof(float2) * (kWavesPerBlock * kHalf + (size_t)band_pairs * n_mels + 7 * 8 + 7 * 64) + sizeof(float) * kNfft +
-                sizeof(int) * n_mels + sizeof(float) * (size_t)n_mels * (kFramesPerBlock + 1);
-  if (smem > 160 * 1024) return eat::fail(EAT_EINVAL, "eat_mel_fwd: mel table too large for LDS (%zu B)", smem);
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mel_fwd_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return eat::fail(EAT_ELAUNCH, "eat_mel_fwd: cannot reserve %zu B of LDS: %s", smem, hipGetErrorString(e));
-  }
-  dim3 grid((T + kFramesPerBlock * kGroupsPerBlock - 1) / (kFramesPerBlock * kGroupsPerBlock), B);
-  hipLaunchKernelGGL(mel_fwd_kernel, grid, dim3(256), smem, (hipStream_t)stream, wave, L, window, win_length,
-                     hop, reinterpret_cast<const float2*>(twiddle), reinterpret_cast<const float2*>(band_w2), band_start,
-                     band_cnt, n_mels, band_pairs, out, T, mask_f0, mask_f1, mask_t0, mask_t1);
-  return eat::check_launch("eat_mel_fwd");
+  return mel_launch<false>("eat_mel_fwd", wave, 0, nullptr, nullptr, B, L, window, win_length, n_fft, hop, twiddle, band_w2,
+                           band_start, band_cnt, n_mels, band_pairs, out, T, mask_f0, mask_f1, mask_t0, mask_t1, stream);
+}
+
+extern "C" int eat_mel_windows_fwd(const float* wave, long long n_wave, const long long* win_start, const int* win_valid,
+                                   int N, int L, const float* window, int win_length, int n_fft, int hop,
+                                   const float* twiddle, const float* band_w2, const int* band_start, const int* band_cnt,
+                                   int n_mels, int band_pairs, float* out, int T, eat_stream_t stream) {
+  return mel_launch<true>("eat_mel_windows_fwd", wave, n_wave, win_start, win_valid, N, L, window, win_length, n_fft, hop,
+                          twiddle, band_w2, band_start, band_cnt, n_mels, band_pairs, out, T, 0, 0, 0, 0, stream);
 }

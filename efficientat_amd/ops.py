@@ -1939,3 +1939,81 @@ def freq_mixstyle(x, perm, lam, apply=None, out=None, stats=None, eps=1e-6):
     _lib.call("eat_freq_mixstyle", _dev(x, "x"), _dev_int32(perm, "perm", B), _dev(lam, "lam"), _dev_int32(apply, "apply", 1),
               _dev(out, "out"), _dev(stats, "stats"), B, C, F, T, float(eps), _stream())
     return out
+
+
+# ------------------------------------------------------------------ long-recording tagger (include/eat_tag.h)
+def check_windows(win_start, win_valid, L, n_wave):
+    """Host-side validation of a window table of `mel_windows` (CPU arrays): 0 <= valid <= L, start >= 0 and
+    start + valid <= n_wave -> (start int64, valid int32) CPU tensors."""
+    start = torch.as_tensor(win_start, dtype=torch.int64).reshape(-1)
+    valid = torch.as_tensor(win_valid, dtype=torch.int64).reshape(-1)
+    if start.numel() < 1 or start.numel() != valid.numel():
+        raise _lib.EatHipError(f"mel_windows: need one (start, valid) pair per window (got {start.numel()} starts, {valid.numel()} valids)")
+    if bool(((valid < 0) | (valid > L)).any()):
+        raise _lib.EatHipError(f"mel_windows: a window's valid length lies outside [0, {L}]")
+    if bool((start < 0).any()) or bool((start + valid > n_wave).any()):
+        raise _lib.EatHipError(f"mel_windows: a window reads outside the waveform buffer of {n_wave} samples")
+    return start.contiguous(), valid.to(torch.int32).contiguous()
+
+
+def mel_windows(wave, win_start, win_valid, L, window, twiddle, band_w2, band_start, band_cnt, n_fft, hop, n_mels, out=None):
+    """Log-mel of N windows of the flat waveform buffer `wave` (n_wave) -> out (N, n_mels, T): window w is wave[start[w] :
+    start[w] + L] with positions >= valid[w] read as 0.0; the bits of `mel_fwd` on the materialised windows.  CPU
+    descriptor arrays are validated here (`check_windows`) and uploaded; device tensors (slices of a table that was
+    validated before it was uploaded) must be int64 / int32.  At most 65535 windows per call."""
+    if wave.dim() != 1:
+        raise _lib.EatHipError(f"mel_windows: wave must be a flat (n_wave) buffer, got {tuple(wave.shape)}")
+    dev = wave.device
+    if not (torch.is_tensor(win_start) and win_start.is_cuda and torch.is_tensor(win_valid) and win_valid.is_cuda):
+        win_start, win_valid = (t.to(dev) for t in check_windows(win_start, win_valid, L, wave.numel()))
+    N = win_start.numel()
+    if (win_start.dtype != torch.int64 or not win_start.is_contiguous() or win_start.device != dev
+            or win_valid.numel() != N):
+        raise _lib.EatHipError("mel_windows: win_start must be a contiguous int64 tensor of N values on the wave's device")
+    if band_w2.shape[1:] != (n_mels, 2) or band_start.numel() != n_mels or band_cnt.numel() != n_mels:
+        raise _lib.EatHipError("mel_windows: band table must be (pairs, n_mels, 2) with n_mels starts / counts")
+    T = 1 + (L - 1) // hop
+    if out is None:
+        out = torch.empty((N, n_mels, T), device=dev, dtype=torch.float32)
+    elif out.numel() != N * n_mels * T or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.EatHipError(f"mel_windows: out must be a contiguous fp32 buffer of {N} x {n_mels} x {T} elements")
+    _lib.call("eat_mel_windows_fwd", _dev(wave, "wave"), wave.numel(), win_start.data_ptr(), _dev_int32(win_valid, "win_valid", N),
+              N, L, _dev(window, "window"), window.numel(), n_fft, hop, _dev(twiddle, "twiddle"), _dev(band_w2, "band_w2"),
+              band_start.data_ptr(), band_cnt.data_ptr(), n_mels, band_w2.shape[0], out.data_ptr(), T, _stream())
+    return out
+
+
+def tag_topk(logits, k, return_probs=False):
+    """sigmoid + per-row top-k of (N, C) logits -> (prob (N, k) fp32, index (N, k) int32[, probs (N, C)]): descending
+    probability, equal probabilities by ascending class index.  1 <= k <= min(C, 64)."""
+    if logits.dim() != 2:
+        raise _lib.EatHipError(f"tag_topk: logits must be (N, C), got {tuple(logits.shape)}")
+    N, C = logits.shape
+    prob = torch.empty((N, k), device=logits.device, dtype=torch.float32)
+    index = torch.empty((N, k), device=logits.device, dtype=torch.int32)
+    probs = torch.empty((N, C), device=logits.device, dtype=torch.float32) if return_probs else None
+    _lib.call("eat_tag_topk", _dev(logits, "x"), N, C, k, prob.data_ptr(), index.data_ptr(), _opt(probs, "probs"), _stream())
+    return (prob, index, probs) if return_probs else (prob, index)
+
+
+def resampled_length(n_in, up, down):
+    """ceil(n_in up / down): the output length of `resample_mono` (and of scipy.signal.resample_poly)."""
+    return -(-int(n_in) * int(up) // int(down))
+
+
+def resample_mono(frames, up, down, taps):
+    """Interleaved (n_in, channels) or (n_in,) frames, int16 (scaled by 1 / 32768) or float32, on the GPU -> the mono
+    waveform resampled by up / down with the FIR `taps` (tagger.resample_plan), (ceil(n_in up / down)) fp32."""
+    if frames.dim() not in (1, 2) or frames.dtype not in (torch.int16, torch.float32) or not frames.is_cuda \
+            or not frames.is_contiguous():
+        raise _lib.EatHipError(f"resample_mono: frames must be a contiguous int16 / float32 GPU tensor (n_in,) or (n_in, channels) "
+                               f"(got {frames.dtype}, {tuple(frames.shape)}, on {frames.device})")
+    if frames.device.index != torch.cuda.current_device():
+        raise _lib.EatHipError(f"resample_mono: frames live on {frames.device} but the current device is cuda:{torch.cuda.current_device()}")
+    n_in = frames.shape[0]
+    channels = frames.shape[1] if frames.dim() == 2 else 1
+    n_out = resampled_length(n_in, up, down)
+    out = torch.empty(max(n_out, 0), device=frames.device, dtype=torch.float32)
+    _lib.call("eat_resample_mono", frames.data_ptr(), 1 if frames.dtype == torch.int16 else 0, n_in, channels, int(up), int(down),
+              _dev(taps, "taps"), taps.numel(), out.data_ptr(), n_out, _stream())
+    return out

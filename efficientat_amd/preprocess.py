@@ -140,6 +140,19 @@ class AugmentMelSTFT(nn.Module):
         return ops.mel_fwd(x, self.window, self._twiddle, band_w2, band_start, band_cnt, self.n_fft, self.hopsize,
                            self.n_mels, fmask, tmask, out=out)
 
+    def forward_windows(self, wave, win_start, win_valid, L, out=None):
+        """Log-mel of N windows of a flat waveform buffer `wave` (n_wave) -> (N, n_mels, T): window w is the L samples from
+        wave[win_start[w]], of which those at and beyond win_valid[w] read as 0.0 - the slices of a zero-padded waveform
+        that windowed_inference.py:96-104 passes to forward() one at a time, with the same bits as forward() gives on them.
+        Evaluation only, on the eval tables (fmin, fmax).  Deviation from the reference loop: nothing is drawn from the host
+        RNG (forward() draws two integers per call that eval ignores; at 1e5 windows the draws alone would take seconds).
+        Descriptors: CPU arrays (validated here), or device tensors as `ops.mel_windows` takes them."""
+        if self.training:
+            raise RuntimeError("AugmentMelSTFT.forward_windows is evaluation only: call .eval() first")
+        band_w2, band_start, band_cnt = self._device_tables(self.fmin, self.fmax, wave.device)
+        return ops.mel_windows(wave, win_start, win_valid, L, self.window, self._twiddle, band_w2, band_start, band_cnt,
+                               self.n_fft, self.hopsize, self.n_mels, out=out)
+
     # -- graph mode: the mel basis as an INPUT BUFFER of a captured step (train_loop.GraphedKDTrainer) -------------------
     def max_band_pairs(self):
         """Pairs of the widest band over every (fmin, fmax) the train-mode jitter can draw: the band of the top filter
