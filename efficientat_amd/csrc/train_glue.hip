@@ -208,6 +208,7 @@ extern "C" int eat_calib_copy(const float* src, float* dst, long long n, int mod
 extern "C" int eat_mixup_fwd(const float* x, const int* perm, const float* lam, float* out, int B, int n,
                              eat_stream_t stream) {
   eat::clear_stale_error();
+  if (!x || !perm || !lam || !out) return eat::fail(EAT_EINVAL, "eat_mixup_fwd: x, perm, lam and out must not be NULL");
   if (B < 1 || n < 1) return eat::fail(EAT_EINVAL, "eat_mixup_fwd: bad shape");
   hipStream_t s = (hipStream_t)stream;
   if ((n & 3) == 0) {
@@ -242,6 +243,8 @@ extern "C" int eat_kd_loss_fwd_bwd(const float* logits, const float* y, const in
                                    const float* teacher, const long long* teacher_idx, int n_teacher, float kd_lambda,
                                    int B, int C, float* sums, float* dlogits, eat_stream_t stream) {
   eat::clear_stale_error();
+  if (!logits || !y || !sums || !dlogits)
+    return eat::fail(EAT_EINVAL, "eat_kd_loss_fwd_bwd: logits, y, sums and dlogits must not be NULL");
   if (B < 1 || C < 1) return eat::fail(EAT_EINVAL, "eat_kd_loss_fwd_bwd: bad shape");
   if ((perm == nullptr) != (lam == nullptr)) return eat::fail(EAT_EINVAL, "eat_kd_loss_fwd_bwd: perm and lam go together");
   if (teacher && (!teacher_idx || n_teacher < 1)) return eat::fail(EAT_EINVAL, "eat_kd_loss_fwd_bwd: teacher needs its index");

@@ -1675,11 +1675,44 @@ def col_sum(m):
     return out
 
 
+def _glue_operand(t, name, dtype, like, n=None, at_least=None):
+    """Metadata check (no sync, no value read) of an operand whose pointer goes straight to a glue kernel: dtype, contiguity,
+    element count and the device of the main operand `like`.  Runs before the residency check of `like`, so a refusal does
+    not need a GPU."""
+    want = f"a contiguous {str(dtype).replace('torch.', '')} tensor" + (f" of {n} elements" if n is not None else "") + \
+        (f" of at least {at_least} elements" if at_least is not None else "")
+    if not isinstance(t, torch.Tensor):
+        raise _lib.EatHipError(f"{name} must be {want} (got {type(t).__name__})")
+    if t.dtype != dtype or not t.is_contiguous() or (n is not None and t.numel() != n) or \
+            (at_least is not None and t.numel() < at_least):
+        raise _lib.EatHipError(f"{name} must be {want} (got {t.dtype}, {tuple(t.shape)}, contiguous={t.is_contiguous()})")
+    if t.device != like.device:
+        raise _lib.EatHipError(f"{name} must live on the device of its batch, {like.device} (got {t.device})")
+    return t.data_ptr()
+
+
+def _mix_operands(fn, perm, lam, B, like):
+    """-> (perm pointer, lam pointer) of a mix-up draw, (None, None) without one: perm (B) int32, lam (B) fp32."""
+    if (perm is None) != (lam is None):
+        raise _lib.EatHipError(f"{fn}: perm and lam go together")
+    if perm is None:
+        return None, None
+    return (_glue_operand(perm, f"{fn}: perm", torch.int32, like, n=B),
+            _glue_operand(lam, f"{fn}: lam", torch.float32, like, n=B))
+
+
 def mixup_fwd(x, perm, lam):
-    """x[b] * lam[b] + x[perm[b]] * (1 - lam[b]) over the flattened per-sample axis; perm int32 (B), lam fp32 (B)."""
+    """x[b] * lam[b] + x[perm[b]] * (1 - lam[b]) over the flattened per-sample axis; perm int32 (B), lam fp32 (B).  The
+    VALUES of perm (in [0, B)) are the caller's responsibility: the kernel gathers rows by them."""
+    if x.dim() < 1 or x.shape[0] < 1 or x.numel() < 1 or x.numel() % x.shape[0]:
+        raise _lib.EatHipError(f"mixup_fwd: x must be a non-empty (B, ...) batch, got {tuple(x.shape)}")
     B = x.shape[0]
+    if perm is None or lam is None:
+        raise _lib.EatHipError("mixup_fwd: perm and lam are both required")
+    p_perm, p_lam = _mix_operands("mixup_fwd", perm, lam, B, x)
+    p_x = _dev(x, "x")
     out = torch.empty_like(x)
-    _lib.call("eat_mixup_fwd", _dev(x, "x"), perm.data_ptr(), lam.data_ptr(), out.data_ptr(), B, x.numel() // B, _stream())
+    _lib.call("eat_mixup_fwd", p_x, p_perm, p_lam, out.data_ptr(), B, x.numel() // B, _stream())
     return out
 
 
@@ -1696,13 +1729,37 @@ def wave_i16_to_f32(src, out=None, scale=1.0 / 32768.0):
 
 
 def kd_loss_fwd_bwd(logits, y, perm, lam, teacher, teacher_idx, kd_lambda, sums):
-    """-> dlogits; accumulates (loss, label part, distillation part) into `sums` (3,) on the device."""
+    """-> dlogits; accumulates (loss, label part, distillation part) into `sums` (>= 3 fp32) on the device.  perm (B) int32 and
+    lam (B) fp32 come together or not at all; teacher (N, C) fp32 probabilities with teacher_idx (B) int64 (-1 = no entry).
+    Operand types and shapes are checked here from metadata; the index VALUES (perm in [0, B), teacher_idx in [-1, N)) are
+    the caller's responsibility - `KDTrainer` validates its table once on the host."""
+    fn = "kd_loss_fwd_bwd"
+    if logits.dim() != 2 or logits.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: logits must be a non-empty (B, C) matrix, got {tuple(logits.shape)}")
     B, C = logits.shape
+    if tuple(y.shape) != (B, C):
+        raise _lib.EatHipError(f"{fn}: y {tuple(y.shape)} does not match the logits {(B, C)}")
+    kd_lambda = float(kd_lambda)
+    if not 0.0 <= kd_lambda <= 1.0:
+        raise _lib.EatHipError(f"{fn}: kd_lambda must lie in [0, 1] (got {kd_lambda})")
+    p_perm, p_lam = _mix_operands(fn, perm, lam, B, logits)
+    p_teacher = p_tidx = None
+    n_teacher = 0
+    if teacher is not None:
+        if teacher.dim() != 2 or teacher.shape[0] < 1 or teacher.shape[1] != C:
+            raise _lib.EatHipError(f"{fn}: teacher must be (N >= 1, {C}) probabilities, got {tuple(teacher.shape)}")
+        _glue_operand(teacher, f"{fn}: teacher", torch.float32, logits)
+        if teacher_idx is None and kd_lambda < 1.0:
+            raise _lib.EatHipError(f"{fn}: teacher_idx is required with a teacher and kd_lambda < 1")
+    if teacher_idx is not None:
+        _glue_operand(teacher_idx, f"{fn}: teacher_idx", torch.int64, logits, n=B)
+    if teacher is not None and teacher_idx is not None:       # (kd_lambda = 1 without an index: the pure label loss)
+        p_teacher, p_tidx, n_teacher = teacher.data_ptr(), teacher_idx.data_ptr(), teacher.shape[0]
+    p_sums = _glue_operand(sums, f"{fn}: sums", torch.float32, logits, at_least=3)
+    p_logits, p_y = _dev(logits, "logits"), _dev(y, "y")
     dlogits = torch.empty_like(logits)
-    _lib.call("eat_kd_loss_fwd_bwd", _dev(logits, "logits"), _dev(y, "y"), None if perm is None else perm.data_ptr(),
-              None if lam is None else lam.data_ptr(), None if teacher is None else _dev(teacher, "teacher"),
-              None if teacher_idx is None else teacher_idx.data_ptr(), 0 if teacher is None else teacher.shape[0],
-              float(kd_lambda), B, C, sums.data_ptr(), dlogits.data_ptr(), _stream())
+    _lib.call("eat_kd_loss_fwd_bwd", p_logits, p_y, p_perm, p_lam, p_teacher, p_tidx, n_teacher, kd_lambda, B, C, p_sums,
+              dlogits.data_ptr(), _stream())
     return dlogits
 
 

@@ -669,7 +669,8 @@ int eat_col_sum(const float* m, float* out, int R, int C, eat_stream_t stream);
 int eat_calib_copy(const float* src, float* dst, long long n, int mode, eat_stream_t stream);
 
 /* Mix-up of a batch with itself (ex_audioset.py:142-148, helpers/utils.py:90-95): out[b] = x[b]*lam[b] + x[perm[b]]*(1-lam[b]);
- * x, out (B, n) fp32 (n = the flattened per-sample size), perm (B) int32, lam (B) fp32.  out must not alias x. */
+ * x, out (B, n) fp32 (n = the flattened per-sample size), perm (B) int32 with values in [0, B), lam (B) fp32.  out must
+ * not alias x.  A NULL x / perm / lam / out is EAT_EINVAL; the index VALUES are the caller's responsibility. */
 int eat_mixup_fwd(const float* x, const int* perm, const float* lam, float* out, int B, int n, eat_stream_t stream);
 
 /* 16-bit PCM transport of the waveforms (the reference moves fp32 clips with a blocking x.to(device),
@@ -685,7 +686,9 @@ int eat_wave_i16_to_f32(const short* src, float* dst, long long n, float scale, 
  * (sigmoid(teacher_logits / temperature), as the reference stores them), teacher_idx (B) int64 with -1 for files that
  * have no teacher entry (their KD term is zeroed; like the reference, row n_teacher-1 stands in for the lookup).
  * sums (3) fp32 += (loss, kd_lambda*label, (1-kd_lambda)*kd): accumulate over steps on the device, read once per epoch
- * (the reference syncs three scalars to the host every step, ex_audioset.py:192-194).  dlogits = d loss / d logits. */
+ * (the reference syncs three scalars to the host every step, ex_audioset.py:192-194).  dlogits = d loss / d logits.
+ * A NULL logits / y / sums / dlogits is EAT_EINVAL; the VALUES of perm (in [0, B)) and teacher_idx (in [-1, n_teacher))
+ * are the caller's responsibility: the kernel gathers rows by them unchecked. */
 int eat_kd_loss_fwd_bwd(const float* logits, const float* y, const int* perm, const float* lam, const float* teacher,
                         const long long* teacher_idx, int n_teacher, float kd_lambda, int B, int C, float* sums,
                         float* dlogits, eat_stream_t stream);
