@@ -817,6 +817,21 @@ extern "C" int eat_dyn_pw_pack_t(const float* bank_t, const float* att, const fl
   return dyn_pw_pack_impl(bank_t, att, row_scale, wp, B, K, Co, Ci, 1, stream);
 }
 
+// a block of the bf16 pack kernels = (m-tile, SB samples, 256-column piece); SB: as many samples as keep >= ~2048 blocks (8 per
+// CU) in the launch, at most 8
+static int dyn_pw_pack_samples_per_block(int B, int Co, int Ci) {
+  const int MT = (Co + 15) / 16, pieces = (Ci + kPackCols - 1) / kPackCols;
+  int SB = 8;
+  while (SB > 1 && (long long)MT * pieces * ((B + SB - 1) / SB) < 2048) SB >>= 1;
+  return SB;
+}
+
+// host helper (tests, measurement tools): the samples per block eat_dyn_pw_pack_bf16 / _t / _b16 launch with for a shape
+extern "C" int eat_dyn_pw_pack_samples_per_block(int B, int Co, int Ci) {
+  if (B < 1 || Co < 1 || Ci < 1) return 1;
+  return dyn_pw_pack_samples_per_block(B, Co, Ci);
+}
+
 static int dyn_pw_pack_bf16_impl(const float* bank, const float* att, void* wp, int B, int K, int Co, int Ci, int trans,
                                  eat_stream_t stream, int np2 = 2) {
   eat::clear_stale_error();
@@ -824,10 +839,8 @@ static int dyn_pw_pack_bf16_impl(const float* bank, const float* att, void* wp, 
   if (trans && Co % 4 != 0) return eat::fail(EAT_EINVAL, "eat_dyn_pw_pack_bf16_t: Co=%d must be a multiple of 4", Co);
   if (B < 1 || K < 1 || Co < 1) return eat::fail(EAT_EINVAL, "eat_dyn_pw_pack_bf16: bad shape");
   const int MT = (Co + 15) / 16, KK = (Ci + 31) / 32;
-  // a block = (m-tile, SB samples, 256-column piece); SB: as many samples as keep >= ~2048 blocks (8 per CU) in the launch, at most 8
   const int pieces = (Ci + kPackCols - 1) / kPackCols;
-  int SB = 8;
-  while (SB > 1 && (long long)MT * pieces * ((B + SB - 1) / SB) < 2048) SB >>= 1;
+  const int SB = dyn_pw_pack_samples_per_block(B, Co, Ci);
   const dim3 grid(MT, (B + SB - 1) / SB, pieces);
   if (K == 4)
     hipLaunchKernelGGL(dyn_pw_pack_bf16_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, bank, att,

@@ -810,6 +810,10 @@ int eat_pw_conv_wgrad_b16(const void* dz, int dz_b16, const void* x, int x_b16, 
  * holds the transposed matrices (K, Ci*Co) - the data-gradient pack; then Co % 4 == 0.  Ci % 4 == 0. */
 int eat_dyn_pw_pack_b16(const float* bank, const float* att, void* wp, int B, int K, int Co, int Ci, int trans,
                         eat_stream_t stream);
+/* host helper for the three bf16 pack entry points (eat_dyn_pw_pack_bf16 / _t / _b16; models/dymn/dy_block.py:111-119): the
+ * number of consecutive samples one block of their kernel packs for a shape - 8 halved while the launch would have fewer than
+ * 2048 blocks, so 1 at small batches.  Launches nothing; tests use it to pin which branch of the kernel a case takes. */
+int eat_dyn_pw_pack_samples_per_block(int B, int Co, int Ci);
 
 /* Twin of eat_pw_conv_dyn_bf16_fwd / eat_pw_conv_stats_fwd(per_sample = 1) (dy_block.py:120-127 for kernel_size 1, forward and
  * data gradient): exactly one of x / y is the wide bf16 tensor.
