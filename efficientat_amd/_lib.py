@@ -1,4 +1,4 @@
-"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h and include/eat_tag.h).
+"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h and include/eat_embed.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("EAT_LIB") or os.path.join(_HERE, "libeat_hip.so")
 HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_hip.h")
 # the long-recording tagger's entry points (efficientat_amd/tagger.py): same library, same conventions, their own header
 TAG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_tag.h")
+# the embedding extractor's entry point (efficientat_amd/embeddings.py): likewise
+EMBED_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_embed.h")
 
 
 class EatHipError(RuntimeError):
@@ -65,6 +67,8 @@ with open(HEADER_PATH) as _f:
 SIGNATURES = {name: args for name, (_, args) in PROTOTYPES.items()}    # name -> argtypes
 with open(TAG_HEADER_PATH) as _f:
     TAG_PROTOTYPES = parse_prototypes(_f.read())                       # bound by lib() as well; not part of PROTOTYPES
+with open(EMBED_HEADER_PATH) as _f:
+    EMBED_PROTOTYPES = parse_prototypes(_f.read())                     # likewise
 
 _lib = None
 
@@ -78,7 +82,7 @@ def lib():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU/PyTorch fallback). "
                 "Build it with `python -m efficientat_amd.build`.")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()) + list(EMBED_PROTOTYPES.items()):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

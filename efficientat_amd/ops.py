@@ -2074,3 +2074,83 @@ def resample_mono(frames, up, down, taps):
     _lib.call("eat_resample_mono", frames.data_ptr(), 1 if frames.dtype == torch.int16 else 0, n_in, channels, int(up), int(down),
               _dev(taps, "taps"), taps.numel(), out.data_ptr(), n_out, _stream())
     return out
+
+
+# ------------------------------------------------------------------ embedding extractor (include/eat_embed.h)
+_EMBED_GRID = 2 ** 31 - 1      # blocks of one eat_embed_pool launch: ceil(D / 4) * B
+_EMBED_TABLES = {}             # (device, map shapes, lo, hi) -> (dims, seg) on the device
+_EMBED_ADDRS = {}              # (device, map addresses, map shapes) -> address table per chunk over B, on the device
+
+
+def check_segments(lo, hi, T_l):
+    """Host-side validation of the segment tables of `embed_pool` (CPU arrays): lo, hi (n_maps, n_seg) with
+    0 <= lo < hi <= T_l[map] everywhere -> (lo, hi) contiguous int32 CPU tensors."""
+    try:
+        lo_t, hi_t = (torch.as_tensor(v) for v in (lo, hi))
+    except (ValueError, TypeError) as e:
+        raise _lib.EatHipError(f"embed_pool: ragged segment table ({e})") from None
+    T = torch.as_tensor(T_l, dtype=torch.int64).reshape(-1)
+    if lo_t.dim() != 2 or lo_t.shape != hi_t.shape or lo_t.shape[0] != T.numel() or lo_t.shape[1] < 1:
+        raise _lib.EatHipError(f"embed_pool: ragged segment table: need lo and hi of one (n_maps, n_seg >= 1) shape with a row "
+                               f"per map (got lo {tuple(lo_t.shape)}, hi {tuple(hi_t.shape)}, {T.numel()} maps)")
+    if lo_t.dtype.is_floating_point or hi_t.dtype.is_floating_point:
+        raise _lib.EatHipError("embed_pool: segment bounds must be integers")
+    lo_t, hi_t = lo_t.to(torch.int64), hi_t.to(torch.int64)
+    bad = (lo_t < 0) | (lo_t >= hi_t) | (hi_t > T.view(-1, 1))
+    if bool(bad.any()):
+        l, s = (int(v) for v in bad.nonzero()[0])
+        raise _lib.EatHipError(f"embed_pool: segment {s} of map {l} is [{int(lo_t[l, s])}, {int(hi_t[l, s])}): need "
+                               f"0 <= lo < hi <= T_l = {int(T[l])}")
+    return lo_t.to(torch.int32).contiguous(), hi_t.to(torch.int32).contiguous()
+
+
+def embed_pool(fmaps, lo, hi, out=None):
+    """Segment means of a list of feature maps (B, C_l, F_l, T_l), concatenated along the channel axis ->
+    out (B, n_seg, D = sum C_l): out[b, s, off_l + c] = mean of fmaps[l][b, c, :, lo[l, s]:hi[l, s]].  lo, hi: CPU
+    (n_maps, n_seg) tables, validated by `check_segments`; the scene embedding is lo = 0, hi = T_l with n_seg = 1.
+    One launch for all maps and segments (chunks over B only beyond the grid limit).  The device copies of the shape and
+    segment tables are cached per (map shapes, plan): a recording's chunks repeat them."""
+    fmaps = list(fmaps)
+    if not 1 <= len(fmaps) <= 64:
+        raise _lib.EatHipError(f"embed_pool: need 1 to 64 feature maps (got {len(fmaps)})")
+    if any(m.dim() != 4 or m.shape[0] != fmaps[0].shape[0] or m.device != fmaps[0].device for m in fmaps):
+        raise _lib.EatHipError("embed_pool: every feature map must be (B, C, F, T) with one B, on one device")
+    if any(m.numel() == 0 for m in fmaps):
+        raise _lib.EatHipError("embed_pool: an empty feature map")
+    ptrs = [_dev(m, "x") for m in fmaps]
+    dev, B = fmaps[0].device, fmaps[0].shape[0]
+    shapes = tuple(tuple(m.shape[1:]) for m in fmaps)
+    lo_t, hi_t = check_segments(lo, hi, [s[2] for s in shapes])
+    n_seg, D = lo_t.shape[1], sum(s[0] for s in shapes)
+    key = (dev, shapes, lo_t.numpy().tobytes(), hi_t.numpy().tobytes())
+    tables = _EMBED_TABLES.get(key)
+    if tables is None:
+        if len(_EMBED_TABLES) >= 64:
+            _EMBED_TABLES.clear()
+        offs, off = [], 0
+        for s in shapes:
+            offs.append(off)
+            off += s[0]
+        dims = torch.tensor([[c, f, t, o] for (c, f, t), o in zip(shapes, offs)], dtype=torch.int32)
+        tables = _EMBED_TABLES[key] = (dims.to(dev), torch.stack((lo_t, hi_t), dim=2).contiguous().to(dev))
+    dims, seg = tables
+    if out is None:
+        out = torch.empty((B, n_seg, D), device=dev, dtype=torch.float32)
+    elif out.shape != (B, n_seg, D) or out.device != dev:
+        raise _lib.EatHipError(f"embed_pool: out must be ({B}, {n_seg}, {D}) on {dev} (got {tuple(out.shape)} on {out.device})")
+    o = _dev(out, "out")
+    step = max(1, _EMBED_GRID // ((D + 3) // 4))
+    # the caching allocator hands a recording's chunks the same addresses again and again: no upload in the steady state
+    akey = (dev, tuple(ptrs), shapes, B)
+    addrs = _EMBED_ADDRS.get(akey)
+    if addrs is None:
+        if len(_EMBED_ADDRS) >= 64:
+            _EMBED_ADDRS.clear()
+        addrs = _EMBED_ADDRS[akey] = [
+            torch.tensor([p + 4 * b0 * c * f * t for p, (c, f, t) in zip(ptrs, shapes)], dtype=torch.int64).to(dev)
+            for b0 in range(0, B, step)]
+    for b0, addr in zip(range(0, B, step), addrs):
+        nb = min(step, B - b0)
+        _lib.call("eat_embed_pool", addr.data_ptr(), dims.data_ptr(), seg.data_ptr(), len(fmaps), nb, n_seg, D,
+                  o + 4 * b0 * n_seg * D, _stream())
+    return out

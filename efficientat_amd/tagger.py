@@ -64,6 +64,30 @@ def window_plan(n_samples, window_size_s, hop_length_s, sample_rate=32000):
     return starts, valids, W
 
 
+def load_waveform(audio_path, sample_rate, device):
+    """WAV file -> mono fp32 waveform at `sample_rate` on the device: decoded on the host (scipy.io.wavfile), int16 and
+    float32 frames uploaded as they are, other sample types converted to float32 as `audio_io.load_audio` does;
+    dequantised, down-mixed and resampled on the device."""
+    from scipy.io import wavfile
+    src_sr, data = wavfile.read(audio_path)
+    if data.dtype == np.uint8:
+        data = (data.astype(np.float32) - 128.0) / 128.0
+    elif data.dtype != np.int16 and np.issubdtype(data.dtype, np.integer):
+        data = data.astype(np.float32) / float(2 ** (8 * data.dtype.itemsize - 1))
+    elif data.dtype != np.int16:
+        data = data.astype(np.float32)
+    if data.shape[0] < 1:
+        raise ValueError(f"{audio_path}: no audio frames")
+    frames = torch.from_numpy(np.ascontiguousarray(data)).to(device)
+    if src_sr == sample_rate and frames.dtype == torch.float32 and frames.dim() == 1:
+        return frames                                        # nothing to do: no launch
+    if src_sr == sample_rate:
+        up, down, taps = 1, 1, torch.ones(1)                 # dequantise + down-mix alone: one tap of 1.0
+    else:
+        up, down, taps = resample_plan(src_sr, sample_rate)
+    return ops.resample_mono(frames, up, down, taps.to(device))
+
+
 def _get_ensemble_model(names):
     """`models.ensemble.get_ensemble_model` of the drop-in tree (dropin/models/ensemble.py), loaded by path: the drop-in
     tree is laid out to shadow the reference's top-level `models` package and is not itself a package."""
@@ -164,27 +188,8 @@ class EATagger:
         return self._tag_flat(flat, lengths, window_size, hop_length, return_probs)
 
     def load_waveform(self, audio_path):
-        """WAV file -> mono fp32 waveform at `sample_rate` on the device: decoded on the host (scipy.io.wavfile), int16 and
-        float32 frames uploaded as they are, other sample types converted to float32 as `audio_io.load_audio` does;
-        dequantised, down-mixed and resampled on the device."""
-        from scipy.io import wavfile
-        src_sr, data = wavfile.read(audio_path)
-        if data.dtype == np.uint8:
-            data = (data.astype(np.float32) - 128.0) / 128.0
-        elif data.dtype != np.int16 and np.issubdtype(data.dtype, np.integer):
-            data = data.astype(np.float32) / float(2 ** (8 * data.dtype.itemsize - 1))
-        elif data.dtype != np.int16:
-            data = data.astype(np.float32)
-        if data.shape[0] < 1:
-            raise ValueError(f"{audio_path}: no audio frames")
-        frames = torch.from_numpy(np.ascontiguousarray(data)).to(self.device)
-        if src_sr == self.sample_rate and frames.dtype == torch.float32 and frames.dim() == 1:
-            return frames                                        # nothing to do: no launch
-        if src_sr == self.sample_rate:
-            up, down, taps = 1, 1, torch.ones(1)                 # dequantise + down-mix alone: one tap of 1.0
-        else:
-            up, down, taps = resample_plan(src_sr, self.sample_rate)
-        return ops.resample_mono(frames, up, down, taps.to(self.device))
+        """`load_waveform` at this tagger's sample rate, on its device."""
+        return load_waveform(audio_path, self.sample_rate, self.device)
 
     def tag_audio_window(self, audio_path, window_size=20.0, hop_length=10.0):
         """The reference's call (windowed_inference.py:71-124) -> list of {'start', 'end', 'tags': [{'tag', 'probability'}
