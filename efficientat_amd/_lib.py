@@ -1,4 +1,5 @@
-"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h and include/eat_embed.h).
+"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h, include/eat_embed.h and
+include/eat_attn.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -21,6 +22,8 @@ HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_hip.h")
 TAG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_tag.h")
 # the embedding extractor's entry point (efficientat_amd/embeddings.py): likewise
 EMBED_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_embed.h")
+# the attention-pooling head's entry points (efficientat_amd/mn.py, mn_train.py): likewise
+ATTN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_attn.h")
 
 
 class EatHipError(RuntimeError):
@@ -69,6 +72,8 @@ with open(TAG_HEADER_PATH) as _f:
     TAG_PROTOTYPES = parse_prototypes(_f.read())                       # bound by lib() as well; not part of PROTOTYPES
 with open(EMBED_HEADER_PATH) as _f:
     EMBED_PROTOTYPES = parse_prototypes(_f.read())                     # likewise
+with open(ATTN_HEADER_PATH) as _f:
+    ATTN_PROTOTYPES = parse_prototypes(_f.read())                      # likewise
 
 _lib = None
 
@@ -82,7 +87,8 @@ def lib():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU/PyTorch fallback). "
                 "Build it with `python -m efficientat_amd.build`.")
         h = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()) + list(EMBED_PROTOTYPES.items()):
+        for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()) + list(EMBED_PROTOTYPES.items())
+                                          + list(ATTN_PROTOTYPES.items())):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -587,7 +587,9 @@ def load_init_checkpoint(model, path):
     """Initialise `model` from a local AudioSet state dict (e.g. one written by `train_dp --out`) - what the reference's
     `pretrained_name` does from its download.  When the class count differs, the output layer is dropped (classifier.5.* for
     the mlp head, classifier.0.weight + classifier.1.* for the fully-convolutional one) with the reference's note, and the
-    rest is loaded strictly; a mismatch on any other head raises ValueError.  -> the list of dropped keys."""
+    rest is loaded strictly; a mismatch on any other head raises ValueError.  An attention-pooling model takes the trunk of a
+    checkpoint of another head (one without `classifier.subspace_proj.weight`): the reference's note, every `classifier.*`
+    key of the checkpoint dropped, the head keeps its fresh initialisation.  -> the list of dropped keys."""
     sd = torch.load(path, map_location="cpu", weights_only=True)
     msd = model.state_dict()
     mismatch = sorted(k for k in sd if k in msd and tuple(sd[k].shape) != tuple(msd[k].shape))
@@ -596,6 +598,22 @@ def load_init_checkpoint(model, path):
         raise ValueError(f"load_init_checkpoint: {path} does not fit head '{getattr(model, 'head_type', None)}' "
                          f"(shape mismatch at {mismatch[:4]}); only the mlp and fully_convolutional heads can be re-sized")
     dropped = []
+    if (not mismatch and getattr(model, "head_type", None) == "multihead_attention_pooling"
+            and "classifier.subspace_proj.weight" not in sd):
+        # a checkpoint of another head (every released one carries the mlp head): the trunk is loaded, the attention head
+        # keeps its fresh initialisation (models/mn/model.py:289-310 prints this note and loads non-strictly)
+        dropped = [k for k in sd if k.startswith("classifier.")]
+        own = sorted(k for k in msd if k.startswith("classifier."))
+        rest = {k for k in sd if not k.startswith("classifier.")}
+        missing, unexpected = sorted(set(msd) - rest), sorted(rest - set(msd))
+        if missing != own or unexpected:
+            raise ValueError(f"load_init_checkpoint: {path} does not hold the model's other tensors "
+                             f"(missing {[k for k in missing if k not in own][:4]}, unexpected {unexpected[:4]})")
+        print("Loading weights for classifier only implemented for head types 'mlp' and 'fully_convolutional'")
+        for k in dropped:
+            sd.pop(k)
+        model.load_state_dict(sd, strict=False)
+        return dropped
     if out is not None:
         keys, n_ckpt, n_model = out
         stray = [k for k in mismatch if k not in keys]

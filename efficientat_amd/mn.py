@@ -19,7 +19,6 @@ from typing import List, Optional
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import ops
 from .utils import make_divisible, cnn_out_size, NAME_TO_WIDTH  # noqa: F401
@@ -126,9 +125,10 @@ class ConcurrentSEBlock(nn.Module):
 
 class MultiHeadAttentionPooling(nn.Module):
     """Parameter holder + eval forward of the PSLA multi-head attention pooling head (models/mn/attention_pooling.py:9-56):
-    mean over frequency, Linear to (att, val) x heads x classes on the MFMA linear kernel, sigmoid attention normalised
-    over time, weighted sum, head-weighted sum.  The (B, heads, T, classes) algebra after the GEMM is a few KB per clip
-    and stays in torch ops."""
+    mean over frequency (`ops.freq_mean`), the Linear to (att, val) x heads x classes as a 1x1 conv over the time positions
+    on the MFMA conv kernels, then sigmoid attention normalised over time, weighted sum and head-weighted sum in ONE
+    kernel (`ops.attn_pool`, csrc/attn_head.hip).  Nothing is transposed and no torch op touches a tensor of the head;
+    training runs the same steps with their backward as `mn_train.AttentionPoolHead`."""
 
     def __init__(self, in_dim, out_dim, att_activation="sigmoid", clf_activation="ident", num_heads=4, epsilon=1e-7):
         super().__init__()
@@ -138,20 +138,24 @@ class MultiHeadAttentionPooling(nn.Module):
         self.subspace_proj = nn.Linear(in_dim, out_dim * 2 * num_heads)
         self.head_weight = nn.Parameter(torch.tensor([1.0 / num_heads] * num_heads).view(1, -1, 1))
 
-    def forward(self, x):
-        b, c = x.shape[0], x.shape[1]
-        xm = x.mean(dim=2).transpose(1, 2).contiguous()                  # collapse_dim(x, 2) -> (B, T, C)
-        n = xm.shape[1]
-        if torch.is_grad_enabled() and (xm.requires_grad or self.subspace_proj.weight.requires_grad):
-            # training: the (B T, C) x (C, 2 heads classes) GEMM under torch autograd (the class count is not a multiple of 4,
-            # which the library's data-gradient GEMM needs; 128 rows per clip)
-            p = F.linear(xm.view(b * n, c), self.subspace_proj.weight, self.subspace_proj.bias)
-        else:
-            p = ops.linear(xm.view(b * n, c), self.subspace_proj.weight, self.subspace_proj.bias, ops.ACT_NONE)
-        p = p.view(b, n, 2, self.num_heads, self.out_dim).permute(2, 0, 3, 1, 4)
-        att, val = torch.sigmoid(p[0]).clamp(self.epsilon, 1.0 - self.epsilon), p[1]
-        att = att / att.sum(dim=2, keepdim=True)
-        return ((att * val).sum(dim=2) * self.head_weight).sum(dim=1)
+    def pack(self):
+        """(packed projection weights, zero GEMM bias, mode) for `forward`; the Linear's bias is added by the pooling kernel."""
+        w = self.subspace_proj.weight
+        wp, _, mode = _pack_pw(w, None, None)
+        return wp, ops.zeros_vec.get(w.shape[0], w.device), mode
+
+    def forward(self, x, pack=None):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            from .mn_train import attention_pool_head
+            return attention_pool_head(self, x)
+        with torch.no_grad():
+            x = x.contiguous().float()
+            B, C, _, T = x.shape
+            N = self.subspace_proj.out_features
+            xm = ops.freq_mean(x)
+            p = _pw(xm.view(B, C, 1, xm.shape[2]), pack or self.pack(), N, ops.ACT_NONE)
+            return ops.attn_pool(p.view(B, N, xm.shape[2]), self.subspace_proj.bias, self.head_weight.contiguous(),
+                                 self.num_heads, T, self.epsilon)
 
 
 class InvertedResidual(nn.Module):
@@ -434,9 +438,10 @@ class MN(nn.Module):
     # ------------------------------------------------------------------ folded weights
     def _fold_sources(self):
         mods = list(self.features.modules()) + (list(self.classifier.modules()) if self.head_type == "fully_convolutional" else [])
+        head = [self.classifier.subspace_proj.weight] if self.head_type == "multihead_attention_pooling" else []
         return [t for m in mods if isinstance(m, (nn.Conv2d, nn.BatchNorm2d))
                 for t in ([m.weight] if isinstance(m, nn.Conv2d) else
-                          [m.weight, m.bias, m.running_mean, m.running_var])]
+                          [m.weight, m.bias, m.running_mean, m.running_var])] + head
 
     def _build_folded(self):
         out = {}
@@ -455,6 +460,8 @@ class MN(nn.Module):
             # eval: mean_s BN(conv1x1(x)) = (scale * W) mean_s(x) + bias - the head collapses onto the pooled features
             s, b = _fold(self.classifier[0], self.classifier[1])
             out["fc_head"] = ((self.classifier[0].weight.flatten(1) * s.view(-1, 1)).contiguous(), b.contiguous())
+        elif self.head_type == "multihead_attention_pooling":
+            out["att_head"] = self.classifier.pack()
         return out
 
     # --------------------------------------------------------------------------- forward
@@ -513,7 +520,7 @@ class MN(nn.Module):
         elif self.head_type == "fully_convolutional":
             logits = ops.linear(pooled, W["fc_head"][0], W["fc_head"][1], ops.ACT_NONE, 1.0 / S)
         else:
-            logits = self.classifier(y)
+            logits = self.classifier(y, W["att_head"])
         if return_fmaps:
             return logits, fmaps
         return logits, pooled * (1.0 / S)

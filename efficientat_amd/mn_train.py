@@ -642,12 +642,70 @@ def _backward_impl(ctx, model, sv, dlogits, dfeat, n_lead):
     return (None,) * n_lead + tuple(grads.get(n) for n in ctx.names)
 
 
+class AttentionPoolHead(torch.autograd.Function):
+    """The multi-head attention-pooling head (models/mn/attention_pooling.py:37-56) on the library, in the layout of the
+    1x1 kernels (csrc/attn_head.hip): y (B, C, F, T) -> logits (B, K).
+
+    forward:  `ops.freq_mean` -> the projection as a 1x1 conv over the T positions (`ops.pw_conv`, pack by the active
+              `ops.precision`) -> `ops.attn_pool` (adds the bias, saves o and s)
+    backward: `ops.attn_pool_bwd` (dp, dbias, dhead_w) -> data gradient on the same conv kernel with the transposed pack
+              -> `ops.pw_conv_wgrad(dp, xm)` -> `ops.freq_mean_bwd`
+    Rows of xm / p / dp have the pitch `ops.pitch4(T)`, pad columns zero.  The data-gradient GEMM contracts over the 2 H K
+    rows of dp and wants a multiple of 4 of them: an odd H K (one head, an odd class count) runs the backward on dp and a
+    copy of the weight padded by two zero rows."""
+
+    @staticmethod
+    def forward(ctx, y, w, b, head_w, H, eps):
+        y = y.contiguous()
+        B, C, Fq, T = y.shape
+        N = w.shape[0]
+        Tp = ops.pitch4(T)
+        xm = ops.freq_mean(y, Tp)
+        wp = ops.pw_prepack(w.contiguous())
+        p = ops.pw_conv(xm.view(B, C, 1, Tp), wp, ops.zeros_vec.get(N, y.device), N, NONE).view(B, N, Tp)
+        hw = head_w.detach().contiguous()
+        out, o, s = ops.attn_pool(p, b, hw, H, T, eps, save=True)
+        ctx.save_for_backward(xm, p, o, s, w, b, hw)
+        ctx.geo, ctx.prec, ctx.hw_shape = (Fq, T, H, eps), ops.precision.mode, head_w.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xm, p, o, s, w, b, hw = ctx.saved_tensors
+        Fq, T, H, eps = ctx.geo
+        B, C, Tp = xm.shape
+        N = w.shape[0]
+        Np = (N + 3) // 4 * 4
+        with ops.precision(ctx.prec), ops.zero_arena.scope("att_head_bwd"):
+            # (the zero-filled memory of the weight gradient first: the pass's one fill precedes the head's own launches)
+            dw = ops.zero_arena.zeros((Np, C), torch.float32, w.device)
+            dp, db, dhw = ops.attn_pool_bwd(g.contiguous().float(), p, b, hw, o, s, H, T, eps, Np=Np)
+            wt = w.contiguous()
+            if Np != N:
+                wt = ops.zero_arena.zeros((Np, C), torch.float32, w.device)
+                wt[:N].copy_(w)
+            dp4 = dp.view(B, Np, 1, Tp)
+            dw = ops.pw_conv_wgrad(dp4, xm.view(B, C, 1, Tp), exact=None, out=dw)[:N].view_as(w)
+            dy = None
+            if ctx.needs_input_grad[0]:
+                dxm = ops.pw_conv(dp4, ops.pw_prepack(wt, trans=True), ops.zeros_vec.get(C, w.device), C, NONE)
+                dy = ops.freq_mean_bwd(dxm.view(B, C, Tp), Fq, T)
+        return dy, dw, db, dhw.view(ctx.hw_shape), None, None
+
+
+def attention_pool_head(head, y):
+    """`MultiHeadAttentionPooling` on the last feature map y under autograd (both training plans)."""
+    return AttentionPoolHead.apply(y, head.subspace_proj.weight, head.subspace_proj.bias, head.head_weight, head.num_heads,
+                                   head.epsilon)
+
+
 def forward_train(model, x, return_fmaps=False):
     """Train-mode `(logits, features)` - or `(logits, fmaps)` - with autograd support (mn/model.py:212-231 in `.train()`).
 
     The default network (mlp head) is one Function incl. the head.  Non-default heads (`fully_convolutional`,
     `multihead_attention_pooling`; mn/model.py:170-185) and `return_fmaps=True` run the trunk Function up to the last
-    feature map and the head module on top of it under torch autograd (both heads act on the 960 x 4 x 32 map only).  The 17 feature maps of
+    feature map and the head on top of it: the attention-pooling head as the library's `AttentionPoolHead`, the
+    fully-convolutional one as torch ops under torch autograd (both act on the 960 x 4 x 32 map only).  The 17 feature maps of
     `return_fmaps` are values only (no gradient flows back through them; the logits are differentiable as usual)."""
     drop = model.classifier[4] if model.head_type == "mlp" else None
     mask = None
@@ -659,12 +717,17 @@ def forward_train(model, x, return_fmaps=False):
         mask = override.to(x.device).float() / (1.0 - drop.p)
     params = [p for _, p in model.named_parameters()]
     trunk = return_fmaps or model.head_type != "mlp"
-    model._eat_trunk_active = trunk       # dp.py: the head's gradients come from torch autograd then (their own reducer hooks)
+    model._eat_trunk_active = trunk       # dp.py: the head's gradients reach its parameters through autograd then (their own reducer hooks)
     with ops.precision(getattr(model, "train_precision", "fp32")), ops.bn_counters, ops.zero_arena.scope("mn_fwd"):
         if not trunk:
             return MNTrainFunction2.apply(model, x, mask, 0, *params)
         outs = MNTrainFunction2.apply(model, x, None, 1, *params)
         y_l, fmaps = outs[0], list(outs[1:])
+        if model.head_type == "multihead_attention_pooling":
+            # the library's head: frequency mean, GEMM, pooling - launched straight behind the trunk's last kernel
+            logits = attention_pool_head(model.classifier, y_l)
+            feat = y_l.mean(dim=(2, 3))
+            return (logits, fmaps + [y_l]) if return_fmaps else (logits, feat)
         feat = y_l.mean(dim=(2, 3))
         if model.head_type == "mlp":
             fc1, fc2 = model.classifier[2], model.classifier[5]
@@ -674,8 +737,8 @@ def forward_train(model, x, return_fmaps=False):
             logits = F.linear(h, fc2.weight, fc2.bias)
         else:
             # fully-convolutional head (1x1 conv to the classes + BatchNorm + mean: the class count, 527, is not a
-            # multiple of 4, which the library's data-gradient GEMM needs) and the attention-pooling module: a few MB of
-            # torch ops on the 4 x 32 map under torch autograd
+            # multiple of 4, which the library's data-gradient GEMM needs): a few MB of torch ops on the 4 x 32 map under
+            # torch autograd
             logits = model.classifier(y_l).reshape(x.shape[0], -1)
     return (logits, fmaps + [y_l]) if return_fmaps else (logits, feat)
 
@@ -743,6 +806,8 @@ def forward_train_modular(model, x, return_fmaps=False):
                 elif drop.p > 0:
                     h = F.dropout(h, drop.p, True)
             logits = Linear.apply(h, fc2.weight, fc2.bias)
+        elif model.head_type == "multihead_attention_pooling":
+            logits = attention_pool_head(model.classifier, y_l)
         else:
             logits = model.classifier(y_l).reshape(x.shape[0], -1)
     return (logits, fmaps + [y_l]) if return_fmaps else (logits, feat)

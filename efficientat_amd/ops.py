@@ -2154,3 +2154,115 @@ def embed_pool(fmaps, lo, hi, out=None):
         _lib.call("eat_embed_pool", addr.data_ptr(), dims.data_ptr(), seg.data_ptr(), len(fmaps), nb, n_seg, D,
                   o + 4 * b0 * n_seg * D, _stream())
     return out
+
+
+# ------------------------------------------------------------------ attention-pooling head (models/mn/attention_pooling.py:9-56)
+def pitch4(T):
+    """Row pitch of the head's (B, rows, T) tensors: T rounded up to a multiple of 4 (16-byte row pieces of the 1x1 kernels)."""
+    return (T + 3) // 4 * 4
+
+
+def _head_out(out, name, shape, like):
+    """A caller's output tensor (checked like an operand) or a fresh one."""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    n = 1
+    for d in shape:
+        n *= d
+    _glue_operand(out, name, torch.float32, like, n=n)
+    return out
+
+
+def _on_gpu(t, name):
+    if not t.is_cuda:
+        raise _lib.EatHipError(f"{name} must live on the GPU: efficientat_amd has no CPU path (got device {t.device})")
+    if t.device.index != torch.cuda.current_device():
+        raise _lib.EatHipError(f"{name} lives on {t.device} but the current device is cuda:{torch.cuda.current_device()}")
+    return t.data_ptr()
+
+
+def freq_mean(y, Tp=None, out=None):
+    """xm (B, C, Tp) = mean over the frequency axis of y (B, C, F, T); pad columns [T, Tp) are written as zeros
+    (Tp defaults to `pitch4(T)`)."""
+    fn = "freq_mean"
+    if not isinstance(y, torch.Tensor) or y.dim() != 4 or y.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: y must be a non-empty (B, C, F, T) tensor, got {tuple(getattr(y, 'shape', ()))}")
+    B, C, F, T = y.shape
+    Tp = pitch4(T) if Tp is None else int(Tp)
+    if Tp < T:
+        raise _lib.EatHipError(f"{fn}: Tp={Tp} is shorter than T={T}")
+    _glue_operand(y, f"{fn}: y", torch.float32, y)
+    xm = _head_out(out, f"{fn}: out", (B, C, Tp), y)
+    _lib.call("eat_freq_mean_fwd", _on_gpu(y, f"{fn}: y"), xm.data_ptr(), B, C, F, T, Tp, _stream())
+    return xm
+
+
+def freq_mean_bwd(dxm, F, T, out=None):
+    """dy (B, C, F, T) = dxm[b, c, t] / F from dxm (B, C, Tp), Tp >= T."""
+    fn = "freq_mean_bwd"
+    if not isinstance(dxm, torch.Tensor) or dxm.dim() != 3 or dxm.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: dxm must be a non-empty (B, C, Tp) tensor, got {tuple(getattr(dxm, 'shape', ()))}")
+    B, C, Tp = dxm.shape
+    F, T = int(F), int(T)
+    if F < 1 or T < 1:
+        raise _lib.EatHipError(f"{fn}: need F, T >= 1 (got {F}, {T})")
+    if Tp < T:
+        raise _lib.EatHipError(f"{fn}: Tp={Tp} is shorter than T={T}")
+    _glue_operand(dxm, f"{fn}: dxm", torch.float32, dxm)
+    dy = _head_out(out, f"{fn}: out", (B, C, F, T), dxm)
+    _lib.call("eat_freq_mean_bwd", _on_gpu(dxm, f"{fn}: dxm"), dy.data_ptr(), B, C, F, T, Tp, _stream())
+    return dy
+
+
+def _pool_operands(fn, p, bias, head_w, H, T, eps):
+    """Metadata checks shared by `attn_pool` / `attn_pool_bwd` -> (B, K, Tp, bias pointer or None, head_w pointer)."""
+    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: p must be a non-empty (B, 2 H K, Tp) tensor, got {tuple(getattr(p, 'shape', ()))}")
+    B, N, Tp = p.shape
+    H, T = int(H), int(T)
+    if H < 1 or N % (2 * H):
+        raise _lib.EatHipError(f"{fn}: p has {N} rows per sample, not a multiple of 2 H = {2 * H}")
+    if T < 1 or Tp < T:
+        raise _lib.EatHipError(f"{fn}: Tp={Tp} is shorter than T={T} (or T < 1)")
+    if not 0.0 <= float(eps) < 0.5:
+        raise _lib.EatHipError(f"{fn}: eps must lie in [0, 0.5) (got {eps})")
+    _glue_operand(p, f"{fn}: p", torch.float32, p)
+    p_hw = _glue_operand(head_w, f"{fn}: head_w", torch.float32, p, n=H)
+    p_bias = None if bias is None else _glue_operand(bias, f"{fn}: bias", torch.float32, p, n=N)
+    return B, N // (2 * H), Tp, p_bias, p_hw
+
+
+def attn_pool(p, bias, head_w, H, T, eps=1e-7, save=False, out=None, o=None, s=None):
+    """Attention pooling of the projection p (B, 2 H K, Tp) -> out (B, K) (include/eat_attn.h: eat_attn_pool_fwd); bias (2 H K)
+    or None is added to p on load, head_w holds H values.  save=True: -> (out, o, s) with o, s (B, H, K) for `attn_pool_bwd`."""
+    fn = "attn_pool"
+    B, K, Tp, p_bias, p_hw = _pool_operands(fn, p, bias, head_w, H, T, eps)
+    out = _head_out(out, f"{fn}: out", (B, K), p)
+    if save or o is not None or s is not None:
+        o, s = _head_out(o, f"{fn}: o", (B, H, K), p), _head_out(s, f"{fn}: s", (B, H, K), p)
+    _lib.call("eat_attn_pool_fwd", _on_gpu(p, f"{fn}: p"), p_bias, p_hw, float(eps), out.data_ptr(),
+              None if o is None else o.data_ptr(), None if s is None else s.data_ptr(), B, int(H), K, int(T), Tp, _stream())
+    return (out, o, s) if save else out
+
+
+def attn_pool_bwd(g, p, bias, head_w, o, s, H, T, eps=1e-7, Np=None, dp=None, dbias=None, dhead_w=None):
+    """Backward of `attn_pool` from g (B, K) -> (dp (B, Np, Tp), dbias (2 H K) or None without a bias, dhead_w (H)).
+    Np >= 2 H K rows per sample of dp (default 2 H K); pad columns and pad rows of dp are written as zeros."""
+    fn = "attn_pool_bwd"
+    B, K, Tp, p_bias, p_hw = _pool_operands(fn, p, bias, head_w, H, T, eps)
+    H, N = int(H), 2 * int(H) * K
+    Np = N if Np is None else int(Np)
+    if Np < N:
+        raise _lib.EatHipError(f"{fn}: Np={Np} is smaller than 2 H K = {N}")
+    p_g = _glue_operand(g, f"{fn}: g", torch.float32, p, n=B * K)
+    p_o = _glue_operand(o, f"{fn}: o", torch.float32, p, n=B * H * K)
+    p_s = _glue_operand(s, f"{fn}: s", torch.float32, p, n=B * H * K)
+    dp = _head_out(dp, f"{fn}: dp", (B, Np, Tp), p)
+    if bias is not None or dbias is not None:
+        dbias = _head_out(dbias, f"{fn}: dbias", (N,), p)
+    dhead_w = _head_out(dhead_w, f"{fn}: dhead_w", (H,), p)
+    p_p = _on_gpu(p, f"{fn}: p")
+    ws = torch.empty((B * (N + H),), device=p.device, dtype=torch.float32)
+    _lib.call("eat_attn_pool_bwd", p_g, p_p, p_bias, p_hw, float(eps), p_o, p_s, dp.data_ptr(),
+              None if dbias is None else dbias.data_ptr(), dhead_w.data_ptr(), ws.data_ptr(), B, H, K, int(T), Tp, Np, _stream())
+    return dp, dbias, dhead_w
