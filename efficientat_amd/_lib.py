@@ -1,5 +1,5 @@
-"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h, include/eat_embed.h and
-include/eat_attn.h).
+"""ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h, include/eat_embed.h,
+include/eat_attn.h and include/eat_detect.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -24,6 +24,8 @@ TAG_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_tag.h")
 EMBED_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_embed.h")
 # the attention-pooling head's entry points (efficientat_amd/mn.py, mn_train.py): likewise
 ATTN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_attn.h")
+# sound event detection's entry points (efficientat_amd/detection.py): likewise
+DETECT_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_detect.h")
 
 
 class EatHipError(RuntimeError):
@@ -74,6 +76,8 @@ with open(EMBED_HEADER_PATH) as _f:
     EMBED_PROTOTYPES = parse_prototypes(_f.read())                     # likewise
 with open(ATTN_HEADER_PATH) as _f:
     ATTN_PROTOTYPES = parse_prototypes(_f.read())                      # likewise
+with open(DETECT_HEADER_PATH) as _f:
+    DETECT_PROTOTYPES = parse_prototypes(_f.read())                    # likewise
 
 _lib = None
 
@@ -88,7 +92,7 @@ def lib():
                 "Build it with `python -m efficientat_amd.build`.")
         h = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()) + list(EMBED_PROTOTYPES.items())
-                                          + list(ATTN_PROTOTYPES.items())):
+                                          + list(ATTN_PROTOTYPES.items()) + list(DETECT_PROTOTYPES.items())):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -2266,3 +2266,201 @@ def attn_pool_bwd(g, p, bias, head_w, o, s, H, T, eps=1e-7, Np=None, dp=None, db
     _lib.call("eat_attn_pool_bwd", p_g, p_p, p_bias, p_hw, float(eps), p_o, p_s, dp.data_ptr(),
               None if dbias is None else dbias.data_ptr(), dhead_w.data_ptr(), ws.data_ptr(), B, H, K, int(T), Tp, Np, _stream())
     return dp, dbias, dhead_w
+
+
+# ------------------------------------------------------------------ sound event detection (include/eat_detect.h)
+_DETECT_MAX_M = 31             # widest median of eat_detect_median
+
+
+class DetectTable:
+    """The validated recording table of the detection kernels: per recording (first window, window count, goff, G) -
+    its windows are rows [first, first + count) of the logits buffer, its G frames columns [goff, goff + G) of the
+    (K, G_total) timelines.  Built by `detect_table` on the host; `dev(device)` uploads it once per device."""
+
+    def __init__(self, rec):
+        self.cpu, self.n_rec, self.G_total, self._dev = rec, int(rec.shape[0]), int(rec[-1, 2] + rec[-1, 3]), {}
+
+    def dev(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self.cpu.to(device)
+        return self._dev[key]
+
+
+def detect_table(rec):
+    """Host-side validation of a recording table (CPU array (n_rec, 4) of integers: first window, window count, goff, G)
+    -> DetectTable.  first >= 0, count >= 1, G >= 1, goff[0] = 0 and goff[i + 1] = goff[i] + G[i]: the recordings tile
+    the timeline axis in order (the kernels bisect over goff), whose length stays below 2^31."""
+    fn = "detect_table"
+    try:
+        t = torch.as_tensor(rec)
+    except (ValueError, TypeError) as e:
+        raise _lib.EatHipError(f"{fn}: rec is ragged ({e})") from None
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != 4 or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise _lib.EatHipError(f"{fn}: rec must be an (n_rec >= 1, 4) table of integers (got {tuple(t.shape)}, {t.dtype})")
+    t = t.to(device="cpu", dtype=torch.int64)
+    first, count, goff, G = t.unbind(1)
+    if bool((first < 0).any()) or bool((count < 1).any()):
+        raise _lib.EatHipError(f"{fn}: rec needs first >= 0 and count >= 1 in every row")
+    if bool((G < 1).any()):
+        raise _lib.EatHipError(f"{fn}: rec needs G >= 1 in every row: a recording has at least one frame")
+    want = torch.cumsum(G, 0) - G
+    if not torch.equal(goff, want):
+        i = int((goff != want).nonzero()[0])
+        raise _lib.EatHipError(f"{fn}: rec row {i} has goff = {int(goff[i])}, but the recordings before it hold {int(want[i])} "
+                               f"frames: goff must be the running sum of G")
+    if int(G.sum()) >= 2 ** 31 or int((first + count).max()) >= 2 ** 31:
+        raise _lib.EatHipError(f"{fn}: rec holds {int(G.sum())} frames / {int((first + count).max())} windows: 2^31 or more")
+    return DetectTable(t.to(torch.int32).contiguous())
+
+
+def _detect_table(fn, table):
+    if not isinstance(table, DetectTable):
+        raise _lib.EatHipError(f"{fn}: table must be a DetectTable from ops.detect_table (got {type(table).__name__})")
+    return table
+
+
+def _overlaps(a, b):
+    if a.device != b.device:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def detect_weights(T, taper="triangle"):
+    """The window weights wt (T) float64 of `detect_stitch`: 'uniform' = ones, 'triangle' = min(j + 1, T - j)."""
+    import numpy as np
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"detect_weights: need T >= 1 (got {T})")
+    if taper == "uniform":
+        return np.ones(T, dtype=np.float64)
+    if taper == "triangle":
+        j = np.arange(T, dtype=np.float64)
+        return np.minimum(j + 1.0, T - j)
+    raise ValueError(f"detect_weights: taper must be 'uniform' or 'triangle' (got {taper!r})")
+
+
+def detect_stitch(p, table, Hf, T, wt, out=None):
+    """Frame logits p (N_w, K, Tp) of overlapping windows -> prob (K, G_total) fp32: per recording of `table` the
+    wt-weighted mean over its windows of sigmoid(p), column j of window q being frame q Hf + j (include/eat_detect.h).
+    wt (T) fp32 > 0 on p's device (`detect_weights`); pad columns [T, Tp) of p are never read."""
+    fn = "detect_stitch"
+    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: p must be a non-empty (N_w, K, Tp) tensor, got {tuple(getattr(p, 'shape', ()))}")
+    table = _detect_table(fn, table)
+    n_w, K, Tp = p.shape
+    Hf, T = int(Hf), int(T)
+    if not 1 <= T <= Tp:
+        raise _lib.EatHipError(f"{fn}: T={T} must lie in [1, Tp = {Tp}]")
+    if not 1 <= Hf <= T:
+        raise _lib.EatHipError(f"{fn}: Hf={Hf} must lie in [1, T = {T}]")
+    _glue_operand(p, f"{fn}: p", torch.float32, p)
+    p_wt = _glue_operand(wt, f"{fn}: wt", torch.float32, p, n=T)
+    first, count, _, G = table.cpu.to(torch.int64).unbind(1)
+    if int((first + count).max()) > n_w:
+        raise _lib.EatHipError(f"{fn}: table names window {int((first + count).max()) - 1}, p holds {n_w}")
+    short = ((count - 1) * Hf + T < G).nonzero()
+    if short.numel():
+        i = int(short[0])
+        raise _lib.EatHipError(f"{fn}: table row {i}: {int(count[i])} windows of {T} frames every {Hf} do not cover its "
+                               f"{int(G[i])} frames")
+    prob = _head_out(out, f"{fn}: out", (K, table.G_total), p)
+    if _overlaps(prob, p):
+        raise _lib.EatHipError(f"{fn}: out must not overlap p")
+    p_p = _on_gpu(p, f"{fn}: p")
+    _lib.call("eat_detect_stitch", p_p, n_w, K, Tp, table.dev(p.device).data_ptr(), table.n_rec, Hf, T, p_wt,
+              prob.data_ptr(), table.G_total, _stream())
+    return prob.view(K, table.G_total)
+
+
+def _timelines(fn, x, name, table):
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: {name} must be a non-empty (K, G_total) tensor, got {tuple(getattr(x, 'shape', ()))}")
+    table = _detect_table(fn, table)
+    if x.shape[1] != table.G_total:
+        raise _lib.EatHipError(f"{fn}: {name} has {x.shape[1]} columns, the table {table.G_total} frames")
+    _glue_operand(x, f"{fn}: {name}", torch.float32, x)
+    return table, x.shape[0]
+
+
+def detect_median(prob, table, m, out=None):
+    """Running median of odd width m (1 <= m <= 31) along time of prob (K, G_total), per class and per recording of
+    `table`, with periodic reflection at the recording's own ends -> filt (K, G_total).  out must not overlap prob."""
+    fn = "detect_median"
+    table, K = _timelines(fn, prob, "prob", table)
+    if isinstance(m, bool) or int(m) != m or not 1 <= int(m) <= _DETECT_MAX_M or int(m) % 2 == 0:
+        raise _lib.EatHipError(f"{fn}: m={m} must be an odd integer in [1, {_DETECT_MAX_M}]")
+    filt = _head_out(out, f"{fn}: out", (K, table.G_total), prob)
+    if _overlaps(filt, prob):
+        raise _lib.EatHipError(f"{fn}: out must not overlap prob (the filter reads its neighbours)")
+    p_x = _on_gpu(prob, f"{fn}: prob")
+    _lib.call("eat_detect_median", p_x, K, table.G_total, table.dev(prob.device).data_ptr(), table.n_rec, int(m),
+              filt.data_ptr(), _stream())
+    return filt.view(K, table.G_total)
+
+
+def check_thresholds(hi, lo, K):
+    """Host-side validation of per-class thresholds (CPU arrays of K values, or scalars): 0 < lo <= hi <= 1 ->
+    (hi, lo) contiguous fp32 CPU tensors of K values, compared as the fp32 numbers the kernel sees."""
+    fn = "detect_events"
+    out = []
+    for name, v in (("hi", hi), ("lo", lo)):
+        t = torch.as_tensor(v, dtype=torch.float32).cpu()
+        if t.dim() == 0:
+            t = t.expand(K)
+        if t.dim() != 1 or t.numel() != K:
+            raise _lib.EatHipError(f"{fn}: {name} must be a scalar or hold K = {K} values (got {tuple(t.shape)})")
+        out.append(t.contiguous())
+    hi_t, lo_t = out
+    if not bool(((lo_t > 0) & (lo_t <= hi_t) & (hi_t <= 1)).all()):           # (NaN fails every comparison)
+        raise _lib.EatHipError(f"{fn}: thresholds need 0 < lo <= hi <= 1 in every class")
+    return hi_t, lo_t
+
+
+def detect_events(filt, table, hi, lo, max_gap=0, min_len=0):
+    """Double-threshold events of every (recording, class) timeline of filt (K, G_total) (include/eat_detect.h) ->
+    (ev_i (E, 4) int32: recording, class, onset, exclusive offset in frames of the recording; ev_f (E, 2) fp32: peak and
+    mean of filt over the event), sorted by (recording, class, onset).  hi, lo: CPU arrays / scalars, validated by
+    `check_thresholds` and uploaded, or fp32 device tensors of K values that were.  Two launches with torch's cumsum and
+    one host read of the total between them; no event: empty tensors, no second launch."""
+    fn = "detect_events"
+    table, K = _timelines(fn, filt, "filt", table)
+    max_gap, min_len = int(max_gap), int(min_len)
+    if max_gap < 0 or min_len < 0:
+        raise _lib.EatHipError(f"{fn}: max_gap and min_len must not be negative (got {max_gap}, {min_len})")
+    if table.n_rec * K >= 2 ** 31:
+        raise _lib.EatHipError(f"{fn}: {table.n_rec} recordings x {K} classes: 2^31 timelines or more")
+    if not (isinstance(hi, torch.Tensor) and hi.is_cuda and isinstance(lo, torch.Tensor) and lo.is_cuda):
+        hi, lo = (t.to(filt.device) for t in check_thresholds(hi, lo, K))
+    p_hi = _glue_operand(hi, f"{fn}: hi", torch.float32, filt, n=K)
+    p_lo = _glue_operand(lo, f"{fn}: lo", torch.float32, filt, n=K)
+    p_x = _on_gpu(filt, f"{fn}: filt")
+    dev = filt.device
+    rec = table.dev(dev).data_ptr()
+    count = torch.empty((table.n_rec * K,), device=dev, dtype=torch.int64)
+    _lib.call("eat_detect_events_count", p_x, K, table.G_total, rec, table.n_rec, p_hi, p_lo, max_gap, min_len,
+              count.data_ptr(), _stream())
+    incl = torch.cumsum(count, 0)
+    E = int(incl[-1].item())                                   # the one host read
+    ev_i = torch.empty((E, 4), device=dev, dtype=torch.int32)
+    ev_f = torch.empty((E, 2), device=dev, dtype=torch.float32)
+    if E > 0:
+        _lib.call("eat_detect_events_write", p_x, K, table.G_total, rec, table.n_rec, p_hi, p_lo, max_gap, min_len,
+                  incl.data_ptr(), ev_i.data_ptr(), ev_f.data_ptr(), _stream())
+    return ev_i, ev_f
+
+
+def pw_conv_into(x, pack, Co, act, out):
+    """The 1x1 conv of `mn._pw` on a (packed weights, bias, mode) triple of `mn._pack_pw`, stored into the caller's
+    contiguous fp32 buffer `out` of B x Co x S elements (a slice of a larger buffer) instead of a fresh tensor."""
+    wp, bias, mode = pack
+    B, Ci, F, T = x.shape
+    p_out = _glue_operand(out, "pw_conv_into: out", torch.float32, x, n=B * Co * F * T)
+    if mode == "fp32":
+        _lib.call("eat_pw_conv_fwd", _dev(x, "x"), _dev(wp, "wp"), _dev(bias, "bias"), None, None, p_out, None, B, Ci, Co,
+                  F * T, act, _stream())
+    else:
+        _lib.call("eat_pw_conv_bf16_fwd", _dev(x, "x"), wp.data_ptr(), _dev(bias, "bias"), None, None, p_out, None, B, Ci, Co,
+                  F * T, act, 1 if mode == "bf16x3" else 0, _stream())
+    return out
