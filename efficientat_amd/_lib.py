@@ -1,5 +1,5 @@
 """ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h, include/eat_embed.h,
-include/eat_attn.h and include/eat_detect.h).
+include/eat_attn.h, include/eat_detect.h and include/eat_sed.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -26,6 +26,8 @@ EMBED_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_embed.h")
 ATTN_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_attn.h")
 # sound event detection's entry points (efficientat_amd/detection.py): likewise
 DETECT_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_detect.h")
+# strong-label SED training's entry points (efficientat_amd/sed.py, mn_train.FrameHead): likewise
+SED_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_sed.h")
 
 
 class EatHipError(RuntimeError):
@@ -78,6 +80,8 @@ with open(ATTN_HEADER_PATH) as _f:
     ATTN_PROTOTYPES = parse_prototypes(_f.read())                      # likewise
 with open(DETECT_HEADER_PATH) as _f:
     DETECT_PROTOTYPES = parse_prototypes(_f.read())                    # likewise
+with open(SED_HEADER_PATH) as _f:
+    SED_PROTOTYPES = parse_prototypes(_f.read())                       # likewise
 
 _lib = None
 
@@ -92,7 +96,8 @@ def lib():
                 "Build it with `python -m efficientat_amd.build`.")
         h = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()) + list(EMBED_PROTOTYPES.items())
-                                          + list(ATTN_PROTOTYPES.items()) + list(DETECT_PROTOTYPES.items())):
+                                          + list(ATTN_PROTOTYPES.items()) + list(DETECT_PROTOTYPES.items())
+                                          + list(SED_PROTOTYPES.items())):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

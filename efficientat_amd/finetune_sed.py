@@ -1,0 +1,156 @@
+"""Fine-tune an MN on strongly labelled sound events on the HIP path: frame-level training of what `detect` runs.
+
+    python -m efficientat_amd.finetune_sed --train_bank DIR --valid_bank DIR [--init_checkpoint mn10_as.pt] [--save sed.pt]
+
+Each DIR is a decoded strong-label split (sed.load_bank: waves.npy, lengths.npy, names.txt, classes.txt, events.npy,
+event_offsets.npy; tools/strong_to_bank.py writes one from WAV files and a `filename onset offset event_label` table).  Each
+step is one hipGraph replay of crop / pad + wave augmentation + frame targets -> mel -> mix-up -> trunk -> frame head ->
+frame BCE -> backward -> FusedAdam (sed.GraphedFrameBCETrainer; `--no_graph`: the eager FrameBCETrainer).  After every epoch
+the validation split is scored frame by frame (sed.evaluate_frames: frame mAP / ROC, segment-based F1 at `--threshold`,
+val_loss).  `--save` writes the final plain state dict: an mlp-head MN with K = the bank's classes, which
+`detection.EADetector(model=...)` and `python -m efficientat_amd.detect --checkpoint` accept.  `--init_checkpoint` loads a
+local state dict and drops its output layer when the class count differs (finetune.load_init_checkpoint).
+
+Augmentation arguments and the schedule are finetune_fsd50k's.  Only MN models with the mlp head, at 32 kHz.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+from .finetune_esc50 import build
+from .utils import exp_warmup_linear_down
+
+METRICS = ("frame_mAP", "frame_ROC", "micro_f1", "micro_precision", "micro_recall", "macro_f1", "macro_precision",
+           "macro_recall", "val_loss")
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="strong-label SED fine-tuning on the HIP path")
+    p.add_argument("--train_bank", required=True, help="decoded training split (sed.load_bank)")
+    p.add_argument("--valid_bank", required=True, help="decoded validation split, scored after every epoch")
+    p.add_argument("--init_checkpoint", default=None, help="state dict to start from (its output layer is re-sized)")
+    p.add_argument("--save", default=None, help="file for the final state dict (loads into EADetector / detect --checkpoint)")
+    p.add_argument("--threshold", type=float, default=0.5, help="probability at which a frame counts as active in the F1")
+    p.add_argument("--json", action="store_true", help="print one JSON line with the run's results at the end")
+    p.add_argument("--batch_size", type=int, default=64)
+    p.add_argument("--batch_windows", type=int, default=64, help="windows per evaluation chunk")
+    p.add_argument("--model_name", type=str, default="mn10_as")
+    p.add_argument("--model_width", type=float, default=1.0)
+    p.add_argument("--se_dims", type=str, default="c")
+    p.add_argument("--n_epochs", type=int, default=80)
+    p.add_argument("--mixup_alpha", type=float, default=0.3)
+    p.add_argument("--no_roll", action="store_true", default=False)
+    p.add_argument("--no_wavmix", action="store_true", default=False)
+    p.add_argument("--gain_augment", type=int, default=12)
+    p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--lr", type=float, default=7e-5)
+    p.add_argument("--warm_up_len", type=int, default=10)
+    p.add_argument("--ramp_down_start", type=int, default=10)
+    p.add_argument("--ramp_down_len", type=int, default=65)
+    p.add_argument("--last_lr_value", type=float, default=0.01)
+    p.add_argument("--window_size", type=int, default=800)
+    p.add_argument("--hop_size", type=int, default=320)
+    p.add_argument("--n_fft", type=int, default=1024)
+    p.add_argument("--n_mels", type=int, default=128)
+    p.add_argument("--freqm", type=int, default=0)
+    p.add_argument("--timem", type=int, default=0)
+    p.add_argument("--fmin", type=int, default=0)
+    p.add_argument("--fmax", type=int, default=None)
+    p.add_argument("--fmin_aug_range", type=int, default=10)
+    p.add_argument("--fmax_aug_range", type=int, default=2000)
+    p.add_argument("--clip_frames", type=int, default=32, help="frames per training clip and evaluation window (32 = 10.24 s)")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--no_graph", action="store_true", help="eager FrameBCETrainer instead of the captured step")
+    p.add_argument("--max_steps", type=int, default=0, help="stop after this many steps (benchmarks / tests); 0 = whole epochs")
+    p.add_argument("--precision", default=None, help="model.train_precision (auto / fp32 / bf16)")
+    args = p.parse_args(argv)
+    if args.model_name.startswith("dymn"):
+        p.error("frame-level training covers the static MobileNets (mn*) only")
+    if args.clip_frames < 1:
+        p.error("--clip_frames must be >= 1")
+    args.head_type, args.resample_rate, args.pretrain_final_temp = "mlp", 32000, 1.0
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("efficientat_amd.finetune_sed needs a GPU: the package has no CPU path")
+    from . import detection, sed
+    from .optim import FusedAdam
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    t_load = time.perf_counter()
+    train = sed.load_bank(args.train_bank, device=dev)
+    valid = sed.load_bank(args.valid_bank, device=dev)
+    t_load = time.perf_counter() - t_load
+    if train["classes"] != valid["classes"]:
+        raise SystemExit("finetune_sed: the two banks differ in classes.txt")
+    n_train, K = train["lengths"].numel(), len(train["classes"])
+    print(f"[finetune_sed] {n_train} training / {valid['lengths'].numel()} validation clips, {K} classes, "
+          f"{train['events'].shape[0]} / {valid['events'].shape[0]} events resident on {dev} ({t_load:.1f} s to load)",
+          file=sys.stderr, flush=True)
+    model, mel = build(args, dev, K)
+    L = args.clip_frames * detection.check_model(model)[1] * args.hop_size
+
+    graphed = not args.no_graph
+    lr = torch.tensor(args.lr, device=dev) if graphed else args.lr            # tensor lr: the schedule needs no re-capture
+    opt = FusedAdam(model.parameters(), lr=lr, weight_decay=args.weight_decay, capturable=graphed)
+    sched = torch.optim.lr_scheduler.LambdaLR(
+        opt, exp_warmup_linear_down(args.warm_up_len, args.ramp_down_len, args.ramp_down_start, args.last_lr_value))
+    model.train()
+    mel.train()
+    common = dict(clip_samples=L, mixup_alpha=args.mixup_alpha, gain_augment=args.gain_augment, roll=not args.no_roll,
+                  wavmix=not args.no_wavmix)
+    trainer = (sed.GraphedFrameBCETrainer(model, mel, opt, train, args.batch_size, **common) if graphed
+               else sed.FrameBCETrainer(model, mel, opt, train, **common))
+
+    steps_total, clips_total, t_train = 0, 0, 0.0
+    ev, stats, done = None, {"train_loss": float("nan")}, False
+    for epoch in range(args.n_epochs):
+        order = torch.randperm(n_train)                                       # shuffle, partial last batch
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_ep = 0
+        for s in range(0, n_train, args.batch_size):
+            batch = order[s:s + args.batch_size].tolist()
+            trainer.step(batch)
+            n_ep += 1
+            clips_total += len(batch)
+            if args.max_steps and steps_total + n_ep >= args.max_steps:
+                done = True
+                break
+        sched.step()
+        stats = trainer.epoch_stats()                                         # the one host sync of the epoch
+        torch.cuda.synchronize()
+        t_train += time.perf_counter() - t0
+        steps_total += n_ep
+        ev = sed.evaluate_frames(model, mel, valid, args.batch_windows, args.threshold, clip_samples=L)
+        print(f"[finetune_sed] epoch {epoch + 1}/{args.n_epochs}: {n_ep} steps, train_loss {stats['train_loss']:.5f}, "
+              f"frame mAP {ev['frame_mAP']:.4f}, ROC {ev['frame_ROC']:.4f}, micro F1 {ev['micro_f1']:.4f}, macro F1 "
+              f"{ev['macro_f1']:.4f}, val_loss {ev['val_loss']:.5f}, lr {float(sched.get_last_lr()[0]):.2e}", file=sys.stderr,
+              flush=True)
+        if done:
+            break
+    if args.save:
+        os.makedirs(os.path.dirname(os.path.abspath(args.save)), exist_ok=True)
+        torch.save(model.state_dict(), args.save)
+    if args.json:
+        line = {"what": "efficientat_amd.finetune_sed", "model": args.model_name, "classes": K, "steps": steps_total,
+                "epochs": epoch + 1, "batch_size": args.batch_size, "clip_samples": L,
+                "launch": "hipGraph replay" if graphed else "eager", "threshold": args.threshold,
+                "train_loss": stats["train_loss"], "clips_per_s": round(clips_total / max(t_train, 1e-9), 1),
+                "n_frames": ev["n_frames"], "eval_s": round(ev["eval_s"], 3), "checkpoint": args.save}
+        line.update({k: ev[k] for k in METRICS})
+        print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -27,32 +27,27 @@ CLIP_SECONDS = 10
 SAMPLE_RATE = 32000
 
 
-def load_bank(path, device=None):
-    """A decoded split (see the module header) -> dict(waves (S) fp32, offsets (N) int64, lengths (N) int32, clip_sum (N)
-    fp64, bank_y (N, 200) fp32 on `device` when given, else on the CPU; lengths_cpu (N) int64 CPU, names).  offsets =
-    the exclusive cumulative sum of lengths; clip_sum[i] = the fp64 sum of clip i's fp32 samples.  waves.npy is memory-mapped
-    while loading and converted in slices, so the host never holds a second fp32 copy.  The training split (about 37 k clips,
-    8e9 samples) is about 32 GB as fp32; int16 on disk halves the file, not the resident bank."""
+def read_waves(path, what):
+    """waves.npy (memory-mapped) and lengths.npy of a bank directory, checked -> (waves (S,) int16 / float32, lengths (N,)
+    int64); `what` names the bank in the ValueError of a violation."""
     waves = np.load(os.path.join(path, "waves.npy"), mmap_mode="r")
     lengths = np.load(os.path.join(path, "lengths.npy"))
-    targets = np.load(os.path.join(path, "targets.npy"))
-    with open(os.path.join(path, "names.txt")) as f:
-        names = f.read().splitlines()
     if waves.ndim != 1 or waves.dtype not in (np.int16, np.float32):
-        raise ValueError(f"FSD50K bank at {path}: waves.npy must be (S,) int16 or float32, got {waves.dtype} {waves.shape}")
+        raise ValueError(f"{what}: waves.npy must be (S,) int16 or float32, got {waves.dtype} {waves.shape}")
     if lengths.ndim != 1 or lengths.dtype.kind not in "iu":
-        raise ValueError(f"FSD50K bank at {path}: lengths.npy must be (N,) integers, got {lengths.dtype} {lengths.shape}")
+        raise ValueError(f"{what}: lengths.npy must be (N,) integers, got {lengths.dtype} {lengths.shape}")
     n = lengths.shape[0]
     lengths = lengths.astype(np.int64)
     if n == 0 or lengths.min() < 1 or lengths.max() >= 2 ** 31 or int(lengths.sum()) != waves.shape[0]:
-        raise ValueError(f"FSD50K bank at {path}: {n} lengths (each must be in [1, 2^31)) summing to "
+        raise ValueError(f"{what}: lengths.npy holds {n} lengths (each must be in [1, 2^31)) summing to "
                          f"{int(lengths.sum()) if n else 0} for {waves.shape[0]} samples")
-    if targets.ndim != 2 or targets.shape[1] != N_CLASSES or targets.dtype not in (np.uint8, np.float32):
-        raise ValueError(f"FSD50K bank at {path}: targets.npy must be (N, {N_CLASSES}) uint8 or float32, got {targets.dtype} "
-                         f"{targets.shape}")
-    if targets.shape[0] != n or len(names) != n:
-        raise ValueError(f"FSD50K bank at {path}: {n} lengths, {targets.shape[0]} target rows and {len(names)} names")
-    dev = torch.device("cpu") if device is None else device
+    return waves, lengths
+
+
+def resident_waves(waves, lengths, dev):
+    """The sample side of a ragged bank on `dev` from `read_waves`' pair -> dict(waves (S) fp32, offsets (N) int64, lengths (N)
+    int32, clip_sum (N) fp64 on `dev`, lengths_cpu (N) int64)."""
+    n = lengths.shape[0]
     offsets = np.concatenate(([0], np.cumsum(lengths)[:-1])).astype(np.int64)
     S = waves.shape[0]
     flat = torch.empty(S, dtype=torch.float32, device=dev)
@@ -72,8 +67,27 @@ def load_bank(path, device=None):
         for i in range(first, last):
             clip_sum[i] += float(xd[max(offsets[i], s) - s:min(ends[i], e) - s].sum())
     return dict(waves=flat, offsets=torch.from_numpy(offsets).to(dev), lengths=torch.from_numpy(lengths.astype(np.int32)).to(dev),
-                clip_sum=torch.from_numpy(clip_sum).to(dev), bank_y=torch.from_numpy(targets.astype(np.float32)).to(dev),
-                lengths_cpu=torch.from_numpy(lengths), names=names)
+                clip_sum=torch.from_numpy(clip_sum).to(dev), lengths_cpu=torch.from_numpy(lengths))
+
+
+def load_bank(path, device=None):
+    """A decoded split (see the module header) -> dict(waves (S) fp32, offsets (N) int64, lengths (N) int32, clip_sum (N)
+    fp64, bank_y (N, 200) fp32 on `device` when given, else on the CPU; lengths_cpu (N) int64 CPU, names).  offsets =
+    the exclusive cumulative sum of lengths; clip_sum[i] = the fp64 sum of clip i's fp32 samples.  waves.npy is memory-mapped
+    while loading and converted in slices, so the host never holds a second fp32 copy.  The training split (about 37 k clips,
+    8e9 samples) is about 32 GB as fp32; int16 on disk halves the file, not the resident bank."""
+    waves, lengths = read_waves(path, f"FSD50K bank at {path}")
+    n = lengths.shape[0]
+    targets = np.load(os.path.join(path, "targets.npy"))
+    with open(os.path.join(path, "names.txt")) as f:
+        names = f.read().splitlines()
+    if targets.ndim != 2 or targets.shape[1] != N_CLASSES or targets.dtype not in (np.uint8, np.float32):
+        raise ValueError(f"FSD50K bank at {path}: targets.npy must be (N, {N_CLASSES}) uint8 or float32, got {targets.dtype} "
+                         f"{targets.shape}")
+    if targets.shape[0] != n or len(names) != n:
+        raise ValueError(f"FSD50K bank at {path}: {n} lengths, {targets.shape[0]} target rows and {len(names)} names")
+    dev = torch.device("cpu") if device is None else device
+    return dict(resident_waves(waves, lengths, dev), bank_y=torch.from_numpy(targets.astype(np.float32)).to(dev), names=names)
 
 
 def _fetch(length, L, gain_augment, roll, shift_range):

@@ -699,6 +699,119 @@ def attention_pool_head(head, y):
                                    head.epsilon)
 
 
+class FrameHead(torch.autograd.Function):
+    """The mlp head applied to every time column of the last feature map (what `detection.frame_logits` runs in eval), in the
+    layout of the 1x1 kernels: y (B, C, F, T) -> frame logits (B, K, Tp), Tp = `ops.pitch4(T)`.  keep (B, H) or None: the
+    dropout factor of a (clip, hidden unit), shared by the clip's frames.
+
+    forward:  `ops.freq_mean` -> fc1 as a 1x1 conv over the Tp positions, bias in its epilogue (`ops.pw_conv`, pack by the
+              active `ops.precision`) -> `ops.frame_hidden_fwd` (Hardswish, keep) -> fc2 likewise
+    backward: `ops.frame_grad_pad` (the arriving gradient with exactly-zero pad rows and columns, and db2) ->
+              `ops.pw_conv_wgrad(dl, h)` -> dh on the conv kernel with the transposed pack -> `ops.frame_hidden_bwd` (dz1,
+              db1) -> `ops.pw_conv_wgrad(dz1, xm)` -> dxm likewise -> `ops.freq_mean_bwd`
+    Hidden rows are zero-padded to a multiple of 4 (hswish(0) = 0 against zero columns of fc2: nothing changes), as
+    `detection._head_packs` pads them; the data-gradient GEMM of fc2 contracts over `pitch4(K)` rows of dl.  Pad columns
+    [T, Tp) of the logits hold the head's answer to a zero column: callers must not read them."""
+
+    @staticmethod
+    def forward(ctx, y, w1, b1, w2, b2, keep):
+        y = y.contiguous()
+        B, C, Fq, T = y.shape
+        H, K = w1.shape[0], w2.shape[0]
+        Hp, Tp = ops.pitch4(H), ops.pitch4(T)
+        w1p, b1p = w1.detach().contiguous(), b1.detach().contiguous()
+        w2p = w2.detach().contiguous()
+        if keep is not None:
+            keep = keep.detach().contiguous().float()
+        if Hp != H:
+            w1p = torch.cat((w1p, w1p.new_zeros((Hp - H, C))))
+            b1p = torch.cat((b1p, b1p.new_zeros(Hp - H)))
+            w2p = torch.cat((w2p, w2p.new_zeros((K, Hp - H))), dim=1)
+            if keep is not None:
+                keep = torch.cat((keep, keep.new_ones((B, Hp - H))), dim=1)
+        xm = ops.freq_mean(y, Tp)
+        z1 = ops.pw_conv(xm.view(B, C, 1, Tp), ops.pw_prepack(w1p), b1p, Hp, NONE).view(B, Hp, Tp)
+        h = ops.frame_hidden_fwd(z1, keep)
+        z = ops.pw_conv(h.view(B, Hp, 1, Tp), ops.pw_prepack(w2p), b2.detach().contiguous(), K, NONE).view(B, K, Tp)
+        ctx.save_for_backward(xm, z1, h, w1p, w2p, keep)
+        ctx.geo, ctx.prec = (Fq, T, H, K), ops.precision.mode
+        return z
+
+    @staticmethod
+    def backward(ctx, g):
+        xm, z1, h, w1p, w2p, keep = ctx.saved_tensors
+        Fq, T, H, K = ctx.geo
+        B, C, Tp = xm.shape
+        Hp, Kp = z1.shape[1], ops.pitch4(K)
+        dev = xm.device
+        with ops.precision(ctx.prec), ops.zero_arena.scope("frame_head_bwd"):
+            # (the zero-filled memory first: the pass's one fill precedes the head's own launches)
+            dw2 = ops.zero_arena.zeros((Kp, Hp), torch.float32, dev)
+            dw1 = ops.zero_arena.zeros((Hp, C), torch.float32, dev)
+            w2t = w2p
+            if Kp != K:
+                w2t = ops.zero_arena.zeros((Kp, Hp), torch.float32, dev)
+                w2t[:K].copy_(w2p)
+            # whatever autograd hands over (the fused loss's gradient times a scalar, or any other): pads re-established
+            dl, db2 = ops.frame_grad_pad(g.contiguous().float(), T, Kp)
+            dl4, h4, xm4 = dl.view(B, Kp, 1, Tp), h.view(B, Hp, 1, Tp), xm.view(B, C, 1, Tp)
+            dw2 = ops.pw_conv_wgrad(dl4, h4, exact=None, out=dw2)[:K, :H]
+            dh = ops.pw_conv(dl4, ops.pw_prepack(w2t, trans=True), ops.zeros_vec.get(Hp, dev), Hp, NONE)
+            dz1, db1 = ops.frame_hidden_bwd(dh.view(B, Hp, Tp), z1, keep, H, T)
+            dz4 = dz1.view(B, Hp, 1, Tp)
+            dw1 = ops.pw_conv_wgrad(dz4, xm4, exact=None, out=dw1)[:H]
+            dy = None
+            if ctx.needs_input_grad[0]:
+                dxm = ops.pw_conv(dz4, ops.pw_prepack(w1p, trans=True), ops.zeros_vec.get(C, dev), C, NONE)
+                dy = ops.freq_mean_bwd(dxm.view(B, C, Tp), Fq, T)
+        return dy, dw1, db1, (dw2 if Hp == H else dw2.contiguous()), db2, None
+
+
+def _frame_scope(model):
+    """What `forward_train_frames` covers: an MN with the mlp head on the monolithic plan.  Everything else: ValueError."""
+    from .mn import MN as _MN
+    if not isinstance(model, _MN):
+        raise ValueError(f"forward_train_frames: {type(model).__name__} is not an MN: the frame-level training path covers the "
+                         "static MobileNets only (a DyMN's trunk has no Function that hands back a differentiable last map)")
+    head = model.head_type
+    if head == "multihead_attention_pooling":
+        raise ValueError("forward_train_frames: the multihead_attention_pooling head has no frame-level logits (its attention "
+                         "is normalised over the whole clip)")
+    if head == "fully_convolutional":
+        raise ValueError("forward_train_frames: the fully_convolutional head carries a BatchNorm whose train-mode statistics "
+                         "would have to span the frames of the batch; train the 'mlp' head")
+    if head != "mlp":
+        raise ValueError(f"forward_train_frames: head_type {head!r} has no frame-level plan")
+    if model._modular_train:
+        raise ValueError("forward_train_frames: this MN trains on the modular plan (dilated blocks or squeeze-excitation "
+                         "beyond the channel axis), which has no trunk Function; only the monolithic plan is covered")
+
+
+def forward_train_frames(model, x):
+    """Train-mode frame logits (B, K, Tp) of an mlp-head MN under autograd: the trunk Function up to the last feature map
+    (`MNTrainFunction2`, mode 1) and `FrameHead` on it.  Dropout (classifier[4]) is one keep value per (clip, hidden
+    unit), shared by that clip's frames, drawn as `forward_train` draws its mask (`_drop_mask_override` replaces the draw)
+    and scaled by 1 / (1 - p).  Frame t of the logits is column t < T = the last map's width; columns [T, Tp) are padding."""
+    _frame_scope(model)
+    if not model.training:
+        raise ValueError("forward_train_frames needs the model in train mode (model.train()); `detection.frame_logits` is the "
+                         "eval path")
+    drop = model.classifier[4]
+    keep = None
+    if drop.p > 0 and drop.training:
+        n_hidden = model.classifier[2].out_features
+        keep = torch.empty((x.shape[0], n_hidden), device=x.device).bernoulli_(1.0 - drop.p) / (1.0 - drop.p)
+    override = getattr(model, "_drop_mask_override", None)       # tests replay the reference's mask
+    if override is not None and drop.training:
+        keep = override.to(x.device).float() / (1.0 - drop.p)
+    params = [p for _, p in model.named_parameters()]
+    model._eat_trunk_active = True        # the head's gradients reach its parameters through autograd (forward_train)
+    fc1, fc2 = model.classifier[2], model.classifier[5]
+    with ops.precision(getattr(model, "train_precision", "fp32")), ops.bn_counters, ops.zero_arena.scope("mn_fwd"):
+        y_l = MNTrainFunction2.apply(model, x, None, 1, *params)[0]
+        return FrameHead.apply(y_l, fc1.weight, fc1.bias, fc2.weight, fc2.bias, keep)
+
+
 def forward_train(model, x, return_fmaps=False):
     """Train-mode `(logits, features)` - or `(logits, fmaps)` - with autograd support (mn/model.py:212-231 in `.train()`).
 

@@ -2464,3 +2464,156 @@ def pw_conv_into(x, pack, Co, act, out):
         _lib.call("eat_pw_conv_bf16_fwd", _dev(x, "x"), wp.data_ptr(), _dev(bias, "bias"), None, None, p_out, None, B, Ci, Co,
                   F * T, act, 1 if mode == "bf16x3" else 0, _stream())
     return out
+
+
+# ------------------------------------------------------------------ strong-label SED training (include/eat_sed.h)
+def check_eval_draws(idx, start, lengths_cpu):
+    """Host-side validation of evaluation tables of `sed_targets` (CPU tensors of 2B values): primary rows in [0, N),
+    partners in [-1, N) and 0 <= start < length for every slot in use (an evaluation window may be padded)."""
+    idx, start = torch.as_tensor(idx), torch.as_tensor(start)
+    lengths = torch.as_tensor(lengths_cpu).to(torch.int64)
+    n_bank = lengths.numel()
+    if idx.numel() % 2 or idx.numel() == 0 or idx.numel() != start.numel():
+        raise ValueError(f"sed_targets: idx / start must hold 2B values each (got {idx.numel()}, {start.numel()})")
+    prim, part = idx[0::2], idx[1::2]
+    if bool(((prim < 0) | (prim >= n_bank)).any()) or bool(((part < -1) | (part >= n_bank)).any()):
+        raise ValueError(f"sed_targets: a bank index lies outside [0, {n_bank}) (partners may be -1)")
+    used = idx >= 0
+    st = start[used].to(torch.int64)
+    if bool(((st < 0) | (st >= lengths[idx[used].long()])).any()):
+        raise ValueError("sed_targets: a window start lies outside its clip")
+
+
+def sed_targets(bank, idx, start, shift, mix, L, R, T, Tp=None, out=None, train=True):
+    """Frame targets y (B, K, Tp) of the batch that `wave_augment_ragged` builds from the same tables (include/eat_sed.h:
+    eat_sed_targets).  bank: the dict of `sed.load_bank` (events (E, 3) int32, event_offsets (N + 1) int64, lengths on the
+    device, lengths_cpu, classes).  idx / start / shift (2B) int32, mix (B) fp32: CPU tensors are validated here -
+    `check_ragged_draws` with train=True, `check_eval_draws` (0 <= start < length) otherwise - and uploaded; device tensors
+    (the static buffers of a captured step) must have been validated before they were staged.  L samples per window, R per
+    frame, T frames, Tp >= T the row pitch (default `pitch4(T)`)."""
+    fn = "sed_targets"
+    events, eo, lengths = bank["events"], bank["event_offsets"], bank["lengths"]
+    n_bank, K = lengths.numel(), len(bank["classes"])
+    L, R, T = int(L), int(R), int(T)
+    Tp = pitch4(T) if Tp is None else int(Tp)
+    B = torch.as_tensor(mix).numel()
+    dev = lengths.device
+    if L < 1 or R < 1 or T < 1 or Tp < T or B < 1:
+        raise _lib.EatHipError(f"{fn}: need B, L, R, T >= 1 and Tp >= T (got B={B} L={L} R={R} T={T} Tp={Tp})")
+    if not idx.is_cuda:
+        if train:
+            check_ragged_draws(idx, start, shift, bank["lengths_cpu"], L)
+        else:
+            check_eval_draws(idx, start, bank["lengths_cpu"])
+            if torch.as_tensor(shift).numel() != 2 * B or bool((torch.as_tensor(shift).abs() >= L).any()):
+                raise ValueError(f"{fn}: shift must hold 2B values inside (-{L}, {L})")
+        idx, start, shift = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, start, shift))
+        mix = mix.to(dev, torch.float32, non_blocking=True)
+    if (events.dtype != torch.int32 or events.dim() != 2 or events.shape[1] != 3 or not events.is_contiguous()
+            or events.device != dev):
+        raise _lib.EatHipError(f"{fn}: events must be a contiguous (E, 3) int32 tensor on {dev}")
+    if eo.dtype != torch.int64 or eo.numel() != n_bank + 1 or not eo.is_contiguous() or eo.device != dev:
+        raise _lib.EatHipError(f"{fn}: event_offsets must be a contiguous int64 tensor of N + 1 = {n_bank + 1} values on {dev}")
+    p_mix = _glue_operand(mix, f"{fn}: mix", torch.float32, lengths, n=B)
+    y = _head_out(out, f"{fn}: out", (B, K, Tp), lengths)
+    E = events.shape[0]
+    _lib.call("eat_sed_targets", events.data_ptr() if E else None, E, eo.data_ptr(), _dev_int32(lengths, "lengths", n_bank), n_bank,
+              K, _dev_int32(idx, "idx", 2 * B), _dev_int32(start, "start", 2 * B), _dev_int32(shift, "shift", 2 * B), p_mix, B,
+              L, R, T, Tp, _on_gpu(y, f"{fn}: out"), _stream())
+    return y.view(B, K, Tp)
+
+
+def frame_bce_fwd_bwd(z, y, T, perm=None, lam=None, nframes=None, sums=None, grad=True, Kp=None, dbias=False, counts=None,
+                      thr=None, rows=None):
+    """Frame-level BCE-with-logits of z (B, K, Tp) against y (B, K, Tp) over the frames t < T (t < nframes[b] with `nframes`
+    (B) int32), the log-mel mix-up of the targets folded in (include/eat_sed.h: eat_frame_bce_fwd_bwd).
+    -> (dlogits (B, Kp, Tp) or None with grad=False, dbias (K) or None): d mean-loss / d z with exactly-zero pad rows and
+    columns.  `sums` (>= 1 fp32) += the mean; `counts` (K, 3) int64 += (tp, fp, fn) of sigmoid(z) >= thr (K) against
+    y > 0.5 (not with perm); `rows` (B T, K) fp32 receives the logits as the row-major score matrix of `metrics.ap_auc`."""
+    fn = "frame_bce_fwd_bwd"
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: z must be a non-empty (B, K, Tp) tensor, got {tuple(getattr(z, 'shape', ()))}")
+    B, K, Tp = z.shape
+    T = int(T)
+    Kp = K if Kp is None else int(Kp)
+    if T < 1 or Tp < T or Kp < K:
+        raise _lib.EatHipError(f"{fn}: need 1 <= T <= Tp and Kp >= K (got T={T} Tp={Tp} K={K} Kp={Kp})")
+    _glue_operand(z, f"{fn}: z", torch.float32, z)
+    p_y = _glue_operand(y, f"{fn}: y", torch.float32, z, n=B * K * Tp)
+    p_perm, p_lam = _mix_operands(fn, perm, lam, B, z)
+    p_nf = None if nframes is None else _glue_operand(nframes, f"{fn}: nframes", torch.int32, z, n=B)
+    p_counts = p_thr = None
+    if counts is not None:
+        if perm is not None:
+            raise _lib.EatHipError(f"{fn}: counts are taken against unmixed targets (perm given)")
+        if thr is None:
+            raise _lib.EatHipError(f"{fn}: counts need thr")
+        p_counts = _glue_operand(counts, f"{fn}: counts", torch.int64, z, n=3 * K)
+        p_thr = _glue_operand(thr, f"{fn}: thr", torch.float32, z, n=K)
+    p_rows = None if rows is None else _glue_operand(rows, f"{fn}: rows", torch.float32, z, n=B * T * K)
+    p_sums = ws = None
+    if sums is not None:
+        p_sums = _glue_operand(sums, f"{fn}: sums", torch.float32, z, at_least=1)
+        ws = torch.empty(K + 1, device=z.device, dtype=torch.float64)
+    dl = torch.empty((B, Kp, Tp), device=z.device, dtype=torch.float32) if grad else None
+    db = torch.empty((K,), device=z.device, dtype=torch.float32) if dbias else None
+    _lib.call("eat_frame_bce_fwd_bwd", _on_gpu(z, f"{fn}: z"), p_y, p_perm, p_lam, p_nf, p_thr, B, K, T, Tp, Kp, p_sums,
+              None if dl is None else dl.data_ptr(), None if db is None else db.data_ptr(), p_counts, p_rows,
+              None if ws is None else ws.data_ptr(), _stream())
+    return dl, db
+
+
+def frame_grad_pad(g, T, Kp=None, out=None):
+    """A gradient g (B, K, Tp) arriving at frame logits -> (dl (B, Kp, Tp): g with rows [K, Kp) and columns [T, Tp) exactly
+    zero, db (K) = the sum of g over (b, t < T), fp64 inside, fixed order) (include/eat_sed.h: eat_frame_grad_pad).  out:
+    the (B, Kp, Tp) buffer to store dl into."""
+    fn = "frame_grad_pad"
+    if not isinstance(g, torch.Tensor) or g.dim() != 3 or g.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: g must be a non-empty (B, K, Tp) tensor, got {tuple(getattr(g, 'shape', ()))}")
+    B, K, Tp = g.shape
+    T = int(T)
+    Kp = K if Kp is None else int(Kp)
+    if T < 1 or Tp < T or Kp < K:
+        raise _lib.EatHipError(f"{fn}: need 1 <= T <= Tp and Kp >= K (got T={T} Tp={Tp} K={K} Kp={Kp})")
+    _glue_operand(g, f"{fn}: g", torch.float32, g)
+    dl = _head_out(out, f"{fn}: out", (B, Kp, Tp), g)
+    db = torch.empty((K,), device=g.device, dtype=torch.float32)
+    _lib.call("eat_frame_grad_pad", _on_gpu(g, f"{fn}: g"), dl.data_ptr(), db.data_ptr(), B, K, Kp, T, Tp, _stream())
+    return dl.view(B, Kp, Tp), db
+
+
+def _keep_operand(fn, keep, B, Hp, like):
+    return None if keep is None else _glue_operand(keep, f"{fn}: keep", torch.float32, like, n=B * Hp)
+
+
+def frame_hidden_fwd(z1, keep=None):
+    """h = hswish(z1) keep[b, j] over z1 (B, Hp, Tp); keep (B, Hp) or None (include/eat_sed.h: eat_frame_hidden_fwd)."""
+    fn = "frame_hidden_fwd"
+    if not isinstance(z1, torch.Tensor) or z1.dim() != 3 or z1.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: z1 must be a non-empty (B, Hp, Tp) tensor, got {tuple(getattr(z1, 'shape', ()))}")
+    B, Hp, Tp = z1.shape
+    _glue_operand(z1, f"{fn}: z1", torch.float32, z1)
+    p_keep = _keep_operand(fn, keep, B, Hp, z1)
+    h = torch.empty_like(z1)
+    _lib.call("eat_frame_hidden_fwd", _on_gpu(z1, f"{fn}: z1"), p_keep, h.data_ptr(), B, Hp, Tp, _stream())
+    return h
+
+
+def frame_hidden_bwd(dh, z1, keep, H, T):
+    """-> (dz1 (B, Hp, Tp) = dh keep hswish'(z1), exactly zero in rows [H, Hp) and columns [T, Tp); db1 (H) = its sum over
+    (b, t), fp64 inside, fixed order) (include/eat_sed.h: eat_frame_hidden_bwd)."""
+    fn = "frame_hidden_bwd"
+    if not isinstance(z1, torch.Tensor) or z1.dim() != 3 or z1.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: z1 must be a non-empty (B, Hp, Tp) tensor, got {tuple(getattr(z1, 'shape', ()))}")
+    B, Hp, Tp = z1.shape
+    H, T = int(H), int(T)
+    if H < 1 or T < 1 or Hp < H or Tp < T:
+        raise _lib.EatHipError(f"{fn}: need 1 <= H <= Hp and 1 <= T <= Tp (got H={H} Hp={Hp} T={T} Tp={Tp})")
+    _glue_operand(z1, f"{fn}: z1", torch.float32, z1)
+    p_dh = _glue_operand(dh, f"{fn}: dh", torch.float32, z1, n=B * Hp * Tp)
+    p_keep = _keep_operand(fn, keep, B, Hp, z1)
+    dz1 = torch.empty_like(z1)
+    db1 = torch.empty((H,), device=z1.device, dtype=torch.float32)
+    _lib.call("eat_frame_hidden_bwd", p_dh, _on_gpu(z1, f"{fn}: z1"), p_keep, dz1.data_ptr(), db1.data_ptr(), B, H, Hp, T, Tp,
+              _stream())
+    return dz1, db1
