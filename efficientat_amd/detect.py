@@ -3,11 +3,14 @@
     python -m efficientat_amd.detect --audio_path A.wav [B.wav ...] --model mn10_as | --checkpoint F.pt [--width 1.0]
                                      [--labels_csv class_labels_indices.csv] [--window_size 10.24 --hop_length 5.12]
                                      [--median_ms 960 --threshold 0.5 --low_threshold 0.3 --min_duration_ms 0 --max_gap_ms 0]
-                                     [--json | --out events.tsv]
+                                     [--thresholds_file ops.json] [--json | --out events.tsv]
 
 Prints one line per event (file, onset and offset in seconds, label, peak and mean probability); with --json one line per
 file: {"audio_path": ..., "events": [{"label", "onset", "offset", "peak", "mean"}]}; with --out writes the DCASE
 tab-separated columns `filename onset offset event_label`, sorted by file, onset, offset and label.
+--thresholds_file takes the per-class operating points that `finetune_sed --save_thresholds` / `score_sed` write
+(sed.load_operating_points): its thresholds, post-processing values and labels become this run's defaults; a flag given
+on the command line still wins.
 """
 import argparse
 import contextlib
@@ -30,19 +33,33 @@ def main(argv=None):
     p.add_argument("--checkpoint", type=str, default=None, help="state dict of an MN model, instead of --model")
     p.add_argument("--width", type=float, default=None, help="width multiplier of --checkpoint (default: from --model)")
     p.add_argument("--audio_path", type=str, nargs="+", required=True, help="WAV files")
-    p.add_argument("--window_size", type=float, default=10.24, help="window size in seconds (a multiple of 0.32)")
-    p.add_argument("--hop_length", type=float, default=5.12, help="window hop in seconds (a multiple of 0.32)")
-    p.add_argument("--median_ms", type=float, default=960.0, help="width of the median filter")
-    p.add_argument("--threshold", type=float, default=0.5, help="a run of frames must reach it to be an event")
+    p.add_argument("--window_size", type=float, default=None, help="window size in seconds (a multiple of 0.32; default 10.24)")
+    p.add_argument("--hop_length", type=float, default=None, help="window hop in seconds (a multiple of 0.32; default 5.12)")
+    p.add_argument("--median_ms", type=float, default=None, help="width of the median filter (default 960)")
+    p.add_argument("--threshold", type=float, default=None, help="a run of frames must reach it to be an event (default 0.5)")
     p.add_argument("--low_threshold", type=float, default=None, help="a run lasts while frames stay at or above it")
-    p.add_argument("--min_duration_ms", type=float, default=0.0, help="shorter events are dropped")
-    p.add_argument("--max_gap_ms", type=float, default=0.0, help="events at most this far apart are merged")
-    p.add_argument("--taper", type=str, default="triangle", choices=["triangle", "uniform"])
+    p.add_argument("--min_duration_ms", type=float, default=None, help="shorter events are dropped (default 0)")
+    p.add_argument("--max_gap_ms", type=float, default=None, help="events at most this far apart are merged (default 0)")
+    p.add_argument("--taper", type=str, default=None, choices=["triangle", "uniform"], help="default triangle")
+    p.add_argument("--thresholds_file", type=str, default=None,
+                   help="per-class operating points (sed.save_operating_points): the defaults of this run")
     p.add_argument("--labels_csv", type=str, default=None, help="index,mid,display_name CSV; default: class indices")
     p.add_argument("--batch_windows", type=int, default=64)
     p.add_argument("--json", action="store_true", help="one JSON line per file")
     p.add_argument("--out", type=str, default=None, help="write the DCASE columns filename onset offset event_label here")
     args = p.parse_args(argv)
+    points = None
+    if args.thresholds_file:
+        from .sed import load_operating_points
+        points = load_operating_points(args.thresholds_file)
+    defaults = dict(window_size=10.24, hop_length=5.12, median_ms=960.0, threshold=0.5, min_duration_ms=0.0, max_gap_ms=0.0,
+                    taper="triangle")
+    file_low = args.low_threshold is None and args.threshold is None and points is not None
+    for name, value in defaults.items():                     # a flag, else the file's value, else the default
+        if getattr(args, name) is None:
+            setattr(args, name, value if points is None else points[name])
+    if file_low:                                             # (an explicit --threshold alone means low = high, as without a file)
+        args.low_threshold = points["low_threshold"]
 
     labels = read_labels(args.labels_csv) if args.labels_csv else None
     kw = dict(labels=labels, batch_windows=args.batch_windows, clip_seconds=args.window_size, hop_seconds=args.hop_length,
@@ -56,6 +73,11 @@ def main(argv=None):
         detector = EADetector(model=model.eval(), **kw)
     else:
         detector = EADetector(model_name=args.model, **kw)
+    if points is not None and len(points["classes"]) != detector.num_classes:
+        raise SystemExit(f"detect: {args.thresholds_file} holds {len(points['classes'])} classes, the model "
+                         f"{detector.num_classes}")
+    if points is not None and labels is None:
+        detector.labels = list(points["classes"])
 
     waves = [detector.load_waveform(path) for path in args.audio_path]
     found = detector.detect(waves, threshold=args.threshold, low_threshold=args.low_threshold, median_ms=args.median_ms,

@@ -7,7 +7,9 @@ event_offsets.npy; tools/strong_to_bank.py writes one from WAV files and a `file
 step is one hipGraph replay of crop / pad + wave augmentation + frame targets -> mel -> mix-up -> trunk -> frame head ->
 frame BCE -> backward -> FusedAdam (sed.GraphedFrameBCETrainer; `--no_graph`: the eager FrameBCETrainer).  After every epoch
 the validation split is scored frame by frame (sed.evaluate_frames: frame mAP / ROC, segment-based F1 at `--threshold`,
-val_loss).  `--save` writes the final plain state dict: an mlp-head MN with K = the bank's classes, which
+val_loss); with `--event_eval` also event by event (sed.evaluate_events: collar-based F1 at a grid of thresholds, the
+post-processing of `detect` given by `--median_ms --min_duration_ms --max_gap_ms --low_ratio`), and `--save_thresholds FILE`
+writes the per-class operating points of the last validation for `detect --thresholds_file`.  `--save` writes the final plain state dict: an mlp-head MN with K = the bank's classes, which
 `detection.EADetector(model=...)` and `python -m efficientat_amd.detect --checkpoint` accept.  `--init_checkpoint` loads a
 local state dict and drops its output layer when the class count differs (finetune.load_init_checkpoint).
 
@@ -27,6 +29,36 @@ from .utils import exp_warmup_linear_down
 
 METRICS = ("frame_mAP", "frame_ROC", "micro_f1", "micro_precision", "micro_recall", "macro_f1", "macro_precision",
            "macro_recall", "val_loss")
+
+
+EVENT_KEYS = ("event_threshold", "event_micro_f1", "event_micro_precision", "event_micro_recall", "event_macro_f1",
+              "event_macro_precision", "event_macro_recall", "event_macro_f1_best", "event_best_threshold", "event_collar_ms",
+              "event_offset_pct", "event_eval_s", "thresholds_file")
+
+
+def add_event_args(p):
+    """The arguments of event-based scoring (sed.evaluate_events), shared with score_sed."""
+    p.add_argument("--collar_ms", type=float, default=200.0, help="onset collar, and the floor of the offset collar")
+    p.add_argument("--offset_pct", type=float, default=0.2, help="offset collar as a fraction of the reference's length")
+    p.add_argument("--median_ms", type=float, default=960.0, help="median filter of the scored detector")
+    p.add_argument("--min_duration_ms", type=float, default=0.0, help="its minimum event length")
+    p.add_argument("--max_gap_ms", type=float, default=0.0, help="its merge gap")
+    p.add_argument("--low_ratio", type=float, default=1.0, help="low threshold as a fraction of the threshold")
+    p.add_argument("--save_thresholds", default=None, help="file for the per-class operating points (detect --thresholds_file)")
+
+
+def event_eval(args, model, mel, bank):
+    """`sed.evaluate_events` with the command line's settings -> (its result, the JSON line's keys)."""
+    from . import sed
+    ev = sed.evaluate_events(model, mel, bank, low_ratio=args.low_ratio, median_ms=args.median_ms,
+                             min_duration_ms=args.min_duration_ms, max_gap_ms=args.max_gap_ms, collar_ms=args.collar_ms,
+                             offset_pct=args.offset_pct, threshold=args.threshold, batch_windows=args.batch_windows)
+    keys = {"event_threshold": ev["threshold"]}
+    keys.update({"event_" + k: ev[k] for k in sed.SCORE_NAMES})
+    keys.update({"event_macro_f1_best": ev["macro_f1_best"], "event_best_threshold": [float(v) for v in ev["best_threshold"]],
+                 "event_collar_ms": args.collar_ms, "event_offset_pct": args.offset_pct, "event_eval_s": round(ev["eval_s"], 3),
+                 "thresholds_file": args.save_thresholds})
+    return ev, keys
 
 
 def parse_args(argv=None):
@@ -68,7 +100,11 @@ def parse_args(argv=None):
     p.add_argument("--no_graph", action="store_true", help="eager FrameBCETrainer instead of the captured step")
     p.add_argument("--max_steps", type=int, default=0, help="stop after this many steps (benchmarks / tests); 0 = whole epochs")
     p.add_argument("--precision", default=None, help="model.train_precision (auto / fp32 / bf16)")
+    add_event_args(p)
+    p.add_argument("--event_eval", action="store_true", help="also score the validation split event by event (collar F1)")
     args = p.parse_args(argv)
+    if args.save_thresholds and not args.event_eval:
+        p.error("--save_thresholds needs --event_eval")
     if args.model_name.startswith("dymn"):
         p.error("frame-level training covers the static MobileNets (mn*) only")
     if args.clip_frames < 1:
@@ -114,6 +150,7 @@ def main(argv=None):
 
     steps_total, clips_total, t_train = 0, 0, 0.0
     ev, stats, done = None, {"train_loss": float("nan")}, False
+    ee, ee_keys = None, {}
     for epoch in range(args.n_epochs):
         order = torch.randperm(n_train)                                       # shuffle, partial last batch
         torch.cuda.synchronize()
@@ -137,8 +174,15 @@ def main(argv=None):
               f"frame mAP {ev['frame_mAP']:.4f}, ROC {ev['frame_ROC']:.4f}, micro F1 {ev['micro_f1']:.4f}, macro F1 "
               f"{ev['macro_f1']:.4f}, val_loss {ev['val_loss']:.5f}, lr {float(sched.get_last_lr()[0]):.2e}", file=sys.stderr,
               flush=True)
+        if args.event_eval:
+            ee, ee_keys = event_eval(args, model, mel, valid)
+            print(f"[finetune_sed] events at {ee['threshold']:.2f}: micro F1 {ee['micro_f1']:.4f}, macro F1 {ee['macro_f1']:.4f}; "
+                  f"macro F1 at the per-class best thresholds (tuned on this split) {ee['macro_f1_best']:.4f} "
+                  f"({ee['eval_s']:.2f} s)", file=sys.stderr, flush=True)
         if done:
             break
+    if args.save_thresholds and ee is not None:
+        sed.save_operating_points(args.save_thresholds, ee, valid["classes"])
     if args.save:
         os.makedirs(os.path.dirname(os.path.abspath(args.save)), exist_ok=True)
         torch.save(model.state_dict(), args.save)
@@ -149,6 +193,7 @@ def main(argv=None):
                 "train_loss": stats["train_loss"], "clips_per_s": round(clips_total / max(t_train, 1e-9), 1),
                 "n_frames": ev["n_frames"], "eval_s": round(ev["eval_s"], 3), "checkpoint": args.save}
         line.update({k: ev[k] for k in METRICS})
+        line.update(ee_keys)
         print(json.dumps(line), flush=True)
 
 

@@ -2451,6 +2451,132 @@ def detect_events(filt, table, hi, lo, max_gap=0, min_len=0):
     return ev_i, ev_f
 
 
+# ------------------------------------------------------------------ event-based scoring (include/eat_event_score.h)
+EVENT_SCORE_MAX_REF = 64       # reference events of one (recording, class): bits of the kernel's taken-mask
+
+
+class EventRefs:
+    """The validated reference events of the scoring kernel: ref (E, 3) int32 rows (class, onset, offset) in samples, tol (E)
+    int32 offset tolerances, ro (N + 1) int64 - recording i owns the rows [ro[i], ro[i + 1]) - for K classes.  Built by
+    `event_refs` on the host; `dev(device)` uploads the three tensors once per device."""
+
+    def __init__(self, ref, tol, ro, K):
+        self.ref, self.tol, self.ro, self.K, self._dev = ref, tol, ro, int(K), {}
+        self.n_rec, self.E = int(ro.numel()) - 1, int(ref.shape[0])
+
+    def dev(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(t.to(device) for t in (self.ref, self.tol, self.ro))
+        return self._dev[key]
+
+
+def event_refs(ref, ref_tol, ro, K):
+    """Host-side validation of reference events (CPU tensors / arrays) -> EventRefs.  ref (E, 3) int32 rows (class, onset,
+    offset) with 0 <= class < K and 0 <= onset <= offset; ref_tol (E) int32 >= 0; ro (N + 1) int64 rising from 0 to E; the
+    rows of a recording sorted by (class, onset), at most EVENT_SCORE_MAX_REF of one class."""
+    fn = "event_refs"
+    ref, ref_tol, ro = (torch.as_tensor(t).cpu() for t in (ref, ref_tol, ro))
+    K = int(K)
+    if K < 1:
+        raise _lib.EatHipError(f"{fn}: need K >= 1 (got {K})")
+    if ref.dim() != 2 or ref.shape[1] != 3 or ref.dtype != torch.int32:
+        raise _lib.EatHipError(f"{fn}: ref must be (E, 3) int32 rows (class, onset, offset), got {ref.dtype} {tuple(ref.shape)}")
+    E = int(ref.shape[0])
+    if ref_tol.dim() != 1 or ref_tol.numel() != E or ref_tol.dtype != torch.int32:
+        raise _lib.EatHipError(f"{fn}: ref_tol must be (E,) = ({E},) int32, got {ref_tol.dtype} {tuple(ref_tol.shape)}")
+    if ro.dim() != 1 or ro.numel() < 2 or ro.dtype != torch.int64:
+        raise _lib.EatHipError(f"{fn}: ro must be (n_rec + 1 >= 2,) int64, got {ro.dtype} {tuple(ro.shape)}")
+    d = ro[1:] - ro[:-1]
+    if int(ro[0]) != 0 or int(ro[-1]) != E or bool((d < 0).any()):
+        raise _lib.EatHipError(f"{fn}: ro must rise from 0 to E = {E} (got {int(ro[0])} .. {int(ro[-1])})")
+    cls, on, off = (ref[:, j].to(torch.int64) for j in range(3))
+    if E and (int(cls.min()) < 0 or int(cls.max()) >= K):
+        raise _lib.EatHipError(f"{fn}: ref names a class outside [0, {K})")
+    if bool(((on < 0) | (off < on)).any()):
+        e = int(((on < 0) | (off < on)).nonzero()[0])
+        raise _lib.EatHipError(f"{fn}: ref row {e} = {ref[e].tolist()} breaks 0 <= onset <= offset")
+    if bool((ref_tol < 0).any()):
+        raise _lib.EatHipError(f"{fn}: ref_tol row {int((ref_tol < 0).nonzero()[0])} is negative")
+    rec = torch.repeat_interleave(torch.arange(ro.numel() - 1), d)            # the recording of every row
+    if E > 1:
+        same = rec[1:] == rec[:-1]
+        ok = (cls[1:] > cls[:-1]) | ((cls[1:] == cls[:-1]) & (on[1:] >= on[:-1]))
+        if bool((same & ~ok).any()):
+            e = int((same & ~ok).nonzero()[0]) + 1
+            raise _lib.EatHipError(f"{fn}: ref row {e} is out of order: a recording's rows are sorted by (class, onset)")
+    if E:
+        per = torch.bincount(rec * K + cls)
+        if int(per.max()) > EVENT_SCORE_MAX_REF:
+            j = int(per.argmax())
+            raise _lib.EatHipError(f"{fn}: recording {j // K} holds {int(per[j])} reference events of class {j % K}: the "
+                                   f"matching kernel takes at most {EVENT_SCORE_MAX_REF} per recording and class")
+    return EventRefs(ref.contiguous(), ref_tol.contiguous(), ro.contiguous(), K)
+
+
+def check_threshold_grid(hi, lo):
+    """`check_thresholds` for a grid of V >= 1 threshold pairs (CPU arrays of one length): 0 < lo <= hi <= 1 ->
+    (hi, lo) contiguous fp32 CPU tensors, compared as the fp32 numbers the kernel sees."""
+    fn = "event_score"
+    hi_t, lo_t = (torch.as_tensor(v, dtype=torch.float32).cpu().contiguous() for v in (hi, lo))
+    if hi_t.dim() != 1 or hi_t.numel() < 1 or lo_t.shape != hi_t.shape:
+        raise _lib.EatHipError(f"{fn}: hi and lo must hold V >= 1 values each (got {tuple(hi_t.shape)}, {tuple(lo_t.shape)})")
+    if not bool(((lo_t > 0) & (lo_t <= hi_t) & (hi_t <= 1)).all()):           # (NaN fails every comparison)
+        raise _lib.EatHipError(f"{fn}: thresholds need 0 < lo <= hi <= 1 in every pair")
+    return hi_t, lo_t
+
+
+def event_score(filt, table, nsamp, R, refs, c, hi, lo, max_gap=0, min_len=0, first=0, out=None):
+    """Event-based scoring of every (recording, class) timeline of filt (K, G_total) at V threshold pairs at once
+    (include/eat_event_score.h) -> counts (n_rec, K, V, 2) int32: (tp, n_est) - the events `detect_events` would list at
+    (hi[v], lo[v], max_gap, min_len), in samples [on R, min(off R, nsamp)), matched against the reference events with
+    |onset distance| <= c and |offset distance| <= tol.  The recordings of `table` are recordings [first, first + n_rec)
+    of `refs` (an `EventRefs`).  nsamp: their lengths in samples, (n_rec) int64 on filt's device, or a CPU array that is
+    checked (>= 1) and uploaded.  hi, lo: CPU arrays validated by `check_threshold_grid` and uploaded, or fp32 device
+    tensors of V values that were.  One launch, no host wait."""
+    fn = "event_score"
+    table, K = _timelines(fn, filt, "filt", table)
+    if not isinstance(refs, EventRefs):
+        raise _lib.EatHipError(f"{fn}: refs must be an EventRefs from ops.event_refs (got {type(refs).__name__})")
+    if refs.K != K:
+        raise _lib.EatHipError(f"{fn}: refs hold {refs.K} classes, filt {K}")
+    R, c, max_gap, min_len, first = int(R), int(c), int(max_gap), int(min_len), int(first)
+    if R < 1:
+        raise _lib.EatHipError(f"{fn}: need R >= 1 samples per frame (got {R})")
+    if c < 0 or c >= 2 ** 31 or max_gap < 0 or min_len < 0:
+        raise _lib.EatHipError(f"{fn}: c, max_gap and min_len must not be negative (got {c}, {max_gap}, {min_len})")
+    if first < 0 or first + table.n_rec > refs.n_rec:
+        raise _lib.EatHipError(f"{fn}: recordings [{first}, {first + table.n_rec}) lie outside the {refs.n_rec} of refs")
+    if table.n_rec * K >= 2 ** 31:
+        raise _lib.EatHipError(f"{fn}: {table.n_rec} recordings x {K} classes: 2^31 timelines or more")
+    if not (isinstance(nsamp, torch.Tensor) and nsamp.is_cuda):
+        nsamp = torch.as_tensor(nsamp).cpu()
+        if nsamp.dim() != 1 or nsamp.numel() != table.n_rec or nsamp.dtype.is_floating_point or nsamp.dtype == torch.bool:
+            raise _lib.EatHipError(f"{fn}: nsamp must hold n_rec = {table.n_rec} integers (got {nsamp.dtype} {tuple(nsamp.shape)})")
+        if bool((nsamp < 1).any()):
+            raise _lib.EatHipError(f"{fn}: nsamp needs >= 1 sample in every recording")
+        nsamp = nsamp.to(device=filt.device, dtype=torch.int64)
+    p_ns = _glue_operand(nsamp, f"{fn}: nsamp", torch.int64, filt, n=table.n_rec)
+    if not (isinstance(hi, torch.Tensor) and hi.is_cuda and isinstance(lo, torch.Tensor) and lo.is_cuda):
+        hi, lo = (t.to(filt.device) for t in check_threshold_grid(hi, lo))
+    V = int(hi.numel())
+    if V < 1 or V > 64 * 65535:
+        raise _lib.EatHipError(f"{fn}: V = {V} threshold pairs must lie in [1, {64 * 65535}]")
+    p_hi = _glue_operand(hi, f"{fn}: hi", torch.float32, filt, n=V)
+    p_lo = _glue_operand(lo, f"{fn}: lo", torch.float32, filt, n=V)
+    n_out = table.n_rec * K * V * 2
+    if out is None:
+        out = torch.empty((table.n_rec, K, V, 2), device=filt.device, dtype=torch.int32)
+    else:
+        _glue_operand(out, f"{fn}: out", torch.int32, filt, n=n_out)
+    p_x = _on_gpu(filt, f"{fn}: filt")
+    ref, tol, ro = refs.dev(filt.device)
+    _lib.call("eat_event_score", p_x, K, table.G_total, table.dev(filt.device).data_ptr(), table.n_rec, p_ns, R,
+              ref.data_ptr() if refs.E else None, tol.data_ptr() if refs.E else None, ro.data_ptr() + 8 * first, refs.E, c,
+              p_hi, p_lo, V, max_gap, min_len, out.data_ptr(), _stream())
+    return out.view(table.n_rec, K, V, 2)
+
+
 def pw_conv_into(x, pack, Co, act, out):
     """The 1x1 conv of `mn._pw` on a (packed weights, bias, mode) triple of `mn._pack_pw`, stored into the caller's
     contiguous fp32 buffer `out` of B x Co x S elements (a slice of a larger buffer) instead of a fresh tensor."""

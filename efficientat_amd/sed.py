@@ -22,9 +22,14 @@ number of frames; the default 327680 is `EADetector`'s 10.24 s window, 32 frames
 
 `evaluate_frames` tiles every clip of a split with non-overlapping windows and scores the eval frame logits
 (`detection.frame_logits`) against the events: frame-level mAP / ROC and segment-based F1 with one frame as the segment.
+`evaluate_events` scores what `EADetector.detect` lists: event-based F1 with onset / offset collars (sed_eval's
+EventBasedMetrics in integer samples) at a whole grid of thresholds in one kernel launch per chunk of clips
+(`ops.event_score`, include/eat_event_score.h), and picks a threshold per class; `save_operating_points` /
+`load_operating_points` carry them to `detect --thresholds_file`.
 The fine-tuned model keeps the reference's state-dict layout (an mlp-head MN with K classes), so its checkpoint loads
 straight into `EADetector(model=...)` and `detect --checkpoint`.  Only MN models with the mlp head on the monolithic plan.
 """
+import json
 import os
 import time
 
@@ -344,4 +349,230 @@ def evaluate_frames(model, mel, bank, batch_windows=64, threshold=0.5, clip_samp
     out.update({"val_loss": float(res[2]), "n_clips": n, "n_frames": int(nframes.sum()), "eval_s": eval_s})
     if keep_outputs:
         out.update(rows=rows, truth=truth, weight=weight, counts=cnt)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- event-based scoring
+SCORE_NAMES = ("micro_f1", "micro_precision", "micro_recall", "macro_f1", "macro_precision", "macro_recall")
+_TINY = np.finfo(np.float32).tiny                                             # the smallest positive normal fp32
+
+
+def collar_samples(collar_ms, sample_rate):
+    """The onset collar c = round(collar_ms sample_rate / 1000) in samples."""
+    c = float(collar_ms) * int(sample_rate) / 1000.0
+    if not np.isfinite(c) or c < 0 or c >= 2 ** 31:
+        raise ValueError(f"collar_ms={collar_ms} must be finite, not negative and below 2^31 samples")
+    return int(round(c))
+
+
+def event_tolerances(events, collar_samples, pct):
+    """Offset tolerance of every reference row of events (E, 3) (class, onset, offset) in samples -> (E,) int32 numpy:
+    max(collar_samples, floor(pct (offset - onset))), the product taken in fp64."""
+    ev = np.asarray(events.cpu() if torch.is_tensor(events) else events)
+    if ev.ndim != 2 or ev.shape[1] != 3:
+        raise ValueError(f"event_tolerances: events must be (E, 3) rows (class, onset, offset), got {ev.shape}")
+    c, pct = int(collar_samples), float(pct)
+    if c < 0 or not np.isfinite(pct) or pct < 0:
+        raise ValueError(f"event_tolerances: collar_samples and pct must not be negative (got {collar_samples}, {pct})")
+    length = ev[:, 2].astype(np.int64) - ev[:, 1].astype(np.int64)
+    tol = np.maximum(np.int64(c), np.floor(np.float64(pct) * length.astype(np.float64)).astype(np.int64))
+    if tol.size and tol.max() >= 2 ** 31:
+        raise ValueError("event_tolerances: a tolerance of 2^31 samples or more")
+    return tol.astype(np.int32)
+
+
+def threshold_grid(thresholds=None, low_ratio=1.0):
+    """-> (hi (V,), lo (V,)) float32: `thresholds` (default the 49 values k / 50, k = 1 .. 49) and
+    lo = max(low_ratio hi, smallest positive normal fp32) with the product taken in fp32, so lo <= hi."""
+    low_ratio = float(low_ratio)
+    if not 0.0 <= low_ratio <= 1.0:
+        raise ValueError(f"low_ratio must lie in [0, 1] (got {low_ratio})")
+    hi = (np.arange(1, 50, dtype=np.float64) / 50.0).astype(np.float32) if thresholds is None else \
+        np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+    if hi.size < 1 or not bool(((hi > 0) & (hi <= 1)).all()):
+        raise ValueError("thresholds must hold V >= 1 values in (0, 1]")
+    lo = np.maximum(np.float32(low_ratio) * hi, _TINY).astype(np.float32)
+    return hi, np.minimum(lo, hi)
+
+
+def class_f1(counts):
+    """(..., 3) (tp, fp, fn) -> F1 = 2 tp / (2 tp + fp + fn) in fp64, NaN where there is nothing to score."""
+    c = np.asarray(counts, dtype=np.float64)
+    den = 2 * c[..., 0] + c[..., 1] + c[..., 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, 2 * c[..., 0] / den, np.nan)
+
+
+def pick_thresholds(counts, hi, lo, threshold, low_ratio=1.0):
+    """counts (V, K, 3), the grid (hi, lo) -> (index of the grid value nearest `threshold` (the first of equals), best
+    index (K,) or -1, best_threshold (K,), best_low_threshold (K,) float32).  Per class the FIRST grid value of maximal F1,
+    a threshold without anything to score ranking below every F1; a class with nothing to score at any threshold keeps
+    `threshold` (index -1)."""
+    f = class_f1(counts)                                                     # (V, K)
+    at = int(np.argmin(np.abs(hi.astype(np.float64) - float(np.float32(threshold)))))
+    best = np.argmax(np.where(np.isnan(f), -1.0, f), axis=0)
+    best = np.where(np.isnan(f).all(axis=0), -1, best)
+    keep_hi = np.float32(threshold)
+    keep_lo = np.minimum(np.maximum(np.float32(low_ratio) * keep_hi, _TINY), keep_hi).astype(np.float32)
+    b_hi = np.where(best >= 0, hi[np.maximum(best, 0)], keep_hi).astype(np.float32)
+    b_lo = np.where(best >= 0, lo[np.maximum(best, 0)], keep_lo).astype(np.float32)
+    return at, best, b_hi, b_lo
+
+
+def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=960, min_duration_ms=0, max_gap_ms=0,
+                    collar_ms=200, offset_pct=0.2, threshold=0.5, batch_clips=256, taper="triangle", clip_seconds=10.24,
+                    hop_seconds=5.12, batch_windows=64):
+    """Event-based (collar) scores of what `detection.EADetector(model=model).detect` lists on a resident strong-label
+    split, at a whole grid of thresholds at once.
+
+    The bank's clips are walked in contiguous chunks of `batch_clips` of the resident flat buffer (no waveform is copied):
+    `detector.plan` on the chunk's lengths, `window_logits` on the slice (through `mel`), `ops.detect_stitch`,
+    `ops.detect_median`, then ONE `ops.event_score` for all thresholds; int64 counts accumulate on the device, with one
+    host wait at the end.  Grid: `threshold_grid(thresholds, low_ratio)`.  An estimated event of frames [on, off) spans the
+    samples [on R, min(off R, n)); it matches a reference of its clip and class iff the onsets are at most
+    c = round(collar_ms sample_rate / 1000) samples apart and the offsets at most max(c, floor(offset_pct length)) of the
+    reference (`event_tolerances`); greedy in reference order as sed_eval's EventBasedMetrics (integer samples: a float-
+    second sed_eval run may differ only where a distance sits exactly on a collar).
+
+    -> {"thresholds", "low_thresholds" (V,) float32; "counts" (V, K, 3) int64 (tp, fp, fn); "grid": {name: (V,) float64} for
+    micro / macro F1, precision, recall (`segment_scores` per threshold); "class_f1" (V, K); "threshold": the grid value
+    nearest the argument (itself when it is on the grid), "threshold_index", and the six scores at it under their plain
+    names; "best_threshold", "best_low_threshold" (K,) float32 and "best_index" (K,) (`pick_thresholds`); "macro_f1_best":
+    macro F1 with those per-class values - TUNED ON THE SCORED SPLIT, an upper bound for any other; "n_clips", "n_ref",
+    "eval_s", "settings"}.  Mode restore and forked RNG as `evaluate_frames`."""
+    n = bank["lengths"].numel()
+    if n == 0:
+        raise ValueError("evaluate_events: the split is empty")
+    if int(batch_clips) < 1:
+        raise ValueError(f"batch_clips must be >= 1 (got {batch_clips})")
+    _, _, K = detection.check_model(model)
+    if len(bank["classes"]) != K:
+        raise ValueError(f"evaluate_events: the bank has {len(bank['classes'])} classes, the model {K}")
+    hi, lo = threshold_grid(thresholds, low_ratio)
+    c = collar_samples(collar_ms, mel.sr)
+    dev = bank["waves"].device
+    events_cpu = bank["events"].cpu()
+    refs = ops.event_refs(events_cpu, torch.from_numpy(event_tolerances(events_cpu, c, offset_pct)),
+                          bank["event_offsets"].cpu(), K)
+    n_ref = np.bincount(events_cpu[:, 0].numpy(), minlength=K).astype(np.int64)
+    lengths = bank["lengths_cpu"].numpy().astype(np.int64)
+    offsets = np.cumsum(lengths) - lengths
+    was_training = (model.training, mel.training)
+    model.eval()
+    mel.eval()
+    try:
+        det = detection.EADetector(model=model, device=dev, sample_rate=mel.sr, window_size=mel.win_length, hop_size=mel.hopsize,
+                                   n_mels=mel.n_mels, batch_windows=batch_windows, clip_seconds=clip_seconds,
+                                   hop_seconds=hop_seconds, taper=taper)
+        det.mel = mel                                                         # the caller's front end, not a default one
+        geo = det.geometry
+        m = detection.median_frames(median_ms, geo.frame_s)
+        min_len, max_gap = detection.ms_to_frames(min_duration_ms, geo.frame_s), detection.ms_to_frames(max_gap_ms, geo.frame_s)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        with torch.random.fork_rng(devices=[]), torch.no_grad():
+            d_hi, d_lo = (t.to(dev) for t in ops.check_threshold_grid(hi, lo))
+            d_n = torch.from_numpy(lengths).to(dev)
+            acc = torch.zeros((K, hi.size, 2), device=dev, dtype=torch.int64)
+            for i0 in range(0, n, int(batch_clips)):
+                i1 = min(i0 + int(batch_clips), n)
+                starts, valids, table = det.plan(lengths[i0:i1].tolist())
+                flat = bank["waves"][int(offsets[i0]):int(offsets[i1 - 1] + lengths[i1 - 1])]
+                P = det.window_logits(flat, starts, valids)
+                prob = ops.detect_stitch(P, table, geo.Hf, geo.T, det._wt)
+                filt = ops.detect_median(prob, table, m) if m != 1 else prob
+                cnt = ops.event_score(filt, table, d_n[i0:i1], geo.R, refs, c, d_hi, d_lo, max_gap, min_len, first=i0)
+                acc += cnt.sum(dim=0, dtype=torch.int64)
+            res = acc.cpu().numpy()                                           # the one host wait
+    finally:
+        model.train(was_training[0])
+        mel.train(was_training[1])
+    eval_s = time.perf_counter() - t0
+    tp, n_est = res[:, :, 0].T, res[:, :, 1].T                                # (V, K)
+    counts = np.stack([tp, n_est - tp, n_ref[None, :] - tp], axis=2).astype(np.int64)
+    rows = [segment_scores(counts[v]) for v in range(hi.size)]
+    at, best, b_hi, b_lo = pick_thresholds(counts, hi, lo, threshold, low_ratio)
+    at_best = np.where(best >= 0, best, at)
+    out = {"thresholds": hi, "low_thresholds": lo, "counts": counts,
+           "grid": {k: np.asarray([r[k] for r in rows], dtype=np.float64) for k in SCORE_NAMES}, "class_f1": class_f1(counts),
+           "threshold": float(hi[at]), "threshold_index": at}
+    out.update(rows[at])
+    out.update({"best_threshold": b_hi, "best_low_threshold": b_lo, "best_index": best,
+                "macro_f1_best": segment_scores(counts[at_best, np.arange(K)])["macro_f1"], "n_clips": n,
+                "n_ref": int(n_ref.sum()), "eval_s": eval_s,
+                "settings": {"median_ms": float(median_ms), "min_duration_ms": float(min_duration_ms),
+                             "max_gap_ms": float(max_gap_ms), "taper": taper, "window_size": float(clip_seconds),
+                             "hop_length": float(hop_seconds), "collar_ms": float(collar_ms), "offset_pct": float(offset_pct),
+                             "low_ratio": float(low_ratio)}})
+    return out
+
+
+# ---- operating points: the per-class thresholds and the post-processing they were tuned with, for `detect --thresholds_file`
+_OP_POST = ("median_ms", "min_duration_ms", "max_gap_ms", "taper", "window_size", "hop_length")
+
+
+def save_operating_points(path, result, classes):
+    """Write the per-class operating points of an `evaluate_events` result as JSON: classes, threshold (K), low_threshold (K),
+    median_ms, min_duration_ms, max_gap_ms, taper, window_size, hop_length (seconds, `detect`'s flags), and under "scoring" /
+    "scores" the settings and the scores they came from."""
+    classes = list(classes)
+    hi, lo = np.asarray(result["best_threshold"], dtype=np.float32), np.asarray(result["best_low_threshold"], dtype=np.float32)
+    if hi.shape != (len(classes),) or lo.shape != hi.shape:
+        raise ValueError(f"save_operating_points: {len(classes)} classes, thresholds of shape {hi.shape} / {lo.shape}")
+    st = result["settings"]
+    doc = {"classes": classes, "threshold": [float(v) for v in hi], "low_threshold": [float(v) for v in lo]}
+    doc.update({k: st[k] for k in _OP_POST})
+    doc["scoring"] = {"collar_ms": st["collar_ms"], "offset_pct": st["offset_pct"], "low_ratio": st["low_ratio"],
+                      "reference_threshold": result["threshold"], "n_clips": result["n_clips"], "n_ref": result["n_ref"],
+                      "grid": [float(v) for v in result["thresholds"]]}
+    doc["scores"] = {"macro_f1_best": result["macro_f1_best"]}
+    doc["scores"].update({k: result[k] for k in SCORE_NAMES})
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    return doc
+
+
+def load_operating_points(path, classes=None, n_classes=None):
+    """Read an operating-point file -> its dict with threshold / low_threshold as (K,) float32 arrays.  classes: the class
+    names, in order, that the file must hold; n_classes: the class count it must hold.  A missing field, a wrong length,
+    another class order, thresholds outside 0 < low_threshold <= threshold <= 1 or an unknown taper: ValueError naming the
+    file."""
+    what = f"operating points at {path}"
+    try:
+        with open(path) as f:
+            doc = json.load(f)
+    except (OSError, ValueError) as e:
+        raise ValueError(f"{what}: not readable as JSON ({e})") from None
+    if not isinstance(doc, dict):
+        raise ValueError(f"{what}: the file must hold one JSON object")
+    missing = [k for k in ("classes", "threshold", "low_threshold") + _OP_POST if k not in doc]
+    if missing:
+        raise ValueError(f"{what}: missing {', '.join(missing)}")
+    names = doc["classes"]
+    if not isinstance(names, list) or len(names) < 1 or not all(isinstance(c, str) for c in names):
+        raise ValueError(f"{what}: classes must be a list of K >= 1 names")
+    K = len(names)
+    if n_classes is not None and K != int(n_classes):
+        raise ValueError(f"{what}: the file holds {K} classes, {int(n_classes)} are expected")
+    if classes is not None and list(classes) != names:
+        raise ValueError(f"{what}: the file's classes {names[:4]}{'...' if K > 4 else ''} are not the expected names in "
+                         f"their order")
+    try:
+        hi, lo = (np.asarray(doc[k], dtype=np.float32) for k in ("threshold", "low_threshold"))
+        post = {k: float(doc[k]) for k in _OP_POST if k != "taper"}
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: thresholds and post-processing values must be numbers") from None
+    if hi.shape != (K,) or lo.shape != (K,):
+        raise ValueError(f"{what}: threshold and low_threshold must hold K = {K} values (got {hi.shape}, {lo.shape})")
+    if not bool(((lo > 0) & (lo <= hi) & (hi <= 1)).all()):
+        raise ValueError(f"{what}: thresholds need 0 < low_threshold <= threshold <= 1 in every class")
+    if doc["taper"] not in ("triangle", "uniform"):
+        raise ValueError(f"{what}: taper must be 'triangle' or 'uniform' (got {doc['taper']!r})")
+    if not all(np.isfinite(v) and v >= 0 for v in post.values()):
+        raise ValueError(f"{what}: post-processing values must be finite and not negative")
+    out = dict(doc)
+    out.update(post)
+    out.update(threshold=hi, low_threshold=lo)
     return out
