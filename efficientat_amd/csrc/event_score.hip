@@ -5,9 +5,10 @@
 // Geometry.  One wavefront (= one block) takes one timeline and 64 threshold pairs, one pair per lane.  The timeline is
 // loaded 64 frames at a time with one coalesced load and handed round by lane broadcast; each lane runs the run / merge /
 // drop state machine of detect.hip's events kernel frame by frame on its own pair and matches an event the moment it is
-// final.  The timeline's reference rows (at most 64) sit in LDS; a lane keeps a taken-mask over them.  Frames that no lane
-// can see as active, and that follow such a frame, change no lane's state and are skipped (wave-uniform).
+// final (the walk of event_walk.h, shared with psds.hip).  The timeline's reference rows (at most 64) sit in LDS; a lane keeps a
+// taken-mask over them.
 #include "eat_common.h"
+#include "event_walk.h"
 #include "../../include/eat_event_score.h"
 
 namespace {
@@ -34,16 +35,8 @@ __global__ __launch_bounds__(64) void event_score_kernel(const float* __restrict
 
   // the rows of class k among the recording's rows [a, b), sorted by (class, onset): two bisections, wave-uniform
   const long long a = min(max(ro[i], 0LL), (long long)n_ref), b = min(max(ro[i + 1], a), (long long)n_ref);
-  auto lower = [&](int cls) {
-    long long l = a, h = b;
-    while (l < h) {
-      const long long m = (l + h) >> 1;
-      if (ref[3 * m] < cls) l = m + 1; else h = m;
-    }
-    return l;
-  };
-  const long long b0 = lower(k);
-  const int nref = (int)min(lower(k + 1) - b0, (long long)kMaxRef);
+  const long long b0 = eat::first_row_of_class(ref, a, b, k);
+  const int nref = (int)min(eat::first_row_of_class(ref, a, b, k + 1) - b0, (long long)kMaxRef);
   if (lane < nref) {
     s_on[lane] = ref[3 * (b0 + lane) + 1];
     s_off[lane] = ref[3 * (b0 + lane) + 2];
@@ -53,17 +46,10 @@ __global__ __launch_bounds__(64) void event_score_kernel(const float* __restrict
 
   const float inf = __builtin_huge_valf();
   const float hi = live ? hi_v[v] : inf, lo = live ? lo_v[v] : inf;       // a lane without a pair never sees an active frame
-  float lo_min = lo;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) lo_min = fminf(lo_min, __shfl_xor(lo_min, o, 64));
-
-  bool open = false, hit = false, cur = false;             // a run in progress; it has reached hi; a pending event
-  int rs = 0, cur_on = 0, cur_off = 0;
   int n_est = 0, tp = 0, first = 0;                        // references before `first` start too early for what follows
   unsigned long long taken = 0;
 
-  auto emit = [&](int on, int off) {
-    if (off - on < min_len) return;
+  eat::event_walk(x, G, hi, lo, max_gap, min_len, [&](int on, int off) {
     ++n_est;
     const long long on_s = (long long)on * R;
     const long long off_s = min((long long)off * R, n_i);
@@ -78,47 +64,7 @@ __global__ __launch_bounds__(64) void event_score_kernel(const float* __restrict
         break;
       }
     }
-  };
-  auto close_run = [&](int re) {                           // the run [rs, re) ends
-    if (hit) {
-      if (cur && rs - cur_off <= max_gap) {
-        cur_off = re;
-      } else {
-        if (cur) emit(cur_on, cur_off);
-        cur = true;
-        cur_on = rs;
-        cur_off = re;
-      }
-    }
-    open = false;
-  };
-
-  unsigned long long carry = 0;                            // the last frame of the step before was active in some lane
-  for (int t0 = 0; t0 < G; t0 += 64) {
-    const int t = t0 + lane;
-    const float val = t < G ? x[t] : 0.0f;
-    const unsigned long long inside = G - t0 >= 64 ? ~0ULL : (1ULL << (G - t0)) - 1;
-    const unsigned long long M = __ballot(t < G && val >= lo_min);
-    unsigned long long todo = (M | (M << 1) | carry) & inside;
-    carry = M >> 63;
-    while (todo != 0) {
-      const int j = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const float f = __shfl(val, j, 64);
-      if (f >= lo) {
-        if (!open) {
-          open = true;
-          hit = false;
-          rs = t0 + j;
-        }
-        if (f >= hi) hit = true;
-      } else if (open) {
-        close_run(t0 + j);
-      }
-    }
-  }
-  if (open) close_run(G);
-  if (cur) emit(cur_on, cur_off);
+  });
   if (live) {
     int2* out = reinterpret_cast<int2*>(counts) + (tl * V + v);
     *out = make_int2(tp, n_est);

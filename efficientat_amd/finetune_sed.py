@@ -9,7 +9,9 @@ frame BCE -> backward -> FusedAdam (sed.GraphedFrameBCETrainer; `--no_graph`: th
 the validation split is scored frame by frame (sed.evaluate_frames: frame mAP / ROC, segment-based F1 at `--threshold`,
 val_loss); with `--event_eval` also event by event (sed.evaluate_events: collar-based F1 at a grid of thresholds, the
 post-processing of `detect` given by `--median_ms --min_duration_ms --max_gap_ms --low_ratio`), and `--save_thresholds FILE`
-writes the per-class operating points of the last validation for `detect --thresholds_file`.  `--save` writes the final plain state dict: an mlp-head MN with K = the bank's classes, which
+writes the per-class operating points of the last validation for `detect --thresholds_file`; with `--psds_eval` also with
+PSDS (sed.evaluate_psds: the scenarios of `--psds`, default both, criteria `--dtc --gtc --cttc --alpha_ct --alpha_st --e_max`).
+`--save` writes the final plain state dict: an mlp-head MN with K = the bank's classes, which
 `detection.EADetector(model=...)` and `python -m efficientat_amd.detect --checkpoint` accept.  `--init_checkpoint` loads a
 local state dict and drops its output layer when the class count differs (finetune.load_init_checkpoint).
 
@@ -61,6 +63,53 @@ def event_eval(args, model, mel, bank):
     return ev, keys
 
 
+def _scenarios(text):
+    """`--psds` values: "1", "2" or "1,2" -> [int]."""
+    try:
+        out = [int(t) for t in str(text).split(",") if t.strip()]
+    except ValueError:
+        out = []
+    if not out or any(v not in (1, 2) for v in out):
+        raise argparse.ArgumentTypeError(f"--psds takes 1, 2 or 1,2 (got {text!r})")
+    return out
+
+
+def add_psds_args(p):
+    """The arguments of PSDS scoring (sed.evaluate_psds), shared with score_sed."""
+    p.add_argument("--psds", type=_scenarios, action="append", default=None, metavar="{1,2}",
+                   help="PSDS scenario(s) of DCASE Task 4 to score: repeatable or comma-separated")
+    for name, what in (("dtc", "detection tolerance criterion"), ("gtc", "ground-truth intersection criterion"),
+                       ("cttc", "cross-trigger tolerance criterion"), ("alpha_ct", "weight of the cross-trigger rate"),
+                       ("alpha_st", "weight of the spread over classes")):
+        p.add_argument("--" + name, type=float, default=None, help=f"PSDS: {what} (default: the scenario's)")
+    p.add_argument("--e_max", type=float, default=100.0, help="PSDS: largest effective false positives per hour")
+
+
+def psds_scenarios(args, default=()):
+    """The scenarios the command line asks for, in first-mention order: those of --psds, else `default`, else scenario 1 as
+    the base of explicit criteria (then under the plain key "psds") -> [(scenario, key of the JSON line)]."""
+    asked = list(dict.fromkeys(v for group in (args.psds or []) for v in group)) or list(default)
+    if asked:
+        return [(v, f"psds_scenario{v}") for v in asked]
+    explicit = any(getattr(args, k) is not None for k in ("dtc", "gtc", "cttc", "alpha_ct", "alpha_st")) or args.e_max != 100.0
+    return [(1, "psds")] if explicit else []
+
+
+def psds_eval(args, model, mel, bank, scenarios):
+    """`sed.evaluate_psds` per scenario with the command line's settings -> the JSON line's keys."""
+    from . import sed
+    keys, seconds = {}, 0.0
+    for scenario, key in scenarios:
+        ev = sed.evaluate_psds(model, mel, bank, scenario=scenario, dtc=args.dtc, gtc=args.gtc, cttc=args.cttc,
+                               alpha_ct=args.alpha_ct, alpha_st=args.alpha_st, e_max=args.e_max, low_ratio=args.low_ratio,
+                               median_ms=args.median_ms, min_duration_ms=args.min_duration_ms, max_gap_ms=args.max_gap_ms,
+                               batch_windows=args.batch_windows)
+        keys[key] = ev["psds"]
+        seconds += ev["eval_s"]
+    keys["psds_eval_s"] = round(seconds, 3)
+    return keys
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="strong-label SED fine-tuning on the HIP path")
     p.add_argument("--train_bank", required=True, help="decoded training split (sed.load_bank)")
@@ -102,7 +151,11 @@ def parse_args(argv=None):
     p.add_argument("--precision", default=None, help="model.train_precision (auto / fp32 / bf16)")
     add_event_args(p)
     p.add_argument("--event_eval", action="store_true", help="also score the validation split event by event (collar F1)")
+    add_psds_args(p)
+    p.add_argument("--psds_eval", action="store_true", help="also score the validation split with PSDS (--psds, default 1,2)")
     args = p.parse_args(argv)
+    if psds_scenarios(args) and not args.psds_eval:
+        p.error("--psds and its criteria need --psds_eval")
     if args.save_thresholds and not args.event_eval:
         p.error("--save_thresholds needs --event_eval")
     if args.model_name.startswith("dymn"):
@@ -150,7 +203,7 @@ def main(argv=None):
 
     steps_total, clips_total, t_train = 0, 0, 0.0
     ev, stats, done = None, {"train_loss": float("nan")}, False
-    ee, ee_keys = None, {}
+    ee, ee_keys, ps_keys = None, {}, {}
     for epoch in range(args.n_epochs):
         order = torch.randperm(n_train)                                       # shuffle, partial last batch
         torch.cuda.synchronize()
@@ -179,6 +232,10 @@ def main(argv=None):
             print(f"[finetune_sed] events at {ee['threshold']:.2f}: micro F1 {ee['micro_f1']:.4f}, macro F1 {ee['macro_f1']:.4f}; "
                   f"macro F1 at the per-class best thresholds (tuned on this split) {ee['macro_f1_best']:.4f} "
                   f"({ee['eval_s']:.2f} s)", file=sys.stderr, flush=True)
+        if args.psds_eval:
+            ps_keys = psds_eval(args, model, mel, valid, psds_scenarios(args, default=(1, 2)))
+            print("[finetune_sed] " + ", ".join(f"{k} {v:.4f}" for k, v in ps_keys.items() if k != "psds_eval_s")
+                  + f" ({ps_keys['psds_eval_s']:.2f} s)", file=sys.stderr, flush=True)
         if done:
             break
     if args.save_thresholds and ee is not None:
@@ -194,6 +251,7 @@ def main(argv=None):
                 "n_frames": ev["n_frames"], "eval_s": round(ev["eval_s"], 3), "checkpoint": args.save}
         line.update({k: ev[k] for k in METRICS})
         line.update(ee_keys)
+        line.update(ps_keys)
         print(json.dumps(line), flush=True)
 
 

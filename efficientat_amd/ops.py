@@ -2526,25 +2526,19 @@ def check_threshold_grid(hi, lo):
     return hi_t, lo_t
 
 
-def event_score(filt, table, nsamp, R, refs, c, hi, lo, max_gap=0, min_len=0, first=0, out=None):
-    """Event-based scoring of every (recording, class) timeline of filt (K, G_total) at V threshold pairs at once
-    (include/eat_event_score.h) -> counts (n_rec, K, V, 2) int32: (tp, n_est) - the events `detect_events` would list at
-    (hi[v], lo[v], max_gap, min_len), in samples [on R, min(off R, nsamp)), matched against the reference events with
-    |onset distance| <= c and |offset distance| <= tol.  The recordings of `table` are recordings [first, first + n_rec)
-    of `refs` (an `EventRefs`).  nsamp: their lengths in samples, (n_rec) int64 on filt's device, or a CPU array that is
-    checked (>= 1) and uploaded.  hi, lo: CPU arrays validated by `check_threshold_grid` and uploaded, or fp32 device
-    tensors of V values that were.  One launch, no host wait."""
-    fn = "event_score"
+def _score_operands(fn, filt, table, nsamp, R, refs, hi, lo, max_gap, min_len, first):
+    """The operands `event_score` and `psds_count` share, checked in one place -> (table, K, R, max_gap, min_len, first,
+    nsamp, hi, lo, V) with nsamp / hi / lo on filt's device."""
     table, K = _timelines(fn, filt, "filt", table)
     if not isinstance(refs, EventRefs):
         raise _lib.EatHipError(f"{fn}: refs must be an EventRefs from ops.event_refs (got {type(refs).__name__})")
     if refs.K != K:
         raise _lib.EatHipError(f"{fn}: refs hold {refs.K} classes, filt {K}")
-    R, c, max_gap, min_len, first = int(R), int(c), int(max_gap), int(min_len), int(first)
+    R, max_gap, min_len, first = int(R), int(max_gap), int(min_len), int(first)
     if R < 1:
         raise _lib.EatHipError(f"{fn}: need R >= 1 samples per frame (got {R})")
-    if c < 0 or c >= 2 ** 31 or max_gap < 0 or min_len < 0:
-        raise _lib.EatHipError(f"{fn}: c, max_gap and min_len must not be negative (got {c}, {max_gap}, {min_len})")
+    if max_gap < 0 or min_len < 0:
+        raise _lib.EatHipError(f"{fn}: max_gap and min_len must not be negative (got {max_gap}, {min_len})")
     if first < 0 or first + table.n_rec > refs.n_rec:
         raise _lib.EatHipError(f"{fn}: recordings [{first}, {first + table.n_rec}) lie outside the {refs.n_rec} of refs")
     if table.n_rec * K >= 2 ** 31:
@@ -2556,14 +2550,34 @@ def event_score(filt, table, nsamp, R, refs, c, hi, lo, max_gap=0, min_len=0, fi
         if bool((nsamp < 1).any()):
             raise _lib.EatHipError(f"{fn}: nsamp needs >= 1 sample in every recording")
         nsamp = nsamp.to(device=filt.device, dtype=torch.int64)
-    p_ns = _glue_operand(nsamp, f"{fn}: nsamp", torch.int64, filt, n=table.n_rec)
+    _glue_operand(nsamp, f"{fn}: nsamp", torch.int64, filt, n=table.n_rec)
     if not (isinstance(hi, torch.Tensor) and hi.is_cuda and isinstance(lo, torch.Tensor) and lo.is_cuda):
-        hi, lo = (t.to(filt.device) for t in check_threshold_grid(hi, lo))
+        try:
+            hi, lo = (t.to(filt.device) for t in check_threshold_grid(hi, lo))
+        except _lib.EatHipError as e:
+            raise _lib.EatHipError(str(e).replace("event_score:", f"{fn}:", 1)) from None
     V = int(hi.numel())
     if V < 1 or V > 64 * 65535:
         raise _lib.EatHipError(f"{fn}: V = {V} threshold pairs must lie in [1, {64 * 65535}]")
-    p_hi = _glue_operand(hi, f"{fn}: hi", torch.float32, filt, n=V)
-    p_lo = _glue_operand(lo, f"{fn}: lo", torch.float32, filt, n=V)
+    _glue_operand(hi, f"{fn}: hi", torch.float32, filt, n=V)
+    _glue_operand(lo, f"{fn}: lo", torch.float32, filt, n=V)
+    return table, K, R, max_gap, min_len, first, nsamp, hi, lo, V
+
+
+def event_score(filt, table, nsamp, R, refs, c, hi, lo, max_gap=0, min_len=0, first=0, out=None):
+    """Event-based scoring of every (recording, class) timeline of filt (K, G_total) at V threshold pairs at once
+    (include/eat_event_score.h) -> counts (n_rec, K, V, 2) int32: (tp, n_est) - the events `detect_events` would list at
+    (hi[v], lo[v], max_gap, min_len), in samples [on R, min(off R, nsamp)), matched against the reference events with
+    |onset distance| <= c and |offset distance| <= tol.  The recordings of `table` are recordings [first, first + n_rec)
+    of `refs` (an `EventRefs`).  nsamp: their lengths in samples, (n_rec) int64 on filt's device, or a CPU array that is
+    checked (>= 1) and uploaded.  hi, lo: CPU arrays validated by `check_threshold_grid` and uploaded, or fp32 device
+    tensors of V values that were.  One launch, no host wait."""
+    fn = "event_score"
+    c = int(c)
+    if c < 0 or c >= 2 ** 31:
+        raise _lib.EatHipError(f"{fn}: c must not be negative (got {c})")
+    table, K, R, max_gap, min_len, first, nsamp, hi, lo, V = _score_operands(fn, filt, table, nsamp, R, refs, hi, lo, max_gap,
+                                                                             min_len, first)
     n_out = table.n_rec * K * V * 2
     if out is None:
         out = torch.empty((table.n_rec, K, V, 2), device=filt.device, dtype=torch.int32)
@@ -2571,10 +2585,58 @@ def event_score(filt, table, nsamp, R, refs, c, hi, lo, max_gap=0, min_len=0, fi
         _glue_operand(out, f"{fn}: out", torch.int32, filt, n=n_out)
     p_x = _on_gpu(filt, f"{fn}: filt")
     ref, tol, ro = refs.dev(filt.device)
-    _lib.call("eat_event_score", p_x, K, table.G_total, table.dev(filt.device).data_ptr(), table.n_rec, p_ns, R,
+    _lib.call("eat_event_score", p_x, K, table.G_total, table.dev(filt.device).data_ptr(), table.n_rec, nsamp.data_ptr(), R,
               ref.data_ptr() if refs.E else None, tol.data_ptr() if refs.E else None, ro.data_ptr() + 8 * first, refs.E, c,
-              p_hi, p_lo, V, max_gap, min_len, out.data_ptr(), _stream())
+              hi.data_ptr(), lo.data_ptr(), V, max_gap, min_len, out.data_ptr(), _stream())
     return out.view(table.n_rec, K, V, 2)
+
+
+# ------------------------------------------------------------------ PSDS counting (include/eat_psds.h)
+def per_mille(name, x, lowest=1):
+    """A criterion given as a ratio -> its whole number of per-mille in [lowest, 1000]; anything else (a ratio outside the
+    range, or one that is no whole per-mille within 1e-9) is refused by name."""
+    fn = "psds_count"
+    try:
+        f = float(x)
+    except (TypeError, ValueError):
+        raise _lib.EatHipError(f"{fn}: {name}={x!r} is not a number") from None
+    pm = round(1000.0 * f) if f == f and abs(f) < 1e6 else None
+    if pm is None or abs(1000.0 * f - pm) > 1e-9:
+        raise _lib.EatHipError(f"{fn}: {name}={x!r} must be a whole number of per-mille (0.7, 0.105, ...)")
+    if not lowest <= pm <= 1000:
+        raise _lib.EatHipError(f"{fn}: {name}={x!r} must lie in {'(0, 1]' if lowest else '[0, 1]'}")
+    return int(pm)
+
+
+def psds_count(filt, table, nsamp, R, refs, dtc, gtc, cttc, hi, lo, max_gap=0, min_len=0, first=0, out=None, ct=None):
+    """The integer counts behind PSDS of every (recording, class) timeline of filt (K, G_total) at V threshold pairs at once
+    (include/eat_psds.h) -> (counts (n_rec, K, V, 4) int32: (tp, n_det, fp, n_ct), ct (V, K, K) int32 or None).  The
+    detections are the events `detect_events` would list at (hi[v], lo[v], max_gap, min_len), in samples [on R, min(off R,
+    nsamp)); dtc, gtc in (0, 1] and cttc in [0, 1] are the intersection criteria as ratios that are a whole number of
+    per-mille.  ct[v, detection class, reference class] counts cross-triggers and is ADDED TO: allocated zeroed when None and
+    cttc > 0, else the caller's (V, K, K) int32 device buffer; with cttc = 0 it is not touched.  The other operands are
+    `event_score`'s (the tolerances of `refs` are not used).  One launch, no host wait."""
+    fn = "psds_count"
+    dtc_pm, gtc_pm, cttc_pm = per_mille("dtc", dtc), per_mille("gtc", gtc), per_mille("cttc", cttc, 0)
+    table, K, R, max_gap, min_len, first, nsamp, hi, lo, V = _score_operands(fn, filt, table, nsamp, R, refs, hi, lo, max_gap,
+                                                                             min_len, first)
+    if out is None:
+        out = torch.empty((table.n_rec, K, V, 4), device=filt.device, dtype=torch.int32)
+    else:
+        _glue_operand(out, f"{fn}: out", torch.int32, filt, n=table.n_rec * K * V * 4)
+    if ct is not None:
+        if not isinstance(ct, torch.Tensor) or tuple(ct.shape) != (V, K, K):
+            raise _lib.EatHipError(f"{fn}: ct must be a (V, K, K) = ({V}, {K}, {K}) tensor (got {tuple(getattr(ct, 'shape', ()))})")
+        _glue_operand(ct, f"{fn}: ct", torch.int32, filt, n=V * K * K)
+    elif cttc_pm > 0:
+        ct = torch.zeros((V, K, K), device=filt.device, dtype=torch.int32)
+    p_x = _on_gpu(filt, f"{fn}: filt")
+    ref, _, ro = refs.dev(filt.device)
+    _lib.call("eat_psds_count", p_x, K, table.G_total, table.dev(filt.device).data_ptr(), table.n_rec, nsamp.data_ptr(), R,
+              ref.data_ptr() if refs.E else None, ro.data_ptr() + 8 * first, refs.E, dtc_pm, gtc_pm, cttc_pm, hi.data_ptr(),
+              lo.data_ptr(), V, max_gap, min_len, out.data_ptr(), ct.data_ptr() if ct is not None and cttc_pm > 0 else None,
+              _stream())
+    return out.view(table.n_rec, K, V, 4), ct
 
 
 def pw_conv_into(x, pack, Co, act, out):

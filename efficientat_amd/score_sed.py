@@ -3,12 +3,15 @@
     python -m efficientat_amd.score_sed --checkpoint sed.pt --bank DIR [--model mn10_as | --width 1.0]
                                         [--collar_ms 200 --offset_pct 0.2 --median_ms 960 --min_duration_ms 0 --max_gap_ms 0
                                          --low_ratio 1.0 --threshold 0.5] [--save_thresholds ops.json] [--json]
+                                        [--psds 1,2] [--dtc --gtc --cttc --alpha_ct --alpha_st --e_max]
 
 DIR is a decoded strong-label split (sed.load_bank), the checkpoint a state dict of an mlp-head MN with the bank's classes
 (what `finetune_sed --save` writes).  `sed.evaluate_events` runs the detector of `detect` over every clip and scores its
 events with onset / offset collars at the 49 thresholds k / 50 in one kernel launch per chunk of clips.  Prints micro / macro
 F1, precision and recall at `--threshold`, and macro F1 at the per-class best thresholds (tuned on this very split);
 `--save_thresholds` writes those operating points for `detect --thresholds_file`; `--json` prints one JSON line.
+`--psds` adds PSDS (sed.evaluate_psds) of the same detector over the same grid for scenario 1 and / or 2 of DCASE Task 4, as
+`psds_scenario1` / `psds_scenario2`; explicit criteria override the scenario's, and without `--psds` they score under `psds`.
 """
 import argparse
 import contextlib
@@ -18,7 +21,7 @@ import sys
 
 import torch
 
-from .finetune_sed import add_event_args, event_eval
+from .finetune_sed import add_event_args, add_psds_args, event_eval, psds_eval, psds_scenarios
 from .utils import NAME_TO_WIDTH
 
 
@@ -36,6 +39,7 @@ def parse_args(argv=None):
     p.add_argument("--n_mels", type=int, default=128)
     p.add_argument("--json", action="store_true", help="print one JSON line with the results")
     add_event_args(p)
+    add_psds_args(p)
     return p.parse_args(argv)
 
 
@@ -67,10 +71,17 @@ def main(argv=None):
     print(f"[score_sed] {ev['n_clips']} clips, {ev['n_ref']} reference events, {K} classes; at threshold {ev['threshold']:.2f}: "
           f"micro F1 {ev['micro_f1']:.4f}, macro F1 {ev['macro_f1']:.4f}; macro F1 at the per-class best thresholds (tuned on "
           f"this split) {ev['macro_f1_best']:.4f} ({ev['eval_s']:.2f} s)", file=sys.stderr, flush=True)
+    scenarios = psds_scenarios(args)
+    ps_keys = {}
+    if scenarios:
+        ps_keys = psds_eval(args, model, mel, bank, scenarios)
+        print("[score_sed] " + ", ".join(f"{k} {v:.4f}" for k, v in ps_keys.items() if k != "psds_eval_s")
+              + f" ({ps_keys['psds_eval_s']:.2f} s)", file=sys.stderr, flush=True)
     if args.json:
         line = {"what": "efficientat_amd.score_sed", "checkpoint": args.checkpoint, "classes": K, "n_clips": ev["n_clips"],
                 "n_ref": ev["n_ref"]}
         line.update(keys)
+        line.update(ps_keys)
         print(json.dumps(line), flush=True)
     return 0
 

@@ -25,7 +25,8 @@ number of frames; the default 327680 is `EADetector`'s 10.24 s window, 32 frames
 `evaluate_events` scores what `EADetector.detect` lists: event-based F1 with onset / offset collars (sed_eval's
 EventBasedMetrics in integer samples) at a whole grid of thresholds in one kernel launch per chunk of clips
 (`ops.event_score`, include/eat_event_score.h), and picks a threshold per class; `save_operating_points` /
-`load_operating_points` carry them to `detect --thresholds_file`.
+`load_operating_points` carry them to `detect --thresholds_file`.  `evaluate_psds` scores the same event lists with PSDS, the
+intersection-based score of DCASE Task 4, over the same grid (`ops.psds_count`, include/eat_psds.h; `psds_from_counts`).
 The fine-tuned model keeps the reference's state-dict layout (an mlp-head MN with K classes), so its checkpoint loads
 straight into `EADetector(model=...)` and `detect --checkpoint`.  Only MN models with the mlp head on the monolithic plan.
 """
@@ -419,42 +420,23 @@ def pick_thresholds(counts, hi, lo, threshold, low_ratio=1.0):
     return at, best, b_hi, b_lo
 
 
-def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=960, min_duration_ms=0, max_gap_ms=0,
-                    collar_ms=200, offset_pct=0.2, threshold=0.5, batch_clips=256, taper="triangle", clip_seconds=10.24,
-                    hop_seconds=5.12, batch_windows=64):
-    """Event-based (collar) scores of what `detection.EADetector(model=model).detect` lists on a resident strong-label
-    split, at a whole grid of thresholds at once.
-
-    The bank's clips are walked in contiguous chunks of `batch_clips` of the resident flat buffer (no waveform is copied):
-    `detector.plan` on the chunk's lengths, `window_logits` on the slice (through `mel`), `ops.detect_stitch`,
-    `ops.detect_median`, then ONE `ops.event_score` for all thresholds; int64 counts accumulate on the device, with one
-    host wait at the end.  Grid: `threshold_grid(thresholds, low_ratio)`.  An estimated event of frames [on, off) spans the
-    samples [on R, min(off R, n)); it matches a reference of its clip and class iff the onsets are at most
-    c = round(collar_ms sample_rate / 1000) samples apart and the offsets at most max(c, floor(offset_pct length)) of the
-    reference (`event_tolerances`); greedy in reference order as sed_eval's EventBasedMetrics (integer samples: a float-
-    second sed_eval run may differ only where a distance sits exactly on a collar).
-
-    -> {"thresholds", "low_thresholds" (V,) float32; "counts" (V, K, 3) int64 (tp, fp, fn); "grid": {name: (V,) float64} for
-    micro / macro F1, precision, recall (`segment_scores` per threshold); "class_f1" (V, K); "threshold": the grid value
-    nearest the argument (itself when it is on the grid), "threshold_index", and the six scores at it under their plain
-    names; "best_threshold", "best_low_threshold" (K,) float32 and "best_index" (K,) (`pick_thresholds`); "macro_f1_best":
-    macro F1 with those per-class values - TUNED ON THE SCORED SPLIT, an upper bound for any other; "n_clips", "n_ref",
-    "eval_s", "settings"}.  Mode restore and forked RNG as `evaluate_frames`."""
+def _walk_chunks(fn, model, mel, bank, hi, lo, n_acc, score, finish=None, median_ms=960, min_duration_ms=0, max_gap_ms=0,
+                 batch_clips=256, taper="triangle", clip_seconds=10.24, hop_seconds=5.12, batch_windows=64):
+    """The chunk walk `evaluate_events` and `evaluate_psds` share.  The bank's clips are walked in contiguous chunks of
+    `batch_clips` of the resident flat buffer (no waveform is copied): `detector.plan` on the chunk's lengths,
+    `window_logits` on the slice (through `mel`), `ops.detect_stitch`, `ops.detect_median`, then
+    `score(acc, filt, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first)`, which adds the chunk's counts to acc, a flat
+    int64 device buffer of n_acc zeros; `finish(acc)` runs after the last chunk; then the one host wait.  Model and mel
+    are put in eval mode and restored, the RNG is forked.  -> (acc on the host, seconds, K)."""
     n = bank["lengths"].numel()
     if n == 0:
-        raise ValueError("evaluate_events: the split is empty")
+        raise ValueError(f"{fn}: the split is empty")
     if int(batch_clips) < 1:
         raise ValueError(f"batch_clips must be >= 1 (got {batch_clips})")
     _, _, K = detection.check_model(model)
     if len(bank["classes"]) != K:
-        raise ValueError(f"evaluate_events: the bank has {len(bank['classes'])} classes, the model {K}")
-    hi, lo = threshold_grid(thresholds, low_ratio)
-    c = collar_samples(collar_ms, mel.sr)
+        raise ValueError(f"{fn}: the bank has {len(bank['classes'])} classes, the model {K}")
     dev = bank["waves"].device
-    events_cpu = bank["events"].cpu()
-    refs = ops.event_refs(events_cpu, torch.from_numpy(event_tolerances(events_cpu, c, offset_pct)),
-                          bank["event_offsets"].cpu(), K)
-    n_ref = np.bincount(events_cpu[:, 0].numpy(), minlength=K).astype(np.int64)
     lengths = bank["lengths_cpu"].numpy().astype(np.int64)
     offsets = np.cumsum(lengths) - lengths
     was_training = (model.training, mel.training)
@@ -473,7 +455,7 @@ def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=
         with torch.random.fork_rng(devices=[]), torch.no_grad():
             d_hi, d_lo = (t.to(dev) for t in ops.check_threshold_grid(hi, lo))
             d_n = torch.from_numpy(lengths).to(dev)
-            acc = torch.zeros((K, hi.size, 2), device=dev, dtype=torch.int64)
+            acc = torch.zeros((int(n_acc),), device=dev, dtype=torch.int64)
             for i0 in range(0, n, int(batch_clips)):
                 i1 = min(i0 + int(batch_clips), n)
                 starts, valids, table = det.plan(lengths[i0:i1].tolist())
@@ -481,13 +463,54 @@ def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=
                 P = det.window_logits(flat, starts, valids)
                 prob = ops.detect_stitch(P, table, geo.Hf, geo.T, det._wt)
                 filt = ops.detect_median(prob, table, m) if m != 1 else prob
-                cnt = ops.event_score(filt, table, d_n[i0:i1], geo.R, refs, c, d_hi, d_lo, max_gap, min_len, first=i0)
-                acc += cnt.sum(dim=0, dtype=torch.int64)
+                score(acc, filt, table, d_n[i0:i1], geo.R, d_hi, d_lo, max_gap, min_len, i0)
+            if finish is not None:
+                finish(acc)
             res = acc.cpu().numpy()                                           # the one host wait
     finally:
         model.train(was_training[0])
         mel.train(was_training[1])
-    eval_s = time.perf_counter() - t0
+    return res, time.perf_counter() - t0, K
+
+
+def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=960, min_duration_ms=0, max_gap_ms=0,
+                    collar_ms=200, offset_pct=0.2, threshold=0.5, batch_clips=256, taper="triangle", clip_seconds=10.24,
+                    hop_seconds=5.12, batch_windows=64):
+    """Event-based (collar) scores of what `detection.EADetector(model=model).detect` lists on a resident strong-label
+    split, at a whole grid of thresholds at once.
+
+    The bank's clips are walked in contiguous chunks of `batch_clips` of the resident flat buffer (`_walk_chunks`): stitch,
+    median, then ONE `ops.event_score` for all thresholds; int64 counts accumulate on the device, with one
+    host wait at the end.  Grid: `threshold_grid(thresholds, low_ratio)`.  An estimated event of frames [on, off) spans the
+    samples [on R, min(off R, n)); it matches a reference of its clip and class iff the onsets are at most
+    c = round(collar_ms sample_rate / 1000) samples apart and the offsets at most max(c, floor(offset_pct length)) of the
+    reference (`event_tolerances`); greedy in reference order as sed_eval's EventBasedMetrics (integer samples: a float-
+    second sed_eval run may differ only where a distance sits exactly on a collar).
+
+    -> {"thresholds", "low_thresholds" (V,) float32; "counts" (V, K, 3) int64 (tp, fp, fn); "grid": {name: (V,) float64} for
+    micro / macro F1, precision, recall (`segment_scores` per threshold); "class_f1" (V, K); "threshold": the grid value
+    nearest the argument (itself when it is on the grid), "threshold_index", and the six scores at it under their plain
+    names; "best_threshold", "best_low_threshold" (K,) float32 and "best_index" (K,) (`pick_thresholds`); "macro_f1_best":
+    macro F1 with those per-class values - TUNED ON THE SCORED SPLIT, an upper bound for any other; "n_clips", "n_ref",
+    "eval_s", "settings"}.  Mode restore and forked RNG as `evaluate_frames`."""
+    n = bank["lengths"].numel()
+    if n == 0:
+        raise ValueError("evaluate_events: the split is empty")
+    hi, lo = threshold_grid(thresholds, low_ratio)
+    c = collar_samples(collar_ms, mel.sr)
+    K = len(bank["classes"])
+    events_cpu = bank["events"].cpu()
+    refs = ops.event_refs(events_cpu, torch.from_numpy(event_tolerances(events_cpu, c, offset_pct)),
+                          bank["event_offsets"].cpu(), K)
+    n_ref = np.bincount(events_cpu[:, 0].numpy(), minlength=K).astype(np.int64)
+
+    def score(acc, filt, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first):
+        cnt = ops.event_score(filt, table, nsamp, R, refs, c, d_hi, d_lo, max_gap, min_len, first=first)
+        acc += cnt.sum(dim=0, dtype=torch.int64).flatten()
+
+    res, eval_s, K = _walk_chunks("evaluate_events", model, mel, bank, hi, lo, K * hi.size * 2, score, None, median_ms,
+                                  min_duration_ms, max_gap_ms, batch_clips, taper, clip_seconds, hop_seconds, batch_windows)
+    res = res.reshape(K, hi.size, 2)
     tp, n_est = res[:, :, 0].T, res[:, :, 1].T                                # (V, K)
     counts = np.stack([tp, n_est - tp, n_ref[None, :] - tp], axis=2).astype(np.int64)
     rows = [segment_scores(counts[v]) for v in range(hi.size)]
@@ -504,6 +527,131 @@ def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=
                              "max_gap_ms": float(max_gap_ms), "taper": taper, "window_size": float(clip_seconds),
                              "hop_length": float(hop_seconds), "collar_ms": float(collar_ms), "offset_pct": float(offset_pct),
                              "low_ratio": float(low_ratio)}})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- PSDS
+# The polyphonic sound detection score of Bilen et al. (ICASSP 2020), the ranking metric of DCASE Task 4: the two scenarios
+# of that task as (dtc, gtc, cttc, alpha_ct, alpha_st, e_max).
+PSDS_SCENARIOS = {1: {"dtc": 0.7, "gtc": 0.7, "cttc": 0.0, "alpha_ct": 0.0, "alpha_st": 1.0, "e_max": 100.0},
+                  2: {"dtc": 0.1, "gtc": 0.1, "cttc": 0.3, "alpha_ct": 0.5, "alpha_st": 1.0, "e_max": 100.0}}
+
+
+def psds_from_counts(tp, fp, ct, n_ref, ref_seconds, total_seconds, alpha_ct, alpha_st, e_max=100.0):
+    """The PSDS curve and its integral from integer counts, in fp64 on the host.  tp, fp (V, K) per threshold and class,
+    ct (V, K, K) cross-triggers [v, detection class, reference class] (None: none), n_ref (K) reference events and
+    ref_seconds (K) their summed length per class, total_seconds the length of the split.
+
+    TPR = tp / n_ref; FPR = fp per hour of the split; CTR[v, c, c'] = ct per hour of class c' references (0 where it has
+    none); eFPR = FPR + alpha_ct mean over c' != c of CTR (no such term for K = 1).  Per class with references, the points
+    (eFPR, TPR) sorted by eFPR, the largest TPR among equal eFPR, then the running maximum, read as a step function f_c
+    (0 before the first point).  eTPR(x) = mean_c f_c(x) - alpha_st std_c f_c(x) (population std over the classes with
+    references, not clipped); PSDS is the exact integral of that step function over [0, e_max], divided by e_max.  No class
+    with references: NaN.
+    -> {"psds", "efpr" (V, K), "tpr" (V, K) (NaN without references), "etpr_x": the breakpoints from 0 to e_max,
+    "etpr_y": eTPR on the interval that starts at each}."""
+    tp, fp = np.asarray(tp, dtype=np.float64), np.asarray(fp, dtype=np.float64)
+    if tp.ndim != 2 or fp.shape != tp.shape:
+        raise ValueError(f"psds_from_counts: tp and fp must be (V, K) (got {tp.shape}, {fp.shape})")
+    V, K = tp.shape
+    ct = np.zeros((V, K, K)) if ct is None else np.asarray(ct, dtype=np.float64)
+    n_ref, ref_seconds = np.asarray(n_ref, dtype=np.float64), np.asarray(ref_seconds, dtype=np.float64)
+    if ct.shape != (V, K, K) or n_ref.shape != (K,) or ref_seconds.shape != (K,):
+        raise ValueError(f"psds_from_counts: need ct (V, K, K), n_ref (K), ref_seconds (K) for V = {V}, K = {K} "
+                         f"(got {ct.shape}, {n_ref.shape}, {ref_seconds.shape})")
+    total_seconds, e_max = float(total_seconds), float(e_max)
+    if not total_seconds > 0 or not e_max > 0:
+        raise ValueError(f"psds_from_counts: total_seconds and e_max must be positive (got {total_seconds}, {e_max})")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tpr = np.where(n_ref > 0, tp / n_ref, np.nan)
+        ctr = np.where(ref_seconds > 0, ct / (ref_seconds / 3600.0), 0.0)     # (V, K, K'), by reference class
+    efpr = fp / (total_seconds / 3600.0)
+    if K > 1:
+        cross = ctr.sum(axis=2) - ctr[:, np.arange(K), np.arange(K)]
+        efpr = efpr + float(alpha_ct) * cross / (K - 1)
+    out = {"psds": float("nan"), "efpr": efpr, "tpr": tpr, "etpr_x": np.zeros(0), "etpr_y": np.zeros(0)}
+    scored = np.flatnonzero(n_ref > 0)
+    if scored.size == 0:
+        return out
+    curves = []
+    for c in scored:
+        order = np.lexsort((-tpr[:, c], efpr[:, c]))                          # by x, the largest y of equal x first
+        x, y = efpr[order, c], tpr[order, c]
+        first = np.concatenate([[True], x[1:] != x[:-1]])
+        curves.append((x[first], np.maximum.accumulate(y[first])))
+    inside = [x[(x >= 0) & (x <= e_max)] for x, _ in curves]
+    bx = np.unique(np.concatenate(inside + [np.asarray([0.0, e_max])]))
+    f = np.zeros((len(curves), bx.size))
+    for j, (x, y) in enumerate(curves):
+        at = np.searchsorted(x, bx, side="right") - 1                         # the last point with x_j <= x
+        f[j] = np.where(at >= 0, y[np.maximum(at, 0)], 0.0)
+    etpr = f.mean(axis=0) - float(alpha_st) * f.std(axis=0)
+    out.update(psds=float(np.sum(etpr[:-1] * np.diff(bx)) / e_max), etpr_x=bx, etpr_y=etpr)
+    return out
+
+
+def evaluate_psds(model, mel, bank, scenario=1, dtc=None, gtc=None, cttc=None, alpha_ct=None, alpha_st=None, e_max=100.0,
+                  thresholds=None, low_ratio=1.0, median_ms=960, min_duration_ms=0, max_gap_ms=0, batch_clips=256,
+                  taper="triangle", clip_seconds=10.24, hop_seconds=5.12, batch_windows=64):
+    """PSDS of what `detection.EADetector(model=model).detect` lists on a resident strong-label split: the operating points
+    are the grid `threshold_grid(thresholds, low_ratio)`, all counted at once.
+
+    The chunk walk of `evaluate_events` (`_walk_chunks`) with ONE `ops.psds_count` per chunk (include/eat_psds.h: detection
+    and ground-truth intersection criteria dtc / gtc, cross-trigger criterion cttc); int64 counts accumulate on the device,
+    the cross-triggers in the same buffer, with one host wait at the end; `psds_from_counts` then integrates the curve.
+    `scenario` (1 or 2) picks a row of `PSDS_SCENARIOS`; dtc, gtc, cttc, alpha_ct, alpha_st given explicitly override it
+    (e_max is the argument's).  This restates the definitions of the psds_eval package in integer samples; no run of that
+    package stands behind it.
+
+    -> {"thresholds", "low_thresholds" (V,) float32; "counts" (V, K, 3) int64 (tp, fp, fn); "n_det" (V, K); "ct" (V, K, K)
+    int64; "psds", "efpr", "tpr", "etpr_x", "etpr_y" of `psds_from_counts`; "n_ref", "ref_seconds" (K,); "total_seconds";
+    "n_clips", "eval_s", "settings"}."""
+    if scenario not in PSDS_SCENARIOS:
+        raise ValueError(f"evaluate_psds: scenario must be one of {sorted(PSDS_SCENARIOS)} (got {scenario!r})")
+    st = dict(PSDS_SCENARIOS[scenario])
+    st["e_max"] = float(e_max)
+    for name, val in (("dtc", dtc), ("gtc", gtc), ("cttc", cttc), ("alpha_ct", alpha_ct), ("alpha_st", alpha_st)):
+        if val is not None:
+            st[name] = float(val)
+    for name in ("dtc", "gtc", "cttc"):
+        ops.per_mille(name, st[name], 0 if name == "cttc" else 1)
+    n = bank["lengths"].numel()
+    if n == 0:
+        raise ValueError("evaluate_psds: the split is empty")
+    hi, lo = threshold_grid(thresholds, low_ratio)
+    V, K = hi.size, len(bank["classes"])
+    events_cpu = bank["events"].cpu()
+    refs = ops.event_refs(events_cpu, torch.zeros(events_cpu.shape[0], dtype=torch.int32), bank["event_offsets"].cpu(), K)
+    ev = events_cpu.numpy().astype(np.int64)
+    n_ref = np.bincount(ev[:, 0], minlength=K).astype(np.int64)
+    ref_seconds = np.bincount(ev[:, 0], weights=(ev[:, 2] - ev[:, 1]).astype(np.float64), minlength=K) / float(mel.sr)
+    total_seconds = float(bank["lengths_cpu"].to(torch.int64).sum()) / float(mel.sr)
+    cross = [None]                                                            # (V, K, K) int32, added to by every chunk
+
+    def score(acc, filt, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first):
+        cnt, cross[0] = ops.psds_count(filt, table, nsamp, R, refs, st["dtc"], st["gtc"], st["cttc"], d_hi, d_lo, max_gap,
+                                       min_len, first=first, ct=cross[0])
+        acc[:K * V * 4] += cnt.sum(dim=0, dtype=torch.int64).flatten()
+
+    def finish(acc):
+        if cross[0] is not None:
+            acc[K * V * 4:] = cross[0].flatten()
+
+    res, eval_s, K = _walk_chunks("evaluate_psds", model, mel, bank, hi, lo, K * V * 4 + V * K * K, score, finish, median_ms,
+                                  min_duration_ms, max_gap_ms, batch_clips, taper, clip_seconds, hop_seconds, batch_windows)
+    per = res[:K * V * 4].reshape(K, V, 4).transpose(1, 0, 2)                 # (V, K, 4): tp, n_det, fp, n_ct
+    ct = res[K * V * 4:].reshape(V, K, K).astype(np.int64)
+    tp, fp = per[:, :, 0], per[:, :, 2]
+    out = {"thresholds": hi, "low_thresholds": lo,
+           "counts": np.stack([tp, fp, n_ref[None, :] - tp], axis=2).astype(np.int64), "n_det": per[:, :, 1].astype(np.int64),
+           "ct": ct}
+    out.update(psds_from_counts(tp, fp, ct, n_ref, ref_seconds, total_seconds, st["alpha_ct"], st["alpha_st"], st["e_max"]))
+    settings = {"scenario": scenario, "median_ms": float(median_ms), "min_duration_ms": float(min_duration_ms),
+                "max_gap_ms": float(max_gap_ms), "taper": taper, "window_size": float(clip_seconds),
+                "hop_length": float(hop_seconds), "low_ratio": float(low_ratio)}
+    settings.update(st)
+    out.update({"n_ref": n_ref, "ref_seconds": ref_seconds, "total_seconds": total_seconds, "n_clips": n, "eval_s": eval_s,
+                "settings": settings})
     return out
 
 
