@@ -11,6 +11,10 @@ val_loss); with `--event_eval` also event by event (sed.evaluate_events: collar-
 post-processing of `detect` given by `--median_ms --min_duration_ms --max_gap_ms --low_ratio`), and `--save_thresholds FILE`
 writes the per-class operating points of the last validation for `detect --thresholds_file`; with `--psds_eval` also with
 PSDS (sed.evaluate_psds: the scenarios of `--psds`, default both, criteria `--dtc --gtc --cttc --alpha_ct --alpha_st --e_max`).
+A training bank may hold weakly labelled clips (strong.npy: clip-level tags only, e.g. DESED's weak.tsv through
+`tools/strong_to_bank.py --weak_tsv`): `--weak_weight W` with W > 0 trains on strong and weak clips in the same batches
+(sed.GraphedWeakFrameTrainer / WeakFrameTrainer: the frame BCE over the clips with frame truth + W times a clip-level BCE
+behind linear-softmax pooling of the frame probabilities, one kernel).  The validation bank must be all strong.
 `--save` writes the final plain state dict: an mlp-head MN with K = the bank's classes, which
 `detection.EADetector(model=...)` and `python -m efficientat_amd.detect --checkpoint` accept.  `--init_checkpoint` loads a
 local state dict and drops its output layer when the class count differs (finetune.load_init_checkpoint).
@@ -110,6 +114,16 @@ def psds_eval(args, model, mel, bank, scenarios):
     return keys
 
 
+def check_weak_banks(args, n_weak_train, n_weak_valid):
+    """The rules of weakly labelled clips, as argument errors: a training bank that holds some needs --weak_weight > 0, a
+    validation bank must hold none."""
+    error = argparse.ArgumentParser(prog="finetune_sed", add_help=False).error     # (exit status 2, as parse_args' own)
+    if n_weak_train and not args.weak_weight > 0:
+        error(f"--train_bank holds {n_weak_train} weakly labelled clips (strong.npy): set --weak_weight W > 0 to train on them")
+    if n_weak_valid:
+        error(f"--valid_bank holds {n_weak_valid} weakly labelled clips (strong.npy): scoring needs onset / offset truth")
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="strong-label SED fine-tuning on the HIP path")
     p.add_argument("--train_bank", required=True, help="decoded training split (sed.load_bank)")
@@ -147,6 +161,8 @@ def parse_args(argv=None):
     p.add_argument("--clip_frames", type=int, default=32, help="frames per training clip and evaluation window (32 = 10.24 s)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no_graph", action="store_true", help="eager FrameBCETrainer instead of the captured step")
+    p.add_argument("--weak_weight", type=float, default=0.0,
+                   help="weight of the pooled clip-level BCE; > 0 trains on weakly labelled clips as well (strong.npy)")
     p.add_argument("--max_steps", type=int, default=0, help="stop after this many steps (benchmarks / tests); 0 = whole epochs")
     p.add_argument("--precision", default=None, help="model.train_precision (auto / fp32 / bf16)")
     add_event_args(p)
@@ -162,6 +178,8 @@ def parse_args(argv=None):
         p.error("frame-level training covers the static MobileNets (mn*) only")
     if args.clip_frames < 1:
         p.error("--clip_frames must be >= 1")
+    if not 0.0 <= args.weak_weight < float("inf"):
+        p.error("--weak_weight must be finite and not negative")
     args.head_type, args.resample_rate, args.pretrain_final_temp = "mlp", 32000, 1.0
     return args
 
@@ -182,6 +200,8 @@ def main(argv=None):
     t_load = time.perf_counter() - t_load
     if train["classes"] != valid["classes"]:
         raise SystemExit("finetune_sed: the two banks differ in classes.txt")
+    check_weak_banks(args, sed.n_weak(train), sed.n_weak(valid))
+    weak = args.weak_weight > 0
     n_train, K = train["lengths"].numel(), len(train["classes"])
     print(f"[finetune_sed] {n_train} training / {valid['lengths'].numel()} validation clips, {K} classes, "
           f"{train['events'].shape[0]} / {valid['events'].shape[0]} events resident on {dev} ({t_load:.1f} s to load)",
@@ -198,8 +218,12 @@ def main(argv=None):
     mel.train()
     common = dict(clip_samples=L, mixup_alpha=args.mixup_alpha, gain_augment=args.gain_augment, roll=not args.no_roll,
                   wavmix=not args.no_wavmix)
-    trainer = (sed.GraphedFrameBCETrainer(model, mel, opt, train, args.batch_size, **common) if graphed
-               else sed.FrameBCETrainer(model, mel, opt, train, **common))
+    if weak:
+        trainer = (sed.GraphedWeakFrameTrainer(model, mel, opt, train, args.batch_size, weak_weight=args.weak_weight, **common)
+                   if graphed else sed.WeakFrameTrainer(model, mel, opt, train, weak_weight=args.weak_weight, **common))
+    else:
+        trainer = (sed.GraphedFrameBCETrainer(model, mel, opt, train, args.batch_size, **common) if graphed
+                   else sed.FrameBCETrainer(model, mel, opt, train, **common))
 
     steps_total, clips_total, t_train = 0, 0, 0.0
     ev, stats, done = None, {"train_loss": float("nan")}, False
@@ -249,6 +273,9 @@ def main(argv=None):
                 "launch": "hipGraph replay" if graphed else "eager", "threshold": args.threshold,
                 "train_loss": stats["train_loss"], "clips_per_s": round(clips_total / max(t_train, 1e-9), 1),
                 "n_frames": ev["n_frames"], "eval_s": round(ev["eval_s"], 3), "checkpoint": args.save}
+        if weak:
+            line.update({"weak_weight": args.weak_weight, "n_weak": sed.n_weak(train),
+                         "train_frame_loss": stats["train_frame_loss"], "train_clip_loss": stats["train_clip_loss"]})
         line.update({k: ev[k] for k in METRICS})
         line.update(ee_keys)
         line.update(ps_keys)

@@ -2805,3 +2805,78 @@ def frame_hidden_bwd(dh, z1, keep, H, T):
     _lib.call("eat_frame_hidden_bwd", p_dh, _on_gpu(z1, f"{fn}: z1"), p_keep, dz1.data_ptr(), db1.data_ptr(), B, H, Hp, T, Tp,
               _stream())
     return dz1, db1
+
+
+# ------------------------------------------------------------------ weak-label SED training (include/eat_weak_sed.h)
+def sed_clip_targets(bank, idx, start, mix, L, out=None, framed_out=None):
+    """Clip-level targets w (B, K) and the frame-truth flag framed (B) int32 of the batch that `wave_augment_ragged` builds
+    from the same tables (include/eat_weak_sed.h: eat_sed_clip_targets).  bank: the dict of `sed.load_bank`; its "strong"
+    (N) uint8 marks the clips with onset / offset annotation (absent: every clip).  idx / start (2B) int32, mix (B) fp32:
+    CPU tensors are validated here with `check_ragged_draws` and uploaded; device tensors (the static buffers of a captured
+    step) must have been validated before they were staged.  L samples per window.  -> (w, framed)."""
+    fn = "sed_clip_targets"
+    events, eo, lengths, strong = bank["events"], bank["event_offsets"], bank["lengths"], bank.get("strong")
+    n_bank, K = lengths.numel(), len(bank["classes"])
+    L = int(L)
+    B = torch.as_tensor(mix).numel()
+    dev = lengths.device
+    if L < 1 or B < 1:
+        raise _lib.EatHipError(f"{fn}: need B, L >= 1 (got B={B} L={L})")
+    if not idx.is_cuda:
+        check_ragged_draws(idx, start, torch.zeros_like(torch.as_tensor(idx)), bank["lengths_cpu"], L)
+        idx, start = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, start))
+        mix = mix.to(dev, torch.float32, non_blocking=True)
+    if (events.dtype != torch.int32 or events.dim() != 2 or events.shape[1] != 3 or not events.is_contiguous()
+            or events.device != dev):
+        raise _lib.EatHipError(f"{fn}: events must be a contiguous (E, 3) int32 tensor on {dev}")
+    if eo.dtype != torch.int64 or eo.numel() != n_bank + 1 or not eo.is_contiguous() or eo.device != dev:
+        raise _lib.EatHipError(f"{fn}: event_offsets must be a contiguous int64 tensor of N + 1 = {n_bank + 1} values on {dev}")
+    p_strong = None if strong is None else _glue_operand(strong, f"{fn}: strong", torch.uint8, lengths, n=n_bank)
+    p_mix = _glue_operand(mix, f"{fn}: mix", torch.float32, lengths, n=B)
+    w = _head_out(out, f"{fn}: out", (B, K), lengths)
+    if framed_out is None:
+        framed_out = torch.empty((B,), device=dev, dtype=torch.int32)
+    p_framed = _glue_operand(framed_out, f"{fn}: framed_out", torch.int32, lengths, n=B)
+    E = events.shape[0]
+    _lib.call("eat_sed_clip_targets", events.data_ptr() if E else None, E, eo.data_ptr(), _dev_int32(lengths, "lengths", n_bank),
+              n_bank, K, _dev_int32(idx, "idx", 2 * B), _dev_int32(start, "start", 2 * B), p_mix, p_strong, B, L,
+              _on_gpu(w, f"{fn}: out"), p_framed, _stream())
+    return w.view(B, K), framed_out
+
+
+def weak_frame_bce_fwd_bwd(z, y, w, framed, T, perm=None, lam=None, weak_weight=1.0, eps=1e-7, sums=None, grad=True, Kp=None,
+                           dbias=False, clip_prob=None):
+    """Frame BCE of z (B, K, Tp) against y (B, K, Tp) over the samples with framed (B) int32 != 0, plus `weak_weight` times
+    the clip-level BCE of the linear-softmax pooled frame probabilities against w (B, K), the log-mel mix-up of both targets
+    folded in (include/eat_weak_sed.h: eat_weak_frame_bce_fwd_bwd).
+    -> (dlogits (B, Kp, Tp) or None with grad=False, dbias (K) or None): d loss / d z with exactly-zero pad rows and columns.
+    `sums` (>= 3 fp32) += (loss, frame term, clip term); `clip_prob` (B, K) fp32 receives the pooled probabilities."""
+    fn = "weak_frame_bce_fwd_bwd"
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: z must be a non-empty (B, K, Tp) tensor, got {tuple(getattr(z, 'shape', ()))}")
+    B, K, Tp = z.shape
+    T = int(T)
+    Kp = K if Kp is None else int(Kp)
+    weak_weight, eps = float(weak_weight), float(eps)
+    if T < 1 or Tp < T or Kp < K:
+        raise _lib.EatHipError(f"{fn}: need 1 <= T <= Tp and Kp >= K (got T={T} Tp={Tp} K={K} Kp={Kp})")
+    if not 0.0 <= weak_weight < float("inf"):
+        raise _lib.EatHipError(f"{fn}: weak_weight must be finite and not negative (got {weak_weight})")
+    if not 0.0 < eps < 0.5:
+        raise _lib.EatHipError(f"{fn}: eps must lie in (0, 0.5) (got {eps})")
+    _glue_operand(z, f"{fn}: z", torch.float32, z)
+    p_y = _glue_operand(y, f"{fn}: y", torch.float32, z, n=B * K * Tp)
+    p_w = _glue_operand(w, f"{fn}: w", torch.float32, z, n=B * K)
+    p_framed = _glue_operand(framed, f"{fn}: framed", torch.int32, z, n=B)
+    p_perm, p_lam = _mix_operands(fn, perm, lam, B, z)
+    p_cp = None if clip_prob is None else _glue_operand(clip_prob, f"{fn}: clip_prob", torch.float32, z, n=B * K)
+    p_sums = ws = None
+    if sums is not None:
+        p_sums = _glue_operand(sums, f"{fn}: sums", torch.float32, z, at_least=3)
+        ws = torch.empty(2 * K + 1, device=z.device, dtype=torch.float64)
+    dl = torch.empty((B, Kp, Tp), device=z.device, dtype=torch.float32) if grad else None
+    db = torch.empty((K,), device=z.device, dtype=torch.float32) if dbias else None
+    _lib.call("eat_weak_frame_bce_fwd_bwd", _on_gpu(z, f"{fn}: z"), p_y, p_w, p_framed, p_perm, p_lam, weak_weight, eps, B, K, T,
+              Tp, Kp, p_sums, None if dl is None else dl.data_ptr(), None if db is None else db.data_ptr(), p_cp,
+              None if ws is None else ws.data_ptr(), _stream())
+    return dl, db

@@ -11,6 +11,8 @@ clip labels
     events.npy         (E, 3) int32 rows (class, onset sample, offset sample)
     event_offsets.npy  (N + 1,) int64: clip i owns the event rows [eo[i], eo[i + 1]), sorted by (class, onset), with
                        0 <= onset < offset <= lengths[i] and 0 <= class < K; a clip may have none
+    strong.npy         optional, (N,) uint8 in {0, 1}: 0 marks a WEAKLY labelled clip, one with clip-level tags only; its
+                       tags are stored as events that span the whole clip, (class, 0, lengths[i]).  Absent: all ones
 
 and kept on the GPU (`load_bank`) as the ragged bank `ops.wave_augment_ragged` takes, plus the event table.  A training
 step draws the FSD50K augmentation (`draw_augment` IS `fsd50k.draw_augment`), builds the waveforms with
@@ -27,6 +29,11 @@ EventBasedMetrics in integer samples) at a whole grid of thresholds in one kerne
 (`ops.event_score`, include/eat_event_score.h), and picks a threshold per class; `save_operating_points` /
 `load_operating_points` carry them to `detect --thresholds_file`.  `evaluate_psds` scores the same event lists with PSDS, the
 intersection-based score of DCASE Task 4, over the same grid (`ops.psds_count`, include/eat_psds.h; `psds_from_counts`).
+A bank with weakly labelled clips (strong.npy) trains with `WeakFrameTrainer` / `GraphedWeakFrameTrainer`: the frame BCE
+over the samples whose clips carry frame truth plus a clip-level BCE behind linear-softmax pooling of the frame
+probabilities, P = sum_t p_t^2 / sum_t p_t (Wang et al., ICASSP 2019), in one kernel (`weak_frame_loss`,
+include/eat_weak_sed.h); the pooling has no parameters, so the checkpoint stays what it was.  The evaluators need onset /
+offset truth and refuse such a bank.
 The fine-tuned model keeps the reference's state-dict layout (an mlp-head MN with K classes), so its checkpoint loads
 straight into `EADetector(model=...)` and `detect --checkpoint`.  Only MN models with the mlp head on the monolithic plan.
 """
@@ -56,8 +63,8 @@ def load_bank(path, device=None):
     """A decoded strong-label split (see the module header) -> the dict of `fsd50k.load_bank` (waves (S) fp32, offsets (N)
     int64, lengths (N) int32, clip_sum (N) fp64, bank_y (N, K) fp32 on `device` when given, else on the CPU; lengths_cpu,
     names) with bank_y the WEAK labels (the class has at least one event in the clip), plus events (E, 3) int32 and
-    event_offsets (N + 1) int64 on the device and classes (K names).  Every violation of the format is a ValueError naming
-    the file."""
+    event_offsets (N + 1) int64 on the device, classes (K names), strong (N) uint8 on the device (strong.npy; all ones
+    without the file) and n_weak, the host count of its zeros.  Every violation of the format is a ValueError naming the file."""
     what = f"SED bank at {path}"
     waves, lengths = fsd50k.read_waves(path, what)
     n = lengths.shape[0]
@@ -93,10 +100,39 @@ def load_bank(path, device=None):
         raise ValueError(f"{what}: events.npy row {e} is out of order: a clip's events are sorted by (class, onset)")
     weak = np.zeros((n, K), dtype=np.float32)
     weak[clip, cls] = 1.0
+    strong = np.ones(n, dtype=np.uint8)
+    if os.path.exists(os.path.join(path, "strong.npy")):
+        strong = np.load(os.path.join(path, "strong.npy"))
+        if strong.shape != (n,) or strong.dtype != np.uint8:
+            raise ValueError(f"{what}: strong.npy must be (N,) = ({n},) uint8, got {strong.dtype} {strong.shape}")
+        if bool((strong > 1).any()):
+            raise ValueError(f"{what}: strong.npy holds a value outside {{0, 1}}")
+        bad = (strong[clip] == 0) & ((on != 0) | (off != lengths[clip]))
+        if bool(bad.any()):
+            e = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"{what}: strong.npy marks clip {int(clip[e])} weak, but events.npy row {e} = {events[e].tolist()} "
+                             f"does not span the whole clip (0, {int(lengths[clip[e]])})")
 
     dev = torch.device("cpu") if device is None else device
     return dict(fsd50k.resident_waves(waves, lengths, dev), bank_y=torch.from_numpy(weak).to(dev), names=names, classes=classes,
-                events=torch.from_numpy(np.ascontiguousarray(events)).to(dev), event_offsets=torch.from_numpy(eo).to(dev))
+                events=torch.from_numpy(np.ascontiguousarray(events)).to(dev), event_offsets=torch.from_numpy(eo).to(dev),
+                strong=torch.from_numpy(np.ascontiguousarray(strong)).to(dev), n_weak=int((strong == 0).sum()))
+
+
+def n_weak(bank):
+    """The number of weakly labelled clips of a bank: the host count `load_bank` took, else read off its "strong" vector
+    (0 without one)."""
+    if "n_weak" in bank:
+        return int(bank["n_weak"])
+    strong = bank.get("strong")
+    return 0 if strong is None else int((strong == 0).sum())
+
+
+def _refuse_weak(fn, bank):
+    n = n_weak(bank)
+    if n:
+        raise ValueError(f"{fn}: strong.npy marks {n} of the bank's clips weakly labelled; scoring needs onset / offset truth "
+                         f"for every clip")
 
 
 def frame_bce_loss(logits, y, T, perm=None, lam=None, sums=None):
@@ -107,6 +143,18 @@ def frame_bce_loss(logits, y, T, perm=None, lam=None, sums=None):
         sums = torch.zeros(1, device=logits.device, dtype=torch.float64)
     y = y.contiguous().float()
     return FusedLoss.apply(logits, sums, 1, lambda z, step: ops.frame_bce_fwd_bwd(z, y, T, perm, lam, sums=step)[0])
+
+
+def weak_frame_loss(logits, y, w, framed, T, perm=None, lam=None, weak_weight=1.0, sums=None):
+    """Frame BCE of frame logits (B, K, Tp) against y (B, K, Tp) over the samples with framed (B) int32 != 0, plus
+    `weak_weight` times the clip-level BCE of their linear-softmax pooling against the clip targets w (B, K), the mix-up
+    (perm, lam) folded into both targets, as a device scalar that supports .backward() (include/eat_weak_sed.h:
+    eat_weak_frame_bce_fwd_bwd); `sums` (3,) accumulates (loss, frame term, clip term) across calls."""
+    if sums is None:
+        sums = torch.zeros(3, device=logits.device, dtype=torch.float64)
+    y, w, weak_weight = y.contiguous().float(), w.contiguous().float(), float(weak_weight)
+    return FusedLoss.apply(logits, sums, 3, lambda z, step: ops.weak_frame_bce_fwd_bwd(z, y, w, framed, T, perm, lam, weak_weight,
+                                                                                     sums=step)[0])
 
 
 def frame_geometry(model, mel, clip_samples):
@@ -186,7 +234,10 @@ class GraphedFrameBCETrainer(GraphedTrainer, FrameBCETrainer):
     def __init__(self, model, mel, optimizer, bank, batch_size, clip_samples=CLIP_SAMPLES, mixup_alpha=0.3, gain_augment=12,
                  roll=True, wavmix=True, warmup=2):
         FrameBCETrainer.__init__(self, model, mel, optimizer, bank, clip_samples, mixup_alpha, gain_augment, roll, wavmix)
-        dev, B = bank["waves"].device, int(batch_size)
+        self._setup_rings(int(batch_size), warmup)
+
+    def _setup_rings(self, B, warmup):
+        dev = self.bank["waves"].device
         first = torch.full((2 * B,), -1, device=dev, dtype=torch.int32)
         first[0::2] = 0                                                       # (clip 0 from its start, no wave-mix: the warm-up batch)
         self._idx = HostRing(first)
@@ -227,6 +278,69 @@ class GraphedFrameBCETrainer(GraphedTrainer, FrameBCETrainer):
         self._shift.put(shift)
         self._amp.put(amp)
         self._mix.put(mix)
+
+
+class WeakFrameTrainer(FrameBCETrainer):
+    """`FrameBCETrainer` on a bank that mixes strongly and weakly labelled clips (`bank["strong"]`): the strong step plus
+    the clip targets and the frame-truth flag from the same uploaded tables (`ops.sed_clip_targets`), and `weak_frame_loss`
+    - the frame BCE over the samples whose clips all carry frame truth plus `weak_weight` times the pooled clip BCE over
+    every sample - in place of `frame_bce_loss`.  Batches are drawn from the whole bank; nothing is stratified."""
+
+    STATS = ("train_loss", "train_frame_loss", "train_clip_loss")
+
+    def __init__(self, model, mel, optimizer, bank, clip_samples=CLIP_SAMPLES, mixup_alpha=0.3, gain_augment=12, roll=True,
+                 wavmix=True, weak_weight=1.0):
+        FrameBCETrainer.__init__(self, model, mel, optimizer, bank, clip_samples, mixup_alpha, gain_augment, roll, wavmix)
+        self._weak_setup(weak_weight)
+
+    def _weak_setup(self, weak_weight):
+        self.weak_weight = float(weak_weight)
+        if not 0.0 <= self.weak_weight < float("inf"):
+            raise ValueError(f"weak_weight must be finite and not negative (got {weak_weight})")
+        n = self.bank["lengths"].numel()
+        strong = self.bank.get("strong")
+        if strong is None or strong.dtype != torch.uint8 or strong.numel() != n or strong.device != self.bank["lengths"].device:
+            raise ValueError("WeakFrameTrainer: the bank needs strong (N) uint8 next to its lengths (sed.load_bank)")
+        self.sums = torch.zeros(3, device=self.sums.device, dtype=torch.float64)
+
+    def loss_and_backward(self, batch):
+        """augment + frame and clip targets -> mel -> log-mel mix-up -> frame logits -> fused frame + clip BCE -> backward."""
+        dev = self.bank["waves"].device
+        idx, start, shift, amp, mix = self.draw(batch)                        # validated: uploaded once for the three kernels
+        idx, start, shift = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, start, shift))
+        amp, mix = (t.to(dev, torch.float32, non_blocking=True) for t in (amp, mix))
+        x, _ = ops.wave_augment_ragged(self.bank, idx, start, shift, amp, mix, self.L, labels=False)
+        y = ops.sed_targets(self.bank, idx, start, shift, mix, self.L, self.R, self.T, self.Tp)
+        w, framed = ops.sed_clip_targets(self.bank, idx, start, mix, self.L)
+        spec = self.mel(x).unsqueeze(1)
+        spec, perm, lam = self._mixup(spec)                                   # host draws, reference order
+        loss = weak_frame_loss(self._frames(spec), y, w, framed, self.T, perm, lam, self.weak_weight, self.sums)
+        loss.backward()
+        return loss.detach()
+
+
+class GraphedWeakFrameTrainer(GraphedFrameBCETrainer, WeakFrameTrainer):
+    """`WeakFrameTrainer` captured once and replayed, on `GraphedFrameBCETrainer`'s scheme: `eat_sed_clip_targets` runs
+    inside the graph next to `eat_sed_targets` and fills the static (B, K) clip targets and (B) frame-truth flags.  The loss
+    kernel counts the framed samples on the device, so the one graph serves every mixture of strong and weak clips, a batch
+    without any frame truth included."""
+
+    def __init__(self, model, mel, optimizer, bank, batch_size, clip_samples=CLIP_SAMPLES, mixup_alpha=0.3, gain_augment=12,
+                 roll=True, wavmix=True, warmup=2, weak_weight=1.0):
+        FrameBCETrainer.__init__(self, model, mel, optimizer, bank, clip_samples, mixup_alpha, gain_augment, roll, wavmix)
+        self._weak_setup(weak_weight)
+        dev, B = bank["waves"].device, int(batch_size)
+        self.w = torch.zeros((B, self.K), device=dev)
+        self.framed = torch.zeros((B,), device=dev, dtype=torch.int32)
+        self._setup_rings(B, warmup)
+
+    def _front(self, fmask=(0, 0), tmask=(0, 0)):
+        ops.sed_clip_targets(self.bank, self._idx.dev, self._start.dev, self._mix.dev, self.L, out=self.w, framed_out=self.framed)
+        super()._front(fmask, tmask)
+
+    def _graph_loss(self, z, perm, lam):
+        return weak_frame_loss(z, self.y.view(self.B, self.K, self.Tp), self.w, self.framed, self.T, perm, lam, self.weak_weight,
+                               self.sums)
 
 
 def eval_windows(lengths, L):
@@ -279,6 +393,7 @@ def evaluate_frames(model, mel, bank, batch_windows=64, threshold=0.5, clip_samp
     sigmoid(logit) >= threshold (a scalar or one value per class) - what `EADetector` binarises without median filter.
     val_loss: the mean BCE over all valid (frame, class) pairs.  One host wait at the end; mode restore and forked RNG as
     `finetune.evaluate_multilabel`."""
+    _refuse_weak("evaluate_frames", bank)
     n = bank["lengths"].numel()
     if n == 0:
         raise ValueError("evaluate_frames: the split is empty")
@@ -493,6 +608,7 @@ def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=
     names; "best_threshold", "best_low_threshold" (K,) float32 and "best_index" (K,) (`pick_thresholds`); "macro_f1_best":
     macro F1 with those per-class values - TUNED ON THE SCORED SPLIT, an upper bound for any other; "n_clips", "n_ref",
     "eval_s", "settings"}.  Mode restore and forked RNG as `evaluate_frames`."""
+    _refuse_weak("evaluate_events", bank)
     n = bank["lengths"].numel()
     if n == 0:
         raise ValueError("evaluate_events: the split is empty")
@@ -615,6 +731,7 @@ def evaluate_psds(model, mel, bank, scenario=1, dtc=None, gtc=None, cttc=None, a
             st[name] = float(val)
     for name in ("dtc", "gtc", "cttc"):
         ops.per_mille(name, st[name], 0 if name == "cttc" else 1)
+    _refuse_weak("evaluate_psds", bank)
     n = bank["lengths"].numel()
     if n == 0:
         raise ValueError("evaluate_psds: the split is empty")

@@ -6,11 +6,13 @@ Workload: a synthetic strong-label bank (tests/sed_ref.synth_bank: clips of 4 - 
 random weights and `--classes` classes, clips of 327680 samples (32 frames), fp32 log-mel, train_precision 'auto'.
   (a) eager   sed.FrameBCETrainer.step
   (b) graph   sed.GraphedFrameBCETrainer.step (one replay per step)
+  (c) weak_graph  sed.GraphedWeakFrameTrainer.step on the same clips with every third marked weak (strong.npy), weak_weight 1
 Both are warmed up, then run alternately in one process, `--steps` steps per leg and `--repeats` legs each; each time is a
 host clock around work that ends in a device synchronise, divided by the steps.  `clip_level_graph` is
 finetune.GraphedBCETrainer on the same bank (the weak labels) for the cost of the frame path over the clip-level one.
 The glue kernels are a host clock around 20 back-to-back launches, divided by 20, at the AudioSet shape (B, 527, 32):
-eat_sed_targets, eat_frame_bce_fwd_bwd (loss + gradient), eat_frame_grad_pad, eat_frame_hidden_fwd / _bwd at H = 1280.
+eat_sed_targets, eat_frame_bce_fwd_bwd (loss + gradient), eat_frame_grad_pad, eat_frame_hidden_fwd / _bwd at H = 1280,
+eat_sed_clip_targets and eat_weak_frame_bce_fwd_bwd (loss + gradient) at the same shape and at K = 10.
 `evaluate_frames` scores the whole bank."""
 import argparse
 import contextlib
@@ -34,6 +36,7 @@ from efficientat_amd.mn import get_model  # noqa: E402
 from efficientat_amd.optim import FusedAdam  # noqa: E402
 from efficientat_amd.preprocess import AugmentMelSTFT  # noqa: E402
 from tests import sed_ref as R  # noqa: E402
+from tests import weak_sed_ref as W  # noqa: E402
 
 
 def timed(fn):
@@ -68,6 +71,8 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         R.synth_bank(d, n_clips=args.clips, K=K, seed=1, lo_s=4.0, hi_s=14.0)
         bank = sed.load_bank(d, device=dev)
+        W.weaken_bank(d)
+        weak_bank = sed.load_bank(d, device=dev)
 
     def trainer(kind):
         torch.manual_seed(0)
@@ -78,9 +83,11 @@ def main():
             return sed.FrameBCETrainer(m, mel, opt, bank, clip_samples=L)
         if kind == "graph":
             return sed.GraphedFrameBCETrainer(m, mel, opt, bank, B, clip_samples=L)
+        if kind == "weak_graph":
+            return sed.GraphedWeakFrameTrainer(m, mel, opt, weak_bank, B, clip_samples=L, weak_weight=1.0)
         return GraphedBCETrainer(m, mel, opt, bank, B, clip_samples=L)
 
-    legs = {k: trainer(k) for k in ("eager", "graph", "clip_level_graph")}
+    legs = {k: trainer(k) for k in ("eager", "graph", "weak_graph", "clip_level_graph")}
     rng = np.random.RandomState(0)
 
     def run(tr):
@@ -94,9 +101,11 @@ def main():
         for k, tr in legs.items():
             times[k].append(timed(lambda: run(tr))[0] / args.steps)
     result = {"workload": {"batch": B, "clips": args.clips, "classes": K, "clip_samples": L, "frames": 32,
-                           "steps_per_leg": args.steps, "bank_seconds": bank["waves"].numel() / 32000.0},
+                           "steps_per_leg": args.steps, "bank_seconds": bank["waves"].numel() / 32000.0,
+                           "weak_clips": sed.n_weak(weak_bank)},
               "step": {k: summary(v) for k, v in times.items()}}
     result["graph_over_eager"] = result["step"]["graph"]["median_s"] / result["step"]["eager"]["median_s"]
+    result["weak_over_strong_graph"] = result["step"]["weak_graph"]["median_s"] / result["step"]["graph"]["median_s"]
     result["frame_over_clip_level"] = result["step"]["graph"]["median_s"] / result["step"]["clip_level_graph"]["median_s"]
 
     ev = legs["graph"]
@@ -116,12 +125,20 @@ def main():
     z1 = torch.randn(B, 1280, T, device=dev)
     keep = torch.ones(B, 1280, device=dev)
     step = torch.zeros(1, device=dev)
+    big_weak = dict(weak_bank, classes=big["classes"])
+    w, framed = ops.sed_clip_targets(big_weak, idx, start, mix, L)
+    step3 = torch.zeros(3, device=dev)
+    z10, y10, w10 = z[:, :10].contiguous(), torch.zeros((B, 10, T), device=dev), w[:, :10].contiguous()
     glue = {
         "sed_targets": lambda: ops.sed_targets(big, idx, start, shift, mix, L, L // T, T, T, out=y),
         "frame_bce_fwd_bwd": lambda: ops.frame_bce_fwd_bwd(z, y, T, sums=step),
         "frame_grad_pad": lambda: ops.frame_grad_pad(z, T, 528),
         "frame_hidden_fwd": lambda: ops.frame_hidden_fwd(z1, keep),
         "frame_hidden_bwd": lambda: ops.frame_hidden_bwd(z1, z1, keep, 1280, T),
+        "sed_clip_targets": lambda: ops.sed_clip_targets(big_weak, idx, start, mix, L, out=w, framed_out=framed),
+        "weak_frame_bce_fwd_bwd": lambda: ops.weak_frame_bce_fwd_bwd(z, y, w, framed, T, sums=step3),
+        "frame_bce_fwd_bwd_K10": lambda: ops.frame_bce_fwd_bwd(z10, y10, T, sums=step),
+        "weak_frame_bce_fwd_bwd_K10": lambda: ops.weak_frame_bce_fwd_bwd(z10, y10, w10, framed, T, sums=step3),
     }
     result["glue_s"] = {}
     for name, fn in glue.items():
