@@ -1,6 +1,6 @@
 """ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h, include/eat_embed.h,
-include/eat_attn.h, include/eat_detect.h, include/eat_sed.h, include/eat_event_score.h, include/eat_psds.h and
-include/eat_weak_sed.h).
+include/eat_attn.h, include/eat_detect.h, include/eat_sed.h, include/eat_event_score.h, include/eat_psds.h,
+include/eat_weak_sed.h and include/eat_median_bank.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -35,6 +35,8 @@ EVENT_SCORE_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_event_s
 PSDS_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_psds.h")
 # weak-label SED training's entry points (efficientat_amd/sed.py: WeakFrameTrainer): likewise
 WEAK_SED_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_weak_sed.h")
+# the width-bank median's entry point (efficientat_amd/sed.py: tune_postprocessing, detection.py): likewise
+MEDIAN_BANK_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_median_bank.h")
 
 
 class EatHipError(RuntimeError):
@@ -95,6 +97,8 @@ with open(PSDS_HEADER_PATH) as _f:
     PSDS_PROTOTYPES = parse_prototypes(_f.read())                      # likewise
 with open(WEAK_SED_HEADER_PATH) as _f:
     WEAK_SED_PROTOTYPES = parse_prototypes(_f.read())                  # likewise
+with open(MEDIAN_BANK_HEADER_PATH) as _f:
+    MEDIAN_BANK_PROTOTYPES = parse_prototypes(_f.read())               # likewise
 
 _lib = None
 
@@ -111,7 +115,8 @@ def lib():
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(TAG_PROTOTYPES.items()) + list(EMBED_PROTOTYPES.items())
                                           + list(ATTN_PROTOTYPES.items()) + list(DETECT_PROTOTYPES.items())
                                           + list(SED_PROTOTYPES.items()) + list(EVENT_SCORE_PROTOTYPES.items())
-                                          + list(PSDS_PROTOTYPES.items()) + list(WEAK_SED_PROTOTYPES.items())):
+                                          + list(PSDS_PROTOTYPES.items()) + list(WEAK_SED_PROTOTYPES.items())
+                                          + list(MEDIAN_BANK_PROTOTYPES.items())):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -9,8 +9,8 @@ Prints one line per event (file, onset and offset in seconds, label, peak and me
 file: {"audio_path": ..., "events": [{"label", "onset", "offset", "peak", "mean"}]}; with --out writes the DCASE
 tab-separated columns `filename onset offset event_label`, sorted by file, onset, offset and label.
 --thresholds_file takes the per-class operating points that `finetune_sed --save_thresholds` / `score_sed` write
-(sed.load_operating_points): its thresholds, post-processing values and labels become this run's defaults; a flag given
-on the command line still wins.
+(sed.load_operating_points): its thresholds, post-processing values (the per-class median widths `class_median_ms` when it
+has them) and labels become this run's defaults; a flag given on the command line still wins, --median_ms for every class.
 """
 import argparse
 import contextlib
@@ -54,10 +54,13 @@ def main(argv=None):
         points = load_operating_points(args.thresholds_file)
     defaults = dict(window_size=10.24, hop_length=5.12, median_ms=960.0, threshold=0.5, min_duration_ms=0.0, max_gap_ms=0.0,
                     taper="triangle")
+    median_given = args.median_ms is not None
     file_low = args.low_threshold is None and args.threshold is None and points is not None
     for name, value in defaults.items():                     # a flag, else the file's value, else the default
         if getattr(args, name) is None:
             setattr(args, name, value if points is None else points[name])
+    if points is not None and not median_given and points.get("class_median_ms") is not None:
+        args.median_ms = points["class_median_ms"]           # the file's per-class widths; an explicit --median_ms wins
     if file_low:                                             # (an explicit --threshold alone means low = high, as without a file)
         args.low_threshold = points["low_threshold"]
 

@@ -9,6 +9,7 @@ buffer, and then launches, once per call for all recordings and classes (include
 
 stitch   prob[k, g] = weighted mean over the windows that hold frame g of sigmoid(logit)      `ops.detect_stitch`
 median   running median along time with reflection at the recording's own ends               `ops.detect_median`
+         (widths that differ between classes: `ops.detect_median_bank`, include/eat_median_bank.h)
 events   double-threshold binarisation, gap merging, minimum length -> sorted event list     `ops.detect_events`
 
 Geometry (host, integers / fp64): R = r hop_size samples per frame (10240), frame_s = R / sample_rate; window W and
@@ -84,6 +85,23 @@ def median_frames(median_ms, frame_s):
     if not 1 <= m <= MAX_MEDIAN:
         raise ValueError(f"median_ms={median_ms} is {m} frames of {1000.0 * frame_s:.6g} ms: the filter takes 1 to {MAX_MEDIAN}")
     return m
+
+
+def median_frames_per_class(median_ms, frame_s, K):
+    """Per-class widths of the median filter in frames -> (K,) int32: `median_frames` of a scalar for every class, or of one
+    value per class.  A value `median_frames` refuses: ValueError naming the class; another shape: ValueError."""
+    ms = np.asarray(median_ms, dtype=np.float64)
+    if ms.ndim == 0:
+        return np.full(int(K), median_frames(float(ms), frame_s), dtype=np.int32)
+    if ms.shape != (int(K),):
+        raise ValueError(f"median_ms must be a scalar or hold one value per class, K = {int(K)} (got shape {ms.shape})")
+    out = np.empty(int(K), dtype=np.int32)
+    for k, v in enumerate(ms.tolist()):
+        try:
+            out[k] = median_frames(v, frame_s)
+        except ValueError as e:
+            raise ValueError(f"class {k}: {e}") from None
+    return out
 
 
 def thresholds(threshold, low_threshold, K):
@@ -298,13 +316,22 @@ class EADetector:
 
     def timelines(self, waves, median=1):
         """-> (prob (K, G_total), filt (K, G_total) or None with median = 1, table, lengths): the stitched probabilities of
-        all recordings side by side, and their running median of `median` frames."""
+        all recordings side by side, and their running median of `median` frames: a scalar, or one odd width in [1, 31] per
+        class.  Widths that are the same in every class run `ops.detect_median` (none at width 1); widths that differ run
+        one `ops.detect_median_bank` of one slice, which copies the classes of width 1."""
+        m = np.asarray(median)
+        if m.ndim > 0:
+            widths = ops.median_width_table(m, self.num_classes)             # (refuses a float, even or out-of-range width)
+            median = int(m.flat[0]) if bool((m == m.flat[0]).all()) else None
         flat, lengths = self._flatten(waves)
         starts, valids, table = self.plan(lengths)
         table.dev(self.device)                                   # (uploaded ahead of the forward)
         P = self.window_logits(flat, starts, valids)
         prob = ops.detect_stitch(P, table, self.geometry.Hf, self.geometry.T, self._wt)
-        filt = ops.detect_median(prob, table, median) if median != 1 else None
+        if median is None:
+            filt = ops.detect_median_bank(prob, table, widths)[0]
+        else:
+            filt = ops.detect_median(prob, table, median) if median != 1 else None
         return prob, filt, table, lengths
 
     def frame_probs(self, waves):
@@ -319,12 +346,14 @@ class EADetector:
     def detect(self, waves, threshold=0.5, low_threshold=None, median_ms=960, min_duration_ms=0, max_gap_ms=0):
         """-> per recording a list of (label or class index, onset_s, offset_s, peak, mean), sorted by class, then onset.
         threshold / low_threshold: scalars or one value per class (low_threshold None: the same as threshold); a run of
-        frames at or above low_threshold is an event if it reaches threshold.  Runs at most max_gap_ms apart are merged,
+        frames at or above low_threshold is an event if it reaches threshold.  median_ms: a scalar or one value per class
+        (`median_frames_per_class`; see `timelines`).  Runs at most max_gap_ms apart are merged,
         then events shorter than min_duration_ms are dropped; ms become frames by rounding to nearest, median_ms then odd
         by rounding up.  onset_s = onset frame_s; offset_s = min(offset R, n) / sample_rate: inside the recording."""
         geo = self.geometry
         hi, lo = thresholds(threshold, low_threshold, self.num_classes)
-        m = median_frames(median_ms, geo.frame_s)
+        m = median_frames(median_ms, geo.frame_s) if np.ndim(median_ms) == 0 else \
+            median_frames_per_class(median_ms, geo.frame_s, self.num_classes)
         min_len, max_gap = ms_to_frames(min_duration_ms, geo.frame_s), ms_to_frames(max_gap_ms, geo.frame_s)
         d_hi, d_lo = torch.from_numpy(hi).to(self.device), torch.from_numpy(lo).to(self.device)
         prob, filt, table, lengths = self.timelines(waves, m)

@@ -9,7 +9,8 @@ frame BCE -> backward -> FusedAdam (sed.GraphedFrameBCETrainer; `--no_graph`: th
 the validation split is scored frame by frame (sed.evaluate_frames: frame mAP / ROC, segment-based F1 at `--threshold`,
 val_loss); with `--event_eval` also event by event (sed.evaluate_events: collar-based F1 at a grid of thresholds, the
 post-processing of `detect` given by `--median_ms --min_duration_ms --max_gap_ms --low_ratio`), and `--save_thresholds FILE`
-writes the per-class operating points of the last validation for `detect --thresholds_file`; with `--psds_eval` also with
+writes the per-class operating points of the last validation for `detect --thresholds_file` (`--tune_median
+[--median_grid_ms a,b,c]` also tunes the median width per class, sed.tune_postprocessing); with `--psds_eval` also with
 PSDS (sed.evaluate_psds: the scenarios of `--psds`, default both, criteria `--dtc --gtc --cttc --alpha_ct --alpha_st --e_max`).
 A training bank may hold weakly labelled clips (strong.npy: clip-level tags only, e.g. DESED's weak.tsv through
 `tools/strong_to_bank.py --weak_tsv`): `--weak_weight W` with W > 0 trains on strong and weak clips in the same batches
@@ -51,19 +52,49 @@ def add_event_args(p):
     p.add_argument("--max_gap_ms", type=float, default=0.0, help="its merge gap")
     p.add_argument("--low_ratio", type=float, default=1.0, help="low threshold as a fraction of the threshold")
     p.add_argument("--save_thresholds", default=None, help="file for the per-class operating points (detect --thresholds_file)")
+    p.add_argument("--tune_median", action="store_true",
+                   help="also tune the median width per class over --median_grid_ms (sed.tune_postprocessing)")
+    p.add_argument("--median_grid_ms", type=_grid_ms, default=None, metavar="a,b,c",
+                   help="median widths to try with --tune_median, in ms (default: the odd widths 1 .. 15 frames)")
+
+
+def _grid_ms(text):
+    """`--median_grid_ms` values: "0,960,2240" -> [float]."""
+    try:
+        out = [float(t) for t in str(text).split(",") if t.strip()]
+    except ValueError:
+        out = []
+    if not out:
+        raise argparse.ArgumentTypeError(f"--median_grid_ms takes a comma-separated list of ms (got {text!r})")
+    return out
+
+
+def tuned_text(ev):
+    """What the programs print about a `sed.tune_postprocessing` result, next to the scores at the reference width."""
+    return (f"median tuned per class (on this split): macro F1 {ev['macro_f1_tuned']:.4f}; best single width "
+            f"{ev['best_single_median_ms']:.0f} ms: {ev['macro_f1_best_single']:.4f}")
 
 
 def event_eval(args, model, mel, bank):
-    """`sed.evaluate_events` with the command line's settings -> (its result, the JSON line's keys)."""
+    """`sed.evaluate_events` - with --tune_median `sed.tune_postprocessing` - with the command line's settings -> (its result,
+    the JSON line's keys)."""
     from . import sed
-    ev = sed.evaluate_events(model, mel, bank, low_ratio=args.low_ratio, median_ms=args.median_ms,
-                             min_duration_ms=args.min_duration_ms, max_gap_ms=args.max_gap_ms, collar_ms=args.collar_ms,
-                             offset_pct=args.offset_pct, threshold=args.threshold, batch_windows=args.batch_windows)
+    kw = dict(low_ratio=args.low_ratio, median_ms=args.median_ms, min_duration_ms=args.min_duration_ms,
+              max_gap_ms=args.max_gap_ms, collar_ms=args.collar_ms, offset_pct=args.offset_pct, threshold=args.threshold,
+              batch_windows=args.batch_windows)
+    if args.tune_median:
+        ev = sed.tune_postprocessing(model, mel, bank, median_grid_ms=args.median_grid_ms, **kw)
+    else:
+        ev = sed.evaluate_events(model, mel, bank, **kw)
     keys = {"event_threshold": ev["threshold"]}
     keys.update({"event_" + k: ev[k] for k in sed.SCORE_NAMES})
     keys.update({"event_macro_f1_best": ev["macro_f1_best"], "event_best_threshold": [float(v) for v in ev["best_threshold"]],
                  "event_collar_ms": args.collar_ms, "event_offset_pct": args.offset_pct, "event_eval_s": round(ev["eval_s"], 3),
                  "thresholds_file": args.save_thresholds})
+    if args.tune_median:
+        keys.update({"macro_f1_tuned": ev["macro_f1_tuned"], "macro_f1_best_single": ev["macro_f1_best_single"],
+                     "best_single_median_ms": ev["best_single_median_ms"],
+                     "best_median_ms": [float(v) for v in ev["best_median_ms"]]})
     return ev, keys
 
 
@@ -99,14 +130,16 @@ def psds_scenarios(args, default=()):
     return [(1, "psds")] if explicit else []
 
 
-def psds_eval(args, model, mel, bank, scenarios):
-    """`sed.evaluate_psds` per scenario with the command line's settings -> the JSON line's keys."""
+def psds_eval(args, model, mel, bank, scenarios, median_ms=None):
+    """`sed.evaluate_psds` per scenario with the command line's settings -> the JSON line's keys.  median_ms: per-class
+    widths to use in place of --median_ms."""
     from . import sed
     keys, seconds = {}, 0.0
     for scenario, key in scenarios:
         ev = sed.evaluate_psds(model, mel, bank, scenario=scenario, dtc=args.dtc, gtc=args.gtc, cttc=args.cttc,
                                alpha_ct=args.alpha_ct, alpha_st=args.alpha_st, e_max=args.e_max, low_ratio=args.low_ratio,
-                               median_ms=args.median_ms, min_duration_ms=args.min_duration_ms, max_gap_ms=args.max_gap_ms,
+                               median_ms=args.median_ms if median_ms is None else median_ms,
+                               min_duration_ms=args.min_duration_ms, max_gap_ms=args.max_gap_ms,
                                batch_windows=args.batch_windows)
         keys[key] = ev["psds"]
         seconds += ev["eval_s"]
@@ -174,6 +207,10 @@ def parse_args(argv=None):
         p.error("--psds and its criteria need --psds_eval")
     if args.save_thresholds and not args.event_eval:
         p.error("--save_thresholds needs --event_eval")
+    if (args.tune_median or args.median_grid_ms) and not args.event_eval:
+        p.error("--tune_median and --median_grid_ms need --event_eval")
+    if args.median_grid_ms and not args.tune_median:
+        p.error("--median_grid_ms needs --tune_median")
     if args.model_name.startswith("dymn"):
         p.error("frame-level training covers the static MobileNets (mn*) only")
     if args.clip_frames < 1:
@@ -256,6 +293,8 @@ def main(argv=None):
             print(f"[finetune_sed] events at {ee['threshold']:.2f}: micro F1 {ee['micro_f1']:.4f}, macro F1 {ee['macro_f1']:.4f}; "
                   f"macro F1 at the per-class best thresholds (tuned on this split) {ee['macro_f1_best']:.4f} "
                   f"({ee['eval_s']:.2f} s)", file=sys.stderr, flush=True)
+            if args.tune_median:
+                print("[finetune_sed] " + tuned_text(ee), file=sys.stderr, flush=True)
         if args.psds_eval:
             ps_keys = psds_eval(args, model, mel, valid, psds_scenarios(args, default=(1, 2)))
             print("[finetune_sed] " + ", ".join(f"{k} {v:.4f}" for k, v in ps_keys.items() if k != "psds_eval_s")

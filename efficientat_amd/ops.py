@@ -2400,6 +2400,66 @@ def detect_median(prob, table, m, out=None):
     return filt.view(K, table.G_total)
 
 
+# ------------------------------------------------------------------ width-bank median (include/eat_median_bank.h)
+class MedianWidthTable:
+    """The validated widths of `detect_median_bank`: cpu (Mw, K) int32, width of slice j and class k, each odd and in
+    [1, 31].  Built by `median_width_table` on the host; `dev(device)` uploads it once per device."""
+
+    def __init__(self, widths):
+        self.cpu, self.Mw, self.K, self._dev = widths, int(widths.shape[0]), int(widths.shape[1]), {}
+
+    def dev(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self.cpu.to(device)
+        return self._dev[key]
+
+
+def median_width_table(widths, K):
+    """Host-side validation of median widths (CPU array or tensor of integers, (K,) = one slice or (Mw >= 1, K)) ->
+    MedianWidthTable.  Every width odd and in [1, 31]; the first that is not is named with its slice, class and value."""
+    fn = "median_width_table"
+    K = int(K)
+    if K < 1:
+        raise _lib.EatHipError(f"{fn}: need K >= 1 (got {K})")
+    try:
+        t = torch.as_tensor(widths)
+    except (ValueError, TypeError) as e:
+        raise _lib.EatHipError(f"{fn}: widths is ragged ({e})") from None
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise _lib.EatHipError(f"{fn}: widths must be integers (got {t.dtype})")
+    if t.dim() == 1:
+        t = t.unsqueeze(0)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != K:
+        raise _lib.EatHipError(f"{fn}: widths must be (K,) or (Mw >= 1, K) with K = {K} (got {tuple(torch.as_tensor(widths).shape)})")
+    t = t.to(device="cpu", dtype=torch.int64)
+    bad = ((t < 1) | (t > _DETECT_MAX_M) | (t % 2 == 0)).nonzero()
+    if bad.numel():
+        j, k = (int(v) for v in bad[0])
+        raise _lib.EatHipError(f"{fn}: slice {j}, class {k}: width {int(t[j, k])} must be an odd integer in [1, {_DETECT_MAX_M}]")
+    return MedianWidthTable(t.to(torch.int32).contiguous())
+
+
+def detect_median_bank(prob, table, widths, out=None):
+    """Running medians of prob (K, G_total) for a bank of widths at once (include/eat_median_bank.h) -> filt (Mw, K, G_total):
+    filt[j, k] is `detect_median` of prob[k] at width widths[j, k], per recording of `table`, bit for bit.  widths: a
+    `MedianWidthTable`, or anything `median_width_table` takes.  prob is read from memory once; out must not overlap prob.
+    One launch, no host wait."""
+    fn = "detect_median_bank"
+    table, K = _timelines(fn, prob, "prob", table)
+    if not isinstance(widths, MedianWidthTable):
+        widths = median_width_table(widths, K)
+    if widths.K != K:
+        raise _lib.EatHipError(f"{fn}: the width table holds {widths.K} classes, prob {K}")
+    filt = _head_out(out, f"{fn}: out", (widths.Mw, K, table.G_total), prob)
+    if _overlaps(filt, prob):
+        raise _lib.EatHipError(f"{fn}: out must not overlap prob (the filter reads its neighbours)")
+    p_x = _on_gpu(prob, f"{fn}: prob")
+    _lib.call("eat_detect_median_bank", p_x, K, table.G_total, table.dev(prob.device).data_ptr(), table.n_rec,
+              widths.dev(prob.device).data_ptr(), widths.Mw, filt.data_ptr(), _stream())
+    return filt.view(widths.Mw, K, table.G_total)
+
+
 def check_thresholds(hi, lo, K):
     """Host-side validation of per-class thresholds (CPU arrays of K values, or scalars): 0 < lo <= hi <= 1 ->
     (hi, lo) contiguous fp32 CPU tensors of K values, compared as the fp32 numbers the kernel sees."""

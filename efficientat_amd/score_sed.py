@@ -3,6 +3,7 @@
     python -m efficientat_amd.score_sed --checkpoint sed.pt --bank DIR [--model mn10_as | --width 1.0]
                                         [--collar_ms 200 --offset_pct 0.2 --median_ms 960 --min_duration_ms 0 --max_gap_ms 0
                                          --low_ratio 1.0 --threshold 0.5] [--save_thresholds ops.json] [--json]
+                                        [--tune_median [--median_grid_ms a,b,c]] [--operating_points ops.json]
                                         [--psds 1,2] [--dtc --gtc --cttc --alpha_ct --alpha_st --e_max]
 
 DIR is a decoded strong-label split (sed.load_bank), the checkpoint a state dict of an mlp-head MN with the bank's classes
@@ -10,6 +11,10 @@ DIR is a decoded strong-label split (sed.load_bank), the checkpoint a state dict
 events with onset / offset collars at the 49 thresholds k / 50 in one kernel launch per chunk of clips.  Prints micro / macro
 F1, precision and recall at `--threshold`, and macro F1 at the per-class best thresholds (tuned on this very split);
 `--save_thresholds` writes those operating points for `detect --thresholds_file`; `--json` prints one JSON line.
+`--tune_median` also tries a grid of median widths in the same walk (sed.tune_postprocessing), prints macro F1 with the width
+and threshold tuned per class next to the best single width, and `--save_thresholds` then writes `class_median_ms` too.
+`--operating_points FILE` scores such a file as it stands on `--bank` (sed.score_operating_points: a file tuned on another
+split is judged on this one) under `*_at_ops` keys, and PSDS then runs at the file's per-class widths.
 `--psds` adds PSDS (sed.evaluate_psds) of the same detector over the same grid for scenario 1 and / or 2 of DCASE Task 4, as
 `psds_scenario1` / `psds_scenario2`; explicit criteria override the scenario's, and without `--psds` they score under `psds`.
 """
@@ -21,7 +26,7 @@ import sys
 
 import torch
 
-from .finetune_sed import add_event_args, add_psds_args, event_eval, psds_eval, psds_scenarios
+from .finetune_sed import add_event_args, add_psds_args, event_eval, psds_eval, psds_scenarios, tuned_text
 from .utils import NAME_TO_WIDTH
 
 
@@ -38,9 +43,14 @@ def parse_args(argv=None):
     p.add_argument("--n_fft", type=int, default=1024)
     p.add_argument("--n_mels", type=int, default=128)
     p.add_argument("--json", action="store_true", help="print one JSON line with the results")
+    p.add_argument("--operating_points", default=None,
+                   help="operating-point file to score as it stands on --bank (sed.score_operating_points)")
     add_event_args(p)
     add_psds_args(p)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.median_grid_ms and not args.tune_median:
+        p.error("--median_grid_ms needs --tune_median")
+    return args
 
 
 def main(argv=None):
@@ -71,16 +81,28 @@ def main(argv=None):
     print(f"[score_sed] {ev['n_clips']} clips, {ev['n_ref']} reference events, {K} classes; at threshold {ev['threshold']:.2f}: "
           f"micro F1 {ev['micro_f1']:.4f}, macro F1 {ev['macro_f1']:.4f}; macro F1 at the per-class best thresholds (tuned on "
           f"this split) {ev['macro_f1_best']:.4f} ({ev['eval_s']:.2f} s)", file=sys.stderr, flush=True)
+    if args.tune_median:
+        print("[score_sed] " + tuned_text(ev), file=sys.stderr, flush=True)
+    ops_keys, points = {}, None
+    if args.operating_points:
+        points = sed.load_operating_points(args.operating_points, classes=bank["classes"])
+        at = sed.score_operating_points(model, mel, bank, points, batch_windows=args.batch_windows)
+        ops_keys = {k + "_at_ops": at[k] for k in sed.SCORE_NAMES}
+        ops_keys.update({"operating_points": args.operating_points, "eval_s_at_ops": round(at["eval_s"], 3)})
+        print(f"[score_sed] at the operating points of {args.operating_points}: micro F1 {at['micro_f1']:.4f}, macro F1 "
+              f"{at['macro_f1']:.4f} ({at['eval_s']:.2f} s)", file=sys.stderr, flush=True)
     scenarios = psds_scenarios(args)
     ps_keys = {}
     if scenarios:
-        ps_keys = psds_eval(args, model, mel, bank, scenarios)
+        file_ms = None if points is None else points.get("class_median_ms")
+        ps_keys = psds_eval(args, model, mel, bank, scenarios, median_ms=file_ms)
         print("[score_sed] " + ", ".join(f"{k} {v:.4f}" for k, v in ps_keys.items() if k != "psds_eval_s")
               + f" ({ps_keys['psds_eval_s']:.2f} s)", file=sys.stderr, flush=True)
     if args.json:
         line = {"what": "efficientat_amd.score_sed", "checkpoint": args.checkpoint, "classes": K, "n_clips": ev["n_clips"],
                 "n_ref": ev["n_ref"]}
         line.update(keys)
+        line.update(ops_keys)
         line.update(ps_keys)
         print(json.dumps(line), flush=True)
     return 0

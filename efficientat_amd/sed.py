@@ -536,13 +536,17 @@ def pick_thresholds(counts, hi, lo, threshold, low_ratio=1.0):
 
 
 def _walk_chunks(fn, model, mel, bank, hi, lo, n_acc, score, finish=None, median_ms=960, min_duration_ms=0, max_gap_ms=0,
-                 batch_clips=256, taper="triangle", clip_seconds=10.24, hop_seconds=5.12, batch_windows=64):
-    """The chunk walk `evaluate_events` and `evaluate_psds` share.  The bank's clips are walked in contiguous chunks of
-    `batch_clips` of the resident flat buffer (no waveform is copied): `detector.plan` on the chunk's lengths,
-    `window_logits` on the slice (through `mel`), `ops.detect_stitch`, `ops.detect_median`, then
-    `score(acc, filt, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first)`, which adds the chunk's counts to acc, a flat
-    int64 device buffer of n_acc zeros; `finish(acc)` runs after the last chunk; then the one host wait.  Model and mel
-    are put in eval mode and restored, the RNG is forked.  -> (acc on the host, seconds, K)."""
+                 batch_clips=256, taper="triangle", clip_seconds=10.24, hop_seconds=5.12, batch_windows=64, unfiltered=False):
+    """The chunk walk `evaluate_events`, `evaluate_psds`, `tune_postprocessing` and `score_operating_points` share.  The
+    bank's clips are walked in contiguous chunks of `batch_clips` of the resident flat buffer (no waveform is copied):
+    `detector.plan` on the chunk's lengths, `window_logits` on the slice (through `mel`), `ops.detect_stitch`, the median,
+    then `score(acc, filt, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first)`, which adds the chunk's counts to acc, a
+    flat int64 device buffer of n_acc zeros; `finish(acc)` runs after the last chunk; then the one host wait.  The median:
+    median_ms is a scalar or one value per class (`detection.median_frames_per_class`); frame widths that are the same in
+    every class run `ops.detect_median` (nothing at width 1), widths that differ one `ops.detect_median_bank` of one slice.
+    unfiltered = True hands `score` the stitched probabilities instead, for a caller that filters them itself (median_ms is
+    still checked).  Model and mel are put in eval mode and restored, the RNG is forked.
+    -> (acc on the host, seconds, K, the (K,) frame widths)."""
     n = bank["lengths"].numel()
     if n == 0:
         raise ValueError(f"{fn}: the split is empty")
@@ -563,7 +567,9 @@ def _walk_chunks(fn, model, mel, bank, hi, lo, n_acc, score, finish=None, median
                                    hop_seconds=hop_seconds, taper=taper)
         det.mel = mel                                                         # the caller's front end, not a default one
         geo = det.geometry
-        m = detection.median_frames(median_ms, geo.frame_s)
+        m_k = detection.median_frames_per_class(median_ms, geo.frame_s, K)
+        m = int(m_k[0])
+        widths = None if bool((m_k == m).all()) else ops.median_width_table(m_k, K)
         min_len, max_gap = detection.ms_to_frames(min_duration_ms, geo.frame_s), detection.ms_to_frames(max_gap_ms, geo.frame_s)
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
@@ -577,7 +583,12 @@ def _walk_chunks(fn, model, mel, bank, hi, lo, n_acc, score, finish=None, median
                 flat = bank["waves"][int(offsets[i0]):int(offsets[i1 - 1] + lengths[i1 - 1])]
                 P = det.window_logits(flat, starts, valids)
                 prob = ops.detect_stitch(P, table, geo.Hf, geo.T, det._wt)
-                filt = ops.detect_median(prob, table, m) if m != 1 else prob
+                if unfiltered:
+                    filt = prob
+                elif widths is not None:
+                    filt = ops.detect_median_bank(prob, table, widths)[0]
+                else:
+                    filt = ops.detect_median(prob, table, m) if m != 1 else prob
                 score(acc, filt, table, d_n[i0:i1], geo.R, d_hi, d_lo, max_gap, min_len, i0)
             if finish is not None:
                 finish(acc)
@@ -585,7 +596,26 @@ def _walk_chunks(fn, model, mel, bank, hi, lo, n_acc, score, finish=None, median
     finally:
         model.train(was_training[0])
         mel.train(was_training[1])
-    return res, time.perf_counter() - t0, K
+    return res, time.perf_counter() - t0, K, m_k
+
+
+def _median_settings(median_ms):
+    """The settings entries of a median given as a scalar ({"median_ms"}) or per class ({"median_ms": the first class's
+    value, "class_median_ms": the K values})."""
+    if np.ndim(median_ms) == 0:
+        return {"median_ms": float(median_ms)}
+    ms = [float(v) for v in np.asarray(median_ms, dtype=np.float64).reshape(-1)]
+    return {"median_ms": ms[0], "class_median_ms": ms}
+
+
+def _event_refs(bank, mel, collar_ms, offset_pct):
+    """The reference events of a strong-label bank for `ops.event_score` -> (EventRefs, collar in samples, n_ref (K,))."""
+    c = collar_samples(collar_ms, mel.sr)
+    K = len(bank["classes"])
+    events_cpu = bank["events"].cpu()
+    refs = ops.event_refs(events_cpu, torch.from_numpy(event_tolerances(events_cpu, c, offset_pct)),
+                          bank["event_offsets"].cpu(), K)
+    return refs, c, np.bincount(events_cpu[:, 0].numpy(), minlength=K).astype(np.int64)
 
 
 def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=960, min_duration_ms=0, max_gap_ms=0,
@@ -607,28 +637,40 @@ def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=
     nearest the argument (itself when it is on the grid), "threshold_index", and the six scores at it under their plain
     names; "best_threshold", "best_low_threshold" (K,) float32 and "best_index" (K,) (`pick_thresholds`); "macro_f1_best":
     macro F1 with those per-class values - TUNED ON THE SCORED SPLIT, an upper bound for any other; "n_clips", "n_ref",
-    "eval_s", "settings"}.  Mode restore and forked RNG as `evaluate_frames`."""
+    "eval_s", "settings"}.  median_ms is a scalar or one value per class; given per class, settings gains "class_median_ms"
+    (the K values) and settings["median_ms"] holds the first class's value.  Mode restore and forked RNG as
+    `evaluate_frames`."""
     _refuse_weak("evaluate_events", bank)
     n = bank["lengths"].numel()
     if n == 0:
         raise ValueError("evaluate_events: the split is empty")
     hi, lo = threshold_grid(thresholds, low_ratio)
-    c = collar_samples(collar_ms, mel.sr)
     K = len(bank["classes"])
-    events_cpu = bank["events"].cpu()
-    refs = ops.event_refs(events_cpu, torch.from_numpy(event_tolerances(events_cpu, c, offset_pct)),
-                          bank["event_offsets"].cpu(), K)
-    n_ref = np.bincount(events_cpu[:, 0].numpy(), minlength=K).astype(np.int64)
+    refs, c, n_ref = _event_refs(bank, mel, collar_ms, offset_pct)
 
     def score(acc, filt, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first):
         cnt = ops.event_score(filt, table, nsamp, R, refs, c, d_hi, d_lo, max_gap, min_len, first=first)
         acc += cnt.sum(dim=0, dtype=torch.int64).flatten()
 
-    res, eval_s, K = _walk_chunks("evaluate_events", model, mel, bank, hi, lo, K * hi.size * 2, score, None, median_ms,
-                                  min_duration_ms, max_gap_ms, batch_clips, taper, clip_seconds, hop_seconds, batch_windows)
-    res = res.reshape(K, hi.size, 2)
+    res, eval_s, K, _ = _walk_chunks("evaluate_events", model, mel, bank, hi, lo, K * hi.size * 2, score, None, median_ms,
+                                     min_duration_ms, max_gap_ms, batch_clips, taper, clip_seconds, hop_seconds, batch_windows)
+    settings = _median_settings(median_ms)
+    settings.update({"min_duration_ms": float(min_duration_ms), "max_gap_ms": float(max_gap_ms), "taper": taper,
+                     "window_size": float(clip_seconds), "hop_length": float(hop_seconds), "collar_ms": float(collar_ms),
+                     "offset_pct": float(offset_pct), "low_ratio": float(low_ratio)})
+    return _event_result(_event_counts(res.reshape(K, hi.size, 2), n_ref), hi, lo, threshold, low_ratio, n, n_ref, eval_s,
+                         settings)
+
+
+def _event_counts(res, n_ref):
+    """(K, V, 2) sums of `ops.event_score`'s (tp, n_est) over a split -> counts (V, K, 3) int64 (tp, fp, fn)."""
     tp, n_est = res[:, :, 0].T, res[:, :, 1].T                                # (V, K)
-    counts = np.stack([tp, n_est - tp, n_ref[None, :] - tp], axis=2).astype(np.int64)
+    return np.stack([tp, n_est - tp, n_ref[None, :] - tp], axis=2).astype(np.int64)
+
+
+def _event_result(counts, hi, lo, threshold, low_ratio, n, n_ref, eval_s, settings):
+    """The result dict of `evaluate_events` from the counts (V, K, 3) of one median setting."""
+    K = counts.shape[1]
     rows = [segment_scores(counts[v]) for v in range(hi.size)]
     at, best, b_hi, b_lo = pick_thresholds(counts, hi, lo, threshold, low_ratio)
     at_best = np.where(best >= 0, best, at)
@@ -638,11 +680,157 @@ def evaluate_events(model, mel, bank, thresholds=None, low_ratio=1.0, median_ms=
     out.update(rows[at])
     out.update({"best_threshold": b_hi, "best_low_threshold": b_lo, "best_index": best,
                 "macro_f1_best": segment_scores(counts[at_best, np.arange(K)])["macro_f1"], "n_clips": n,
-                "n_ref": int(n_ref.sum()), "eval_s": eval_s,
-                "settings": {"median_ms": float(median_ms), "min_duration_ms": float(min_duration_ms),
-                             "max_gap_ms": float(max_gap_ms), "taper": taper, "window_size": float(clip_seconds),
-                             "hop_length": float(hop_seconds), "collar_ms": float(collar_ms), "offset_pct": float(offset_pct),
-                             "low_ratio": float(low_ratio)}})
+                "n_ref": int(n_ref.sum()), "eval_s": eval_s, "settings": settings})
+    return out
+
+
+# ---- the median width per class: one trunk pass per chunk, all candidate widths from one `ops.detect_median_bank`
+def pick_operating_points(counts_grid, hi, lo, threshold, ref_index, low_ratio=1.0):
+    """counts_grid (Mw, V, K, 3) (tp, fp, fn) per median width (ascending), threshold pair and class; the grid (hi, lo) ->
+    (index of the grid value nearest `threshold`, best width index (K,), best threshold index (K,) or -1, best_threshold
+    (K,), best_low_threshold (K,) float32).  Per class the FIRST maximum of F1 over the (Mw, V) grid in width-major order:
+    the narrowest width, then the lowest threshold; a point without anything to score ranks below every F1.  A class with
+    nothing to score anywhere keeps width `ref_index` and `threshold` (threshold index -1): the rule of `pick_thresholds`."""
+    counts_grid = np.asarray(counts_grid)
+    if counts_grid.ndim != 4 or counts_grid.shape[3] != 3 or counts_grid.shape[1] != hi.size:
+        raise ValueError(f"pick_operating_points: counts_grid must be (Mw, V = {hi.size}, K, 3) (got {counts_grid.shape})")
+    Mw, V, K, _ = counts_grid.shape
+    if not 0 <= int(ref_index) < Mw:
+        raise ValueError(f"pick_operating_points: ref_index={ref_index} lies outside the {Mw} widths")
+    f = class_f1(counts_grid)                                                 # (Mw, V, K)
+    at = int(np.argmin(np.abs(hi.astype(np.float64) - float(np.float32(threshold)))))
+    first = np.argmax(np.where(np.isnan(f), -1.0, f).reshape(Mw * V, K), axis=0)
+    none = np.isnan(f).all(axis=(0, 1))
+    best_j = np.where(none, int(ref_index), first // V)
+    best_v = np.where(none, -1, first % V)
+    keep_hi = np.float32(threshold)
+    keep_lo = np.minimum(np.maximum(np.float32(low_ratio) * keep_hi, _TINY), keep_hi).astype(np.float32)
+    b_hi = np.where(best_v >= 0, hi[np.maximum(best_v, 0)], keep_hi).astype(np.float32)
+    b_lo = np.where(best_v >= 0, lo[np.maximum(best_v, 0)], keep_lo).astype(np.float32)
+    return at, best_j, best_v, b_hi, b_lo
+
+
+def _sweep_timelines(prob, table, nsamp, R, refs, c, width_table, hi, lo, max_gap, min_len, first=0):
+    """Event counts of stitched probabilities prob (K, G_total) at every median width of `width_table` (Mw, K) and every
+    threshold pair -> (Mw, K, V, 2) int64 on the device, (tp, n_est) summed over the recordings of `table`: ONE
+    `ops.detect_median_bank`, then one `ops.event_score` per slice on the contiguous filt[j].  The other operands are
+    `ops.event_score`'s.  No host wait."""
+    filt = ops.detect_median_bank(prob, table, width_table)
+    return torch.stack([ops.event_score(filt[j], table, nsamp, R, refs, c, hi, lo, max_gap, min_len, first=first)
+                        .sum(dim=0, dtype=torch.int64) for j in range(filt.shape[0])])
+
+
+def tune_postprocessing(model, mel, bank, median_grid_ms=None, median_ms=960, thresholds=None, low_ratio=1.0,
+                        min_duration_ms=0, max_gap_ms=0, collar_ms=200, offset_pct=0.2, threshold=0.5, batch_clips=256,
+                        taper="triangle", clip_seconds=10.24, hop_seconds=5.12, batch_windows=64):
+    """`evaluate_events` at a whole grid of median widths in one walk of the split, and the width and threshold that suit
+    each class.  The widths in frames are `detection.median_frames` of every entry of median_grid_ms (default: the odd
+    widths 1 .. 15 frames) plus that of median_ms (a scalar: the reference width), without repeats, ascending.  Per chunk
+    of clips ONE trunk pass and stitch (`_walk_chunks`), then `_sweep_timelines`: one `ops.detect_median_bank` whose slice
+    j holds width j in every class and one `ops.event_score` per slice; int64 counts accumulate on the device with one host
+    wait at the end.  The remaining arguments are `evaluate_events`'s.
+
+    -> every key of `evaluate_events(median_ms=median_ms)` (counts, grid, scores, "macro_f1_best", settings: all at the
+    reference width), and: "median_frames" (Mw,) int32, "median_ms_grid" (Mw,) float64 (frames times the frame length);
+    "counts_grid" (Mw, V, K, 3) int64, "class_f1_grid" (Mw, V, K); "best_median_index", "best_median_frames",
+    "best_median_ms" (K,) (`pick_operating_points`); "best_threshold", "best_low_threshold", "best_index" are taken AT THE
+    CHOSEN WIDTH; "macro_f1_tuned": macro F1 with each class at its width and threshold; "macro_f1_best_single" with
+    "best_single_median_ms": the best macro F1 one shared width reaches with per-class thresholds (`pick_thresholds` per
+    width, the narrowest of equals).  Both figures are TUNED ON THE SCORED SPLIT, an upper bound for any other, as
+    "macro_f1_best" is; `score_operating_points` judges a saved choice on another split.  settings gains "frame_ms"."""
+    _refuse_weak("tune_postprocessing", bank)
+    n = bank["lengths"].numel()
+    if n == 0:
+        raise ValueError("tune_postprocessing: the split is empty")
+    if np.ndim(median_ms) != 0:
+        raise ValueError("tune_postprocessing: median_ms is the scalar reference width; the grid goes in median_grid_ms")
+    hi, lo = threshold_grid(thresholds, low_ratio)
+    V, K = hi.size, len(bank["classes"])
+    refs, c, n_ref = _event_refs(bank, mel, collar_ms, offset_pct)
+    frame_s = detection.frame_geometry(detection.check_model(model)[1], mel.hopsize, mel.sr, clip_seconds, hop_seconds).frame_s
+    m_ref = detection.median_frames(median_ms, frame_s)
+    if median_grid_ms is None:
+        grid = list(range(1, 16, 2))
+    else:
+        grid = [detection.median_frames(v, frame_s) for v in np.asarray(median_grid_ms, dtype=np.float64).reshape(-1)]
+    frames = np.asarray(sorted(set(grid + [m_ref])), dtype=np.int32)
+    Mw, ref_index = frames.size, int(np.flatnonzero(frames == m_ref)[0])
+    width_table = ops.median_width_table(np.repeat(frames[:, None], K, axis=1), K)
+
+    def score(acc, prob, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first):
+        acc += _sweep_timelines(prob, table, nsamp, R, refs, c, width_table, d_hi, d_lo, max_gap, min_len, first).flatten()
+
+    res, eval_s, K, _ = _walk_chunks("tune_postprocessing", model, mel, bank, hi, lo, Mw * K * V * 2, score, None, median_ms,
+                                     min_duration_ms, max_gap_ms, batch_clips, taper, clip_seconds, hop_seconds, batch_windows,
+                                     unfiltered=True)
+    res = res.reshape(Mw, K, V, 2)
+    counts_grid = np.stack([_event_counts(res[j], n_ref) for j in range(Mw)])                  # (Mw, V, K, 3)
+    settings = {"median_ms": float(median_ms), "min_duration_ms": float(min_duration_ms), "max_gap_ms": float(max_gap_ms),
+                "taper": taper, "window_size": float(clip_seconds), "hop_length": float(hop_seconds),
+                "collar_ms": float(collar_ms), "offset_pct": float(offset_pct), "low_ratio": float(low_ratio),
+                "frame_ms": 1000.0 * frame_s}
+    out = _event_result(counts_grid[ref_index], hi, lo, threshold, low_ratio, n, n_ref, eval_s, settings)
+    ms_grid = frames.astype(np.float64) * (1000.0 * frame_s)
+    tuned = tuned_scores(counts_grid, hi, lo, threshold, ref_index, low_ratio)
+    best_j, j_single = tuned["best_median_index"], tuned.pop("best_single_index")
+    out.update(tuned)
+    out.update({"median_frames": frames, "median_ms_grid": ms_grid, "counts_grid": counts_grid,
+                "class_f1_grid": class_f1(counts_grid), "best_median_frames": frames[best_j], "best_median_ms": ms_grid[best_j],
+                "best_single_median_ms": float(ms_grid[j_single])})
+    return out
+
+
+def tuned_scores(counts_grid, hi, lo, threshold, ref_index, low_ratio=1.0):
+    """The choices and figures `tune_postprocessing` derives from counts_grid (Mw, V, K, 3), pure numpy -> {"best_median_index",
+    "best_index" (K,), "best_threshold", "best_low_threshold" (K,) float32 (`pick_operating_points`); "macro_f1_tuned":
+    macro F1 of the classes' counts at their chosen points (a class that keeps the reference: at the reference width and the
+    grid value nearest `threshold`); "macro_f1_best_single", "best_single_index": the largest macro F1 one width reaches
+    with per-class thresholds (`pick_thresholds` per width), and the narrowest width that reaches it}."""
+    at, best_j, best_v, b_hi, b_lo = pick_operating_points(counts_grid, hi, lo, threshold, ref_index, low_ratio)
+    counts_grid = np.asarray(counts_grid)
+    cls = np.arange(counts_grid.shape[2])
+    single = []
+    for j in range(counts_grid.shape[0]):
+        _, best, _, _ = pick_thresholds(counts_grid[j], hi, lo, threshold, low_ratio)
+        single.append(segment_scores(counts_grid[j][np.where(best >= 0, best, at), cls])["macro_f1"])
+    single = np.asarray(single, dtype=np.float64)
+    j_single = int(np.argmax(np.where(np.isnan(single), -1.0, single)))
+    return {"best_median_index": best_j, "best_index": best_v, "best_threshold": b_hi, "best_low_threshold": b_lo,
+            "macro_f1_tuned": segment_scores(counts_grid[best_j, np.where(best_v >= 0, best_v, at), cls])["macro_f1"],
+            "macro_f1_best_single": float(single[j_single]), "best_single_index": j_single}
+
+
+def score_operating_points(model, mel, bank, doc, batch_clips=256, batch_windows=64):
+    """Score a loaded operating-point file (`load_operating_points`) on a resident strong-label split: the event-based
+    scores of `detect --thresholds_file` with that file, so that a choice tuned on one split can be judged on another.
+    The detector's post-processing, collars and per-class thresholds are the file's; its "class_median_ms" (else its
+    "median_ms") gives the widths, filtered as in `_walk_chunks` (unequal widths: one `ops.detect_median_bank` of one
+    slice).  The K pairs (threshold[k], low_threshold[k]) are the grid of ONE `ops.event_score` per chunk; class k's counts
+    are read at pair k.
+    -> {"counts" (K, 3) int64 (tp, fp, fn), the six `segment_scores`, "n_clips", "n_ref", "eval_s"}.  On the split the
+    file was tuned on, "macro_f1" is `tune_postprocessing`'s "macro_f1_tuned" exactly."""
+    _refuse_weak("score_operating_points", bank)
+    n = bank["lengths"].numel()
+    if n == 0:
+        raise ValueError("score_operating_points: the split is empty")
+    K = len(bank["classes"])
+    if list(doc["classes"]) != list(bank["classes"]):
+        raise ValueError("score_operating_points: the operating points and the bank differ in their classes")
+    scoring = doc.get("scoring") or {}
+    refs, c, n_ref = _event_refs(bank, mel, scoring.get("collar_ms", 200.0), scoring.get("offset_pct", 0.2))
+    median = doc["class_median_ms"] if doc.get("class_median_ms") is not None else doc["median_ms"]
+
+    def score(acc, filt, table, nsamp, R, d_hi, d_lo, max_gap, min_len, first):
+        cnt = ops.event_score(filt, table, nsamp, R, refs, c, d_hi, d_lo, max_gap, min_len, first=first)       # V = K pairs
+        acc += cnt.sum(dim=0, dtype=torch.int64).diagonal(dim1=0, dim2=1).t().flatten()                       # [k, pair k]
+
+    res, eval_s, K, _ = _walk_chunks("score_operating_points", model, mel, bank, doc["threshold"], doc["low_threshold"], K * 2,
+                                     score, None, median, doc["min_duration_ms"], doc["max_gap_ms"], batch_clips, doc["taper"],
+                                     doc["window_size"], doc["hop_length"], batch_windows)
+    counts = _event_counts(res.reshape(K, 1, 2), n_ref)[0]
+    out = {"counts": counts}
+    out.update(segment_scores(counts))
+    out.update({"n_clips": n, "n_ref": int(n_ref.sum()), "eval_s": eval_s})
     return out
 
 
@@ -721,7 +909,8 @@ def evaluate_psds(model, mel, bank, scenario=1, dtc=None, gtc=None, cttc=None, a
 
     -> {"thresholds", "low_thresholds" (V,) float32; "counts" (V, K, 3) int64 (tp, fp, fn); "n_det" (V, K); "ct" (V, K, K)
     int64; "psds", "efpr", "tpr", "etpr_x", "etpr_y" of `psds_from_counts`; "n_ref", "ref_seconds" (K,); "total_seconds";
-    "n_clips", "eval_s", "settings"}."""
+    "n_clips", "eval_s", "settings"}.  median_ms is a scalar or one value per class, with the settings entries of
+    `evaluate_events`."""
     if scenario not in PSDS_SCENARIOS:
         raise ValueError(f"evaluate_psds: scenario must be one of {sorted(PSDS_SCENARIOS)} (got {scenario!r})")
     st = dict(PSDS_SCENARIOS[scenario])
@@ -754,8 +943,8 @@ def evaluate_psds(model, mel, bank, scenario=1, dtc=None, gtc=None, cttc=None, a
         if cross[0] is not None:
             acc[K * V * 4:] = cross[0].flatten()
 
-    res, eval_s, K = _walk_chunks("evaluate_psds", model, mel, bank, hi, lo, K * V * 4 + V * K * K, score, finish, median_ms,
-                                  min_duration_ms, max_gap_ms, batch_clips, taper, clip_seconds, hop_seconds, batch_windows)
+    res, eval_s, K, _ = _walk_chunks("evaluate_psds", model, mel, bank, hi, lo, K * V * 4 + V * K * K, score, finish, median_ms,
+                                     min_duration_ms, max_gap_ms, batch_clips, taper, clip_seconds, hop_seconds, batch_windows)
     per = res[:K * V * 4].reshape(K, V, 4).transpose(1, 0, 2)                 # (V, K, 4): tp, n_det, fp, n_ct
     ct = res[K * V * 4:].reshape(V, K, K).astype(np.int64)
     tp, fp = per[:, :, 0], per[:, :, 2]
@@ -763,9 +952,10 @@ def evaluate_psds(model, mel, bank, scenario=1, dtc=None, gtc=None, cttc=None, a
            "counts": np.stack([tp, fp, n_ref[None, :] - tp], axis=2).astype(np.int64), "n_det": per[:, :, 1].astype(np.int64),
            "ct": ct}
     out.update(psds_from_counts(tp, fp, ct, n_ref, ref_seconds, total_seconds, st["alpha_ct"], st["alpha_st"], st["e_max"]))
-    settings = {"scenario": scenario, "median_ms": float(median_ms), "min_duration_ms": float(min_duration_ms),
-                "max_gap_ms": float(max_gap_ms), "taper": taper, "window_size": float(clip_seconds),
-                "hop_length": float(hop_seconds), "low_ratio": float(low_ratio)}
+    settings = {"scenario": scenario}
+    settings.update(_median_settings(median_ms))
+    settings.update({"min_duration_ms": float(min_duration_ms), "max_gap_ms": float(max_gap_ms), "taper": taper,
+                     "window_size": float(clip_seconds), "hop_length": float(hop_seconds), "low_ratio": float(low_ratio)})
     settings.update(st)
     out.update({"n_ref": n_ref, "ref_seconds": ref_seconds, "total_seconds": total_seconds, "n_clips": n, "eval_s": eval_s,
                 "settings": settings})
@@ -779,7 +969,9 @@ _OP_POST = ("median_ms", "min_duration_ms", "max_gap_ms", "taper", "window_size"
 def save_operating_points(path, result, classes):
     """Write the per-class operating points of an `evaluate_events` result as JSON: classes, threshold (K), low_threshold (K),
     median_ms, min_duration_ms, max_gap_ms, taper, window_size, hop_length (seconds, `detect`'s flags), and under "scoring" /
-    "scores" the settings and the scores they came from."""
+    "scores" the settings and the scores they came from.  A `tune_postprocessing` result (one with "best_median_ms") also
+    writes class_median_ms (K floats: the chosen width per class, which `detect` prefers to median_ms), frame_ms and the
+    tuned scores."""
     classes = list(classes)
     hi, lo = np.asarray(result["best_threshold"], dtype=np.float32), np.asarray(result["best_low_threshold"], dtype=np.float32)
     if hi.shape != (len(classes),) or lo.shape != hi.shape:
@@ -792,6 +984,13 @@ def save_operating_points(path, result, classes):
                       "grid": [float(v) for v in result["thresholds"]]}
     doc["scores"] = {"macro_f1_best": result["macro_f1_best"]}
     doc["scores"].update({k: result[k] for k in SCORE_NAMES})
+    if "best_median_ms" in result:
+        ms = np.asarray(result["best_median_ms"], dtype=np.float64)
+        if ms.shape != (len(classes),):
+            raise ValueError(f"save_operating_points: {len(classes)} classes, best_median_ms of shape {ms.shape}")
+        doc["class_median_ms"] = [float(v) for v in ms]
+        doc["frame_ms"] = st["frame_ms"]
+        doc["scores"].update({k: result[k] for k in ("macro_f1_tuned", "macro_f1_best_single", "best_single_median_ms")})
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
@@ -803,7 +1002,8 @@ def load_operating_points(path, classes=None, n_classes=None):
     """Read an operating-point file -> its dict with threshold / low_threshold as (K,) float32 arrays.  classes: the class
     names, in order, that the file must hold; n_classes: the class count it must hold.  A missing field, a wrong length,
     another class order, thresholds outside 0 < low_threshold <= threshold <= 1 or an unknown taper: ValueError naming the
-    file."""
+    file.  class_median_ms is optional: a file without it loads as ever; with it, it comes back as a (K,) float64 array and
+    must hold K finite values that are each a legal median width in frames of the file's frame_ms (320 when absent)."""
     what = f"operating points at {path}"
     try:
         with open(path) as f:
@@ -840,4 +1040,19 @@ def load_operating_points(path, classes=None, n_classes=None):
     out = dict(doc)
     out.update(post)
     out.update(threshold=hi, low_threshold=lo)
+    if "class_median_ms" in doc:                             # optional: the per-class widths of `tune_postprocessing`
+        try:
+            ms = np.asarray(doc["class_median_ms"], dtype=np.float64)
+            frame_ms = float(doc.get("frame_ms", 320.0))
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: class_median_ms and frame_ms must be numbers") from None
+        if ms.shape != (K,):
+            raise ValueError(f"{what}: class_median_ms must hold K = {K} values (got shape {ms.shape})")
+        if not np.isfinite(frame_ms) or frame_ms <= 0:
+            raise ValueError(f"{what}: frame_ms must be finite and positive")
+        try:
+            detection.median_frames_per_class(ms, frame_ms / 1000.0, K)
+        except ValueError as e:
+            raise ValueError(f"{what}: class_median_ms: {e}") from None
+        out.update(class_median_ms=ms, frame_ms=frame_ms)
     return out
