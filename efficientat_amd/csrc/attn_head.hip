@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "eat_common.h"
+#include "loss_terms.h"
 #include "../../include/eat_attn.h"
 
 namespace {
@@ -27,8 +28,6 @@ __device__ __forceinline__ float group_sum(float v, int L) {      // L: power of
   for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-
-__device__ __forceinline__ float sigmoidf(float q) { return 1.0f / (1.0f + expf(-q)); }
 
 int group_lanes(int Tp) {
   int L = 1;
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void attn_pool_fwd_kernel(const float* __
     float s = 0.0f, m = 0.0f;
     for (int t = j; t < T; t += L) {
       if (live) {
-        const float a = fminf(fmaxf(sigmoidf(ra[t] + ba), lo), hi);
+        const float a = fminf(fmaxf(eat::sigmoid(ra[t] + ba), lo), hi);
         s += a;
         m += a * (rv[t] + bv);
       }
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void attn_pool_bwd_kernel(const float* __
     for (int t = j; t < Tp; t += L) {
       float dqa = 0.0f, dqv = 0.0f;
       if (t < T) {
-        const float sg = sigmoidf(ra[t] + ba);
+        const float sg = eat::sigmoid(ra[t] + ba);
         const float a = fminf(fmaxf(sg, lo), hi);
         dqv = d_o * a * inv_s;
         const float da = d_o * ((rv[t] + bv) - o) * inv_s;

@@ -10,6 +10,8 @@
 // that the block's columns touch, and ranks by counting.  events gives one wavefront (= one block) a whole timeline and
 // walks it 64 frames per step on ballot masks; everything it carries from step to step is wave-uniform.
 #include "eat_common.h"
+#include "loss_terms.h"
+#include "timeline.h"
 #include "../../include/eat_detect.h"
 
 namespace {
@@ -18,25 +20,7 @@ constexpr int kTile = 256;            // columns per block of stitch / median
 constexpr int kMaxM = 31;             // widest median
 constexpr int kGridY = 65535;
 
-// the sigmoid of tag.hip: ONE expression for a probability across the library
-__device__ __forceinline__ float sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-struct Rec { int first, count, goff, G; };
-
-__device__ __forceinline__ Rec load_rec(const int* __restrict__ rec, int r) {
-  const int4 v = *reinterpret_cast<const int4*>(rec + 4 * (long long)r);
-  return Rec{v.x, v.y, v.z, v.w};
-}
-
-// the last recording whose goff is <= c (goff ascending, goff[0] = 0)
-__device__ __forceinline__ int find_rec(const int* __restrict__ rec, int n_rec, int c) {
-  int lo = 0, hi = n_rec - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rec[4 * (long long)mid + 2] <= c) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+using eat::find_rec, eat::load_rec, eat::Rec, eat::reflect;
 
 __global__ __launch_bounds__(kTile) void detect_stitch_kernel(const float* __restrict__ p, int n_w, int K, int Tp,
                                                               const int* __restrict__ rec, int n_rec, int Hf, int T,
@@ -57,19 +41,11 @@ __global__ __launch_bounds__(kTile) void detect_stitch_kernel(const float* __res
     for (int q = q_lo; q <= q_hi; ++q) {
       const int j = g - q * Hf;
       const float w = wt[j];
-      num += w * sigmoid(p[((long long)(r.first + q) * K + k) * Tp + j]);
+      num += w * eat::sigmoid(p[((long long)(r.first + q) * K + k) * Tp + j]);
       den += w;
     }
     prob[(long long)k * G_total + c] = q_hi >= q_lo ? num / den : 0.0f;
   }
-}
-
-// periodic reflection of index j about the ends of [0, G)
-__device__ __forceinline__ int reflect(long long j, int G) {
-  const long long P = 2LL * G;
-  long long u = j % P;
-  if (u < 0) u += P;
-  return (int)(u < G ? u : P - 1 - u);
 }
 
 __global__ __launch_bounds__(kTile) void detect_median_kernel(const float* __restrict__ x, int K, int G_total,

@@ -9,6 +9,7 @@
 // never sees an active frame and never emits.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "event_bank.h"
 
 namespace eat {
 
@@ -66,17 +67,6 @@ __device__ __forceinline__ void event_walk(const float* __restrict__ x, int G, f
   }
   if (open) close_run(G);
   if (cur) final_event(cur_on, cur_off);
-}
-
-// The reference rows of class `cls` among the rows [a, b) of one recording, sorted by (class, onset): the first row whose
-// class is not below cls, by bisection over ref (n, 3) rows (class, onset, offset).  Wave-uniform.
-__device__ __forceinline__ long long first_row_of_class(const int* __restrict__ ref, long long a, long long b, int cls) {
-  long long l = a, h = b;
-  while (l < h) {
-    const long long m = (l + h) >> 1;
-    if (ref[3 * m] < cls) l = m + 1; else h = m;
-  }
-  return l;
 }
 
 }  // namespace eat

@@ -9,17 +9,15 @@
 //                           folded in, its gradient, the per-row loss and sigmoid(z) in one pass (ex_openmic.py:102-121, :160-187)
 //   eat_openmic_targets     the label rule of OpenMIC's MixupDataset (datasets/openmic.py:74-95) for the rows of a wave-mixed batch
 #include "eat_common.h"
+#include "loss_terms.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int kCeRowsPerBlock = 4;     // one wave per row
 constexpr int kCeReg = 4;              // C <= 64 * kCeReg: the row stays in registers between the passes
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using eat::wave_sum_d;
 
 // numpy argmax order: a NaN beats every number (first NaN wins), otherwise the larger value, ties to the lower index.  A total
 // order, so the xor butterfly leaves the same (value, index) in every lane.
@@ -48,13 +46,9 @@ template <int KR>
 __device__ CeRow ce_row(const float* __restrict__ z, const float* __restrict__ y, const int* __restrict__ perm,
                         const float* __restrict__ lam, int B, int C, int b, float* __restrict__ dz) {
   const int lane = threadIdx.x & 63;
-  int pb = -1;
-  double l = 1.0;
-  if (perm != nullptr) {
-    pb = perm[b];
-    l = (double)lam[b];
-    if (pb < 0 || pb >= B) pb = b, l = __builtin_nan("");   // (a bad permutation poisons its row instead of reading outside y)
-  }
+  const eat::MixRow m = eat::mix_row(perm, lam, b, B);
+  const int pb = m.mixed ? m.pb : -1;              // (-1: no mix-up)
+  const double l = m.lam;
   const float* zr = z + (size_t)b * C;
   float zv[KR > 0 ? KR : 1];
   double tv[KR > 0 ? KR : 1];
@@ -236,28 +230,21 @@ __device__ double bce_row(const float* __restrict__ z, const float* __restrict__
                           const float* __restrict__ lam, int B, int C, int binarize, int b, float* __restrict__ dz,
                           float* __restrict__ probs, long long probs_stride) {
   const int lane = threadIdx.x & 63;
-  int pb = -1;
-  double l = 1.0;
-  if (perm != nullptr) {
-    pb = perm[b];
-    l = (double)lam[b];
-    if (pb < 0 || pb >= B) pb = b, l = __builtin_nan("");   // (as ce_row: a bad permutation poisons its row, nothing outside yy is read)
-  }
+  const eat::MixRow mr = eat::mix_row(perm, lam, b, B);
   const float* zr = z + (size_t)b * C;
   const float* ya = yy + (size_t)b * 2 * C;
-  const float* yp = yy + (size_t)(pb < 0 ? b : pb) * 2 * C;
+  const float* yp = yy + (size_t)mr.pb * 2 * C;
   const double inv_bc = 1.0 / ((double)B * (double)C);
   double acc = 0.0;
   for (int c = lane; c < C; c += 64) {
     const double v = (double)zr[c];
     const double m = (double)ya[C + c];                     // the mask of row b only: the log-mel mix-up does not mix masks
     double t = binarize ? (ya[c] > 0.5f ? 1.0 : 0.0) : (double)ya[c];
-    if (pb >= 0) t = l * t + (1.0 - l) * (binarize ? (yp[c] > 0.5f ? 1.0 : 0.0) : (double)yp[c]);
-    const double e = exp(-fabs(v));
-    const double sg = v >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);          // NaN logit: NaN
-    acc += m * ((v > 0.0 ? v : 0.0) - v * t + log1p(e));                   // 0 * NaN = NaN: a NaN logit shows under mask 0 too
-    if (dz != nullptr) dz[(size_t)b * C + c] = (float)(m * (sg - t) * inv_bc);
-    if (probs != nullptr) probs[(long long)b * probs_stride + c] = (float)sg;
+    if (mr.mixed) t = mr.lam * t + (1.0 - mr.lam) * (binarize ? (yp[c] > 0.5f ? 1.0 : 0.0) : (double)yp[c]);
+    const eat::BceTerm r = eat::bce_term(v);                               // NaN logit: NaN
+    acc += m * r.loss(v, t);                                               // 0 * NaN = NaN: a NaN logit shows under mask 0 too
+    if (dz != nullptr) dz[(size_t)b * C + c] = (float)(m * (r.p - t) * inv_bc);
+    if (probs != nullptr) probs[(long long)b * probs_stride + c] = (float)r.p;
   }
   return wave_sum_d(acc) / (double)C;
 }

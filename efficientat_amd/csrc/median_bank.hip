@@ -6,8 +6,8 @@
 // recording that the block's columns touch.  The piece and the reflected halo of the WIDEST width the class has in the bank
 // are staged in LDS once; every slice then ranks by counting inside that one staging, its own window centred in it.  The
 // width of a (slice, class) is the same in every thread of the block, so every trip count and barrier is block-uniform.
-// Rec / find_rec / reflect restate detect.hip's (file-local there): a change of either definition belongs in both files.
 #include "eat_common.h"
+#include "timeline.h"
 #include "../../include/eat_median_bank.h"
 
 namespace {
@@ -16,30 +16,7 @@ constexpr int kTile = 256;            // columns per block
 constexpr int kMaxM = 31;             // widest median
 constexpr int kGridY = 65535;
 
-struct Rec { int first, count, goff, G; };
-
-__device__ __forceinline__ Rec load_rec(const int* __restrict__ rec, int r) {
-  const int4 v = *reinterpret_cast<const int4*>(rec + 4 * (long long)r);
-  return Rec{v.x, v.y, v.z, v.w};
-}
-
-// the last recording whose goff is <= c (goff ascending, goff[0] = 0)
-__device__ __forceinline__ int find_rec(const int* __restrict__ rec, int n_rec, int c) {
-  int lo = 0, hi = n_rec - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rec[4 * (long long)mid + 2] <= c) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// periodic reflection of index j about the ends of [0, G)
-__device__ __forceinline__ int reflect(long long j, int G) {
-  const long long P = 2LL * G;
-  long long u = j % P;
-  if (u < 0) u += P;
-  return (int)(u < G ? u : P - 1 - u);
-}
+using eat::find_rec, eat::load_rec, eat::Rec, eat::reflect;
 
 // the width the kernel uses for a table entry: odd and in [1, kMaxM] whatever the entry holds (the host refuses others)
 __device__ __forceinline__ int safe_width(int w) { return min(max(w, 1), kMaxM) | 1; }

@@ -6,17 +6,13 @@
 // apply (one block per (b, c, f) row of T values, 16-byte stores).  A device flag switches the whole thing to a copy, so that
 // a captured step can follow the reference's host coin flip without being captured again.
 #include "eat_common.h"
+#include "loss_terms.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int kMsRowsPerBlock = 4;     // one wave per (b, f) row
 constexpr int kMsReg = 16;             // C T <= 64 * kMsReg: the row stays in registers between the passes
-
-__device__ __forceinline__ double ms_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // stats[(b F + f) 2] = {mu, sig} of row (b, f): n = C T values, C segments of T contiguous floats.  Lane l takes the values
 // l, l + 64, ... of the row in order, sums them in fp64, then a fixed butterfly: mu = sum / n; the second pass sums
@@ -53,7 +49,7 @@ __global__ __launch_bounds__(256) void mixstyle_stats_kernel(const float* __rest
   } else {
     for (int j = lane; j < n; j += 64) s += (double)at(j);
   }
-  const double mu = ms_wave_sum(s) / (double)n;
+  const double mu = eat::wave_sum_d(s) / (double)n;
   double q = 0.0;
   if constexpr (KR > 0) {
 #pragma unroll
@@ -68,7 +64,7 @@ __global__ __launch_bounds__(256) void mixstyle_stats_kernel(const float* __rest
       q += d * d;
     }
   }
-  const double var = ms_wave_sum(q) / (double)(n - 1);
+  const double var = eat::wave_sum_d(q) / (double)(n - 1);
   if (lane == 0) {
     stats[2 * (size_t)row] = (float)mu;
     stats[2 * (size_t)row + 1] = (float)sqrt(var + (double)eps);
@@ -92,9 +88,9 @@ __global__ __launch_bounds__(256) void mixstyle_apply_kernel(const float* __rest
   const bool on = apply == nullptr || *apply != 0;
   double a = 1.0, m0 = 0.0, m1 = 0.0;
   if (on) {
-    int pb = perm[b];
-    double l = (double)lam[b];
-    if (pb < 0 || pb >= B) pb = b, l = __builtin_nan("");          // (the wrapper validates; never read outside stats)
+    const eat::MixRow mr = eat::mix_row(perm, lam, b, B);         // (the wrapper validates; never read outside stats)
+    const int pb = mr.pb;
+    const double l = mr.lam;
     const float* sa = stats + 2 * ((size_t)b * F + f);
     const float* sp = stats + 2 * ((size_t)pb * F + f);
     const double mu = (double)sa[0], sig = (double)sa[1];

@@ -4,16 +4,12 @@
 //   eat_wave_augment_ragged  launch 1: the mean of each wave-mixed slot's window (fp64, fixed order) into a workspace;
 //                            launch 2: crop / pad + gain + roll + wave-mix of the rows, and the mixed multi-hot label rows
 #include "eat_common.h"
+#include "event_bank.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int kMeanThreads = 1024;     // one block per slot: 16 waves of 16-byte loads keep ~64 KB in flight per window
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // One slot (clip i cropped at st): where its window starts in `waves` and how many samples of it exist.  ok = false: a table
 // entry or a bank entry that would read outside `waves` or outside the clip - nothing is read for such a slot.
@@ -26,16 +22,11 @@ struct Slot {
 
 __device__ __forceinline__ Slot ragged_slot(const long long* __restrict__ offsets, const int* __restrict__ lengths,
                                             long long n_bank, long long n_samples, int L, int i, int st) {
-  Slot s{0, 0, 0, false};
-  if (i < 0 || i >= n_bank) return s;
-  const long long off = offsets[i];
-  const int len = lengths[i];
-  if (off < 0 || len < 1 || off > n_samples - len || st < 0 || st >= len) return s;
-  s.src = off + st;
-  s.w = min(len - st, L);
-  s.whole = st == 0 && len <= L;
-  s.ok = true;
-  return s;
+  if (i < 0 || i >= n_bank) return Slot{0, 0, 0, false};
+  const long long off = offsets[i];                             // (issued with clip_window's load of lengths[i])
+  const eat::ClipWindow cw = eat::clip_window(lengths, n_bank, L, i, st);
+  if (!cw.ok || off < 0 || off > n_samples - cw.len) return Slot{0, 0, 0, false};
+  return Slot{off + st, cw.w, st == 0 && cw.len <= L, true};
 }
 
 struct Row {
@@ -93,7 +84,7 @@ __global__ __launch_bounds__(kMeanThreads) void ragged_mean_kernel(
   }
   if (t == 0)
     for (int n = head + 4 * nv; n < s.w; ++n) acc += (double)x[n];
-  acc = wave_sum_d(acc);
+  acc = eat::wave_sum_d(acc);
   if ((t & 63) == 0) s_red[t >> 6] = acc;
   __syncthreads();
   if (t == 0) {

@@ -9,6 +9,9 @@
 // over all (b, t): a thread takes the elements tid, tid + 256, ... in order and adds in fp64, then a fixed butterfly and the four
 // waves in order - no atomics, the same bits on every call.  Reads are runs of Tp contiguous floats per sample.
 #include "eat_common.h"
+#include "event_bank.h"
+#include "loss_terms.h"
+#include "reduce.h"
 #include "../../include/eat_sed.h"
 
 namespace {
@@ -16,37 +19,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kGridY = 65535;
 
-// the sigmoid of tag.hip / detect.hip: ONE expression for a probability across the library
-__device__ __forceinline__ float sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum over the block in a fixed order (every thread receives it); s: 4 doubles of LDS, free to reuse after the call
-__device__ __forceinline__ double block_sum_d(double v, double* s) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = ((s[0] + s[1]) + s[2]) + s[3];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ long long block_sum_ll(long long v, long long* s) {
-  v = wave_sum_ll(v);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const long long r = s[0] + s[1] + s[2] + s[3];
-  __syncthreads();
-  return r;
-}
+using eat::block_sum_d, eat::block_sum_ll;
 
 // ---------------------------------------------------------------------------------------------------------- targets
 struct SedSlot {
@@ -57,39 +30,23 @@ struct SedSlot {
 
 __device__ __forceinline__ SedSlot sed_slot(const long long* __restrict__ eo, const int* __restrict__ lengths, long long n_bank,
                                             long long n_events, int L, int i, int st, int sh) {
-  SedSlot q{0, 0, 0, 0, 0, false};
-  if (i < 0 || i >= n_bank) return q;
-  const int len = lengths[i];
-  if (len < 1 || st < 0 || st >= len) return q;             // (the refusals of ragged_slot)
-  const long long a = eo[i], b = eo[i + 1];
-  q.e0 = a < 0 ? 0 : (a > n_events ? n_events : a);
-  q.e1 = b < q.e0 ? q.e0 : (b > n_events ? n_events : b);
-  q.st = st;
-  q.w = min(len - st, L);
-  q.s = (int)(((long long)sh % L + L) % L);
-  q.ok = true;
-  return q;
+  const eat::ClipWindow cw = eat::clip_window(lengths, n_bank, L, i, st);
+  if (!cw.ok) return SedSlot{0, 0, 0, 0, 0, false};
+  const eat::EventRows r = eat::event_rows(eo, n_events, i);
+  return SedSlot{r.e0, r.e1, st, cw.w, (int)(((long long)sh % L + L) % L), true};
 }
 
 // 1 iff an event of class c of the slot's clip shows in one of the output samples [n0, n1) of the rolled window
 __device__ __forceinline__ int sed_active(const int* __restrict__ ev, const SedSlot& q, int c, long long n0, long long n1, int L) {
-  long long lo = q.e0, hi = q.e1;
-  while (lo < hi) {                                          // the first row of a class >= c
-    const long long mid = (lo + hi) >> 1;
-    if (ev[3 * mid] < c) lo = mid + 1; else hi = mid;
-  }
   // window positions p = (n - s) mod L of the frame: [a_lo, a_hi) from its samples n >= s, [b_lo, b_hi) from those below s;
   // only p < w is signal
   const long long s = q.s, w = q.w;
   const long long a_lo = (n0 > s ? n0 : s) - s, a_hi = min(n1 - s, w);
   const long long b_lo = n0 - s + L, b_hi = min((n1 < s ? n1 : s) - s + L, w);
-  for (long long e = lo; e < q.e1; ++e) {
-    if (ev[3 * e] != c) break;
-    const long long on = (long long)ev[3 * e + 1] - q.st, off = (long long)ev[3 * e + 2] - q.st;
-    if (a_lo < a_hi && on < a_hi && off > a_lo) return 1;
-    if (b_lo < b_hi && on < b_hi && off > b_lo) return 1;
-  }
-  return 0;
+  return eat::any_row_of_class(ev, q.e0, q.e1, c, [&](long long ev_on, long long ev_off) {
+    const long long on = ev_on - q.st, off = ev_off - q.st;
+    return (a_lo < a_hi && on < a_hi && off > a_lo) || (b_lo < b_hi && on < b_hi && off > b_lo);
+  });
 }
 
 __global__ __launch_bounds__(kThreads) void sed_targets_kernel(
@@ -170,20 +127,15 @@ __global__ __launch_bounds__(kThreads) void frame_bce_kernel(
     if (t < nb) {
       const float yf = y[at];
       double tt = (double)yf;
-      if (perm != nullptr) {
-        int pb = perm[b];
-        double l = (double)lam[b];
-        if (pb < 0 || pb >= B) pb = b, l = __builtin_nan("");        // a bad permutation poisons its row, nothing outside y is read
-        tt = l * tt + (1.0 - l) * (double)y[((long long)pb * K + c) * Tp + t];
-      }
+      const eat::MixRow mr = eat::mix_row(perm, lam, b, B);
+      if (mr.mixed) tt = mr.lam * tt + (1.0 - mr.lam) * (double)y[((long long)mr.pb * K + c) * Tp + t];
       const double v = (double)zf;
-      const double e = exp(-fabs(v));
-      const double sg = v >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-      loss += (v > 0.0 ? v : 0.0) - v * tt + log1p(e);
-      d = (sg - tt) / dM;                                            // (nb >= 1 here, so M >= 1)
+      const eat::BceTerm r = eat::bce_term(v);
+      loss += r.loss(v, tt);
+      d = (r.p - tt) / dM;                                           // (nb >= 1 here, so M >= 1)
       db += d;
       if (counts != nullptr) {
-        const bool p = sigmoid(zf) >= th, g = yf > 0.5f;
+        const bool p = eat::sigmoid(zf) >= th, g = yf > 0.5f;
         tp += (p && g) ? 1 : 0;
         fp += (p && !g) ? 1 : 0;
         fn += (!p && g) ? 1 : 0;

@@ -2,15 +2,15 @@
 // on the host - sigmoid, device->host copy, numpy argsort - and what librosa.load does per file - dequantise, down-mix,
 // resample - as two kernels over all windows / all samples at once.  (The windowed mel front-end is in mel.hip.)
 #include "eat_common.h"
+#include "loss_terms.h"
 #include "../../include/eat_tag.h"
 
 namespace {
 
 constexpr int kRowsPerBlock = 4;      // one wavefront per row
 
-// ONE expression for p, used by the store of probs_all and by every selection round: the rounds recompute p from the
-// logits (C / 64 exps per lane and round, L1 hits) instead of caching a row whose length has no bound.
-__device__ __forceinline__ float sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+// eat::sigmoid is ONE expression for p, used by the store of probs_all and by every selection round: the rounds recompute
+// p from the logits (C / 64 exps per lane and round, L1 hits) instead of caching a row whose length has no bound.
 
 // (p, i) ranks before (q, j): larger probability first, equal probabilities by ascending class index
 __device__ __forceinline__ bool before(float p, int i, float q, int j) { return p > q || (p == q && i < j); }
@@ -25,14 +25,14 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void tag_topk_kernel(const floa
   if (row >= N) return;                                    // wave-uniform
   const float* z = logits + row * C;
   if (probs_all != nullptr)
-    for (int i = lane; i < C; i += 64) probs_all[row * C + i] = sigmoid(z[i]);
+    for (int i = lane; i < C; i += 64) probs_all[row * C + i] = eat::sigmoid(z[i]);
   float lp = 2.0f;                                         // the winner of the previous round; p <= 1 ranks after (2, -1)
   int li = -1;
   for (int r = 0; r < k; ++r) {
     float bp = -1.0f;                                      // p >= 0 ranks before (-1, C)
     int bi = C;
     for (int i = lane; i < C; i += 64) {
-      const float p = sigmoid(z[i]);
+      const float p = eat::sigmoid(z[i]);
       if (before(lp, li, p, i) && before(p, i, bp, bi)) { bp = p; bi = i; }
     }
 #pragma unroll

@@ -12,40 +12,16 @@
 // four waves in order - no atomics, the same bits on every call.  The number of framed samples is counted by every block from
 // `framed` itself, so a captured step serves any mixture of strong and weak clips.
 #include "eat_common.h"
+#include "event_bank.h"
+#include "loss_terms.h"
+#include "reduce.h"
 #include "../../include/eat_weak_sed.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum over the block in a fixed order (every thread receives it); s: 4 values of LDS, free to reuse after the call
-__device__ __forceinline__ double block_sum_d(double v, double* s) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = ((s[0] + s[1]) + s[2]) + s[3];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ long long block_sum_ll(long long v, long long* s) {
-  v = wave_sum_ll(v);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const long long r = s[0] + s[1] + s[2] + s[3];
-  __syncthreads();
-  return r;
-}
+using eat::block_sum_d, eat::block_sum_ll;
 
 // ---------------------------------------------------------------------------------------------------------- clip targets
 struct ClipSlot {
@@ -54,34 +30,17 @@ struct ClipSlot {
   bool ok;
 };
 
-// (the refusals of sed_slot in sed.hip)
 __device__ __forceinline__ ClipSlot clip_slot(const long long* __restrict__ eo, const int* __restrict__ lengths, long long n_bank,
                                               long long n_events, int L, int i, int st) {
-  ClipSlot q{0, 0, 0, 0, false};
-  if (i < 0 || i >= n_bank) return q;
-  const int len = lengths[i];
-  if (len < 1 || st < 0 || st >= len) return q;
-  const long long a = eo[i], b = eo[i + 1];
-  q.e0 = a < 0 ? 0 : (a > n_events ? n_events : a);
-  q.e1 = b < q.e0 ? q.e0 : (b > n_events ? n_events : b);
-  q.lo = st;
-  q.hi = (long long)st + min(len - st, L);
-  q.ok = true;
-  return q;
+  const eat::ClipWindow cw = eat::clip_window(lengths, n_bank, L, i, st);
+  if (!cw.ok) return ClipSlot{0, 0, 0, 0, false};
+  const eat::EventRows r = eat::event_rows(eo, n_events, i);
+  return ClipSlot{r.e0, r.e1, st, (long long)st + cw.w, true};
 }
 
 // 1 iff an event of class c of the slot's clip meets the samples the slot shows
 __device__ __forceinline__ int clip_active(const int* __restrict__ ev, const ClipSlot& q, int c) {
-  long long lo = q.e0, hi = q.e1;
-  while (lo < hi) {                                          // the first row of a class >= c
-    const long long mid = (lo + hi) >> 1;
-    if (ev[3 * mid] < c) lo = mid + 1; else hi = mid;
-  }
-  for (long long e = lo; e < q.e1; ++e) {
-    if (ev[3 * e] != c) break;
-    if ((long long)ev[3 * e + 1] < q.hi && (long long)ev[3 * e + 2] > q.lo) return 1;
-  }
-  return 0;
+  return eat::class_run_overlaps(ev, q.e0, q.e1, c, q.lo, q.hi);
 }
 
 __global__ __launch_bounds__(kThreads) void sed_clip_targets_kernel(
@@ -125,15 +84,6 @@ __device__ __forceinline__ int row_framed(const int* __restrict__ framed, const 
   return f;
 }
 
-struct Prob {
-  double p, q, sp;       // s(z), s(-z) and the softplus log1p(exp(-|z|)) of the frame BCE
-};
-__device__ __forceinline__ Prob prob(double v) {
-  const double e = exp(-fabs(v));
-  const double a = 1.0 / (1.0 + e), b = e / (1.0 + e);
-  return Prob{v >= 0.0 ? a : b, v >= 0.0 ? b : a, log1p(e)};
-}
-
 // Block c: class row c of every sample, a group of G lanes per row (b, c).  ws[c] = the class's frame-loss sum, ws[K + c] its
 // clip-loss sum (fp64, not yet normalised), ws[2 K] = N_f (block 0).
 template <int G>
@@ -171,9 +121,8 @@ __global__ __launch_bounds__(kThreads) void weak_frame_bce_kernel(
       fb = framed[b] != 0;
       tw = (double)w[(long long)b * K + c];
       if (perm != nullptr) {
-        pb = perm[b];
-        lm = (double)lam[b];
-        if (pb < 0 || pb >= B) pb = b, lm = __builtin_nan(""), bad = true;   // a bad permutation poisons its row, nothing outside is read
+        const eat::MixRow mr = eat::mix_row(perm, lam, b, B);
+        pb = mr.pb, lm = mr.lam, bad = mr.bad;
         tw = lm * tw + (1.0 - lm) * (double)w[(long long)pb * K + c];
         fb = fb && framed[pb] != 0;
       }
@@ -184,14 +133,14 @@ __global__ __launch_bounds__(kThreads) void weak_frame_bce_kernel(
     if (live)
       for (int t = l; t < T; t += G) {
         const double v = (double)z[row + t];
-        const Prob r = prob(v);
+        const eat::BceTerm r = eat::bce_term(v);
         s1 += r.p;
         s2 += r.p * r.p;
         double ty = 0.0;
         if (fb) {
           ty = (double)y[row + t];
           if (perm != nullptr) ty = lm * ty + (1.0 - lm) * (double)y[prow + t];
-          loss_f += (v > 0.0 ? v : 0.0) - v * ty + r.sp;
+          loss_f += r.loss(v, ty);
         }
         if (t == l) p0 = r.p, q0 = r.q, ty0 = ty;
       }
@@ -215,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void weak_frame_bce_kernel(
         if (t < T) {
           double p = p0, q = q0, ty = ty0;
           if (t != l) {
-            const Prob r = prob((double)z[row + t]);
+            const eat::BceTerm r = eat::bce_term((double)z[row + t]);
             p = r.p, q = r.q;
             if (fb) {
               ty = (double)y[row + t];

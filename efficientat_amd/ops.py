@@ -1773,27 +1773,27 @@ def _dev_int32(t, name, n):
     return t.data_ptr()
 
 
+def _row_loss_operands(fn, logits, perm, lam, sums, row_loss):
+    """What `softmax_ce_fwd_bwd` and `masked_bce_fwd_bwd` check alike -> (B, C, perm, lam, sums, row_loss pointers)."""
+    if logits.dim() != 2:
+        raise _lib.EatHipError(f"{fn}: logits must be (B, C), got {tuple(logits.shape)}")
+    B, C = logits.shape
+    p_perm, p_lam = _mix_operands(fn, perm, lam, B, logits)
+    p_sums = None if sums is None else _glue_operand(sums, f"{fn}: sums", torch.float32, logits, at_least=1)
+    p_row = None if row_loss is None else _glue_operand(row_loss, f"{fn}: row_loss", torch.float32, logits, n=B)
+    return B, C, p_perm, p_lam, p_sums, p_row
+
+
 def softmax_ce_fwd_bwd(logits, y, perm=None, lam=None, sums=None, grad=True, row_loss=None, row_argmax=None):
     """Soft-target cross-entropy of (B, C) logits against y (B, C), with the mix-up t = lam y + (1 - lam) y[perm] folded in
     (include/eat_hip.h: eat_softmax_ce_fwd_bwd).  -> dlogits (B, C) (None with grad=False); `sums` (>= 1 fp32) += the batch
     mean; `row_loss` (B) fp32 and `row_argmax` (B) int32 are filled when given."""
-    if logits.dim() != 2:
-        raise _lib.EatHipError(f"softmax_ce_fwd_bwd: logits must be (B, C), got {tuple(logits.shape)}")
-    B, C = logits.shape
+    B, C, p_perm, p_lam, p_sums, p_row = _row_loss_operands("softmax_ce_fwd_bwd", logits, perm, lam, sums, row_loss)
     if tuple(y.shape) != (B, C):
         raise _lib.EatHipError(f"softmax_ce_fwd_bwd: y {tuple(y.shape)} does not match the logits {(B, C)}")
-    if (perm is None) != (lam is None):
-        raise _lib.EatHipError("softmax_ce_fwd_bwd: perm and lam go together")
-    if lam is not None and lam.numel() != B:
-        raise _lib.EatHipError("softmax_ce_fwd_bwd: lam must hold B values")
-    if row_loss is not None and row_loss.numel() != B:
-        raise _lib.EatHipError("softmax_ce_fwd_bwd: row_loss must hold B values")
-    if sums is not None and (sums.dtype != torch.float32 or sums.numel() < 1):
-        raise _lib.EatHipError("softmax_ce_fwd_bwd: sums must be a float32 tensor")
     dlogits = torch.empty_like(logits) if grad else None
-    _lib.call("eat_softmax_ce_fwd_bwd", _dev(logits, "logits"), _dev(y, "y"), _dev_int32(perm, "perm", B), _opt(lam, "lam"),
-              B, C, _opt(sums, "sums"), _opt(dlogits, "dlogits"), _opt(row_loss, "row_loss"),
-              _dev_int32(row_argmax, "row_argmax", B), _stream())
+    _lib.call("eat_softmax_ce_fwd_bwd", _dev(logits, "logits"), _dev(y, "y"), p_perm, p_lam, B, C, p_sums,
+              _opt(dlogits, "dlogits"), p_row, _dev_int32(row_argmax, "row_argmax", B), _stream())
     return dlogits
 
 
@@ -1846,19 +1846,9 @@ def masked_bce_fwd_bwd(logits, yy, perm=None, lam=None, sums=None, grad=True, ro
     labels folded in (include/eat_hip.h: eat_masked_bce_fwd_bwd).  -> dlogits (B, C) (None with grad=False); `sums` (>= 1 fp32)
     += the batch mean; `row_loss` (B) fp32 is filled when given; `probs` (B, C) fp32 receives sigmoid(logits) - it may be a
     row slice of a wider matrix (unit column stride)."""
-    if logits.dim() != 2:
-        raise _lib.EatHipError(f"masked_bce_fwd_bwd: logits must be (B, C), got {tuple(logits.shape)}")
-    B, C = logits.shape
+    B, C, p_perm, p_lam, p_sums, p_row = _row_loss_operands("masked_bce_fwd_bwd", logits, perm, lam, sums, row_loss)
     if tuple(yy.shape) != (B, 2 * C):
         raise _lib.EatHipError(f"masked_bce_fwd_bwd: yy {tuple(yy.shape)} does not match the logits: expected {(B, 2 * C)}")
-    if (perm is None) != (lam is None):
-        raise _lib.EatHipError("masked_bce_fwd_bwd: perm and lam go together")
-    if lam is not None and lam.numel() != B:
-        raise _lib.EatHipError("masked_bce_fwd_bwd: lam must hold B values")
-    if row_loss is not None and row_loss.numel() != B:
-        raise _lib.EatHipError("masked_bce_fwd_bwd: row_loss must hold B values")
-    if sums is not None and (sums.dtype != torch.float32 or sums.numel() < 1):
-        raise _lib.EatHipError("masked_bce_fwd_bwd: sums must be a float32 tensor")
     stride = 0
     if probs is not None:
         if (not probs.is_cuda or probs.dtype != torch.float32 or tuple(probs.shape) != (B, C) or probs.stride(1) != 1
@@ -1867,9 +1857,8 @@ def masked_bce_fwd_bwd(logits, yy, perm=None, lam=None, sums=None, grad=True, ro
                                    f"stride (got {probs.dtype}, {tuple(probs.shape)}, strides {probs.stride()})")
         stride = probs.stride(0) if B > 1 else C
     dlogits = torch.empty_like(logits) if grad else None
-    _lib.call("eat_masked_bce_fwd_bwd", _dev(logits, "logits"), _dev(yy, "yy"), _dev_int32(perm, "perm", B), _opt(lam, "lam"),
-              B, C, int(bool(binarize)), _opt(sums, "sums"), _opt(dlogits, "dlogits"), _opt(row_loss, "row_loss"),
-              None if probs is None else probs.data_ptr(), stride, _stream())
+    _lib.call("eat_masked_bce_fwd_bwd", _dev(logits, "logits"), _dev(yy, "yy"), p_perm, p_lam, B, C, int(bool(binarize)), p_sums,
+              _opt(dlogits, "dlogits"), p_row, None if probs is None else probs.data_ptr(), stride, _stream())
     return dlogits
 
 
@@ -1913,6 +1902,15 @@ def check_ragged_draws(idx, start, shift, lengths_cpu, L):
         raise ValueError(f"wave_augment_ragged: a crop start lies outside [0, max(0, length - {L})]")
 
 
+def _stage_draws(dev, check, ints, floats):
+    """Draw tables -> on `dev`, int32 / fp32: CPU tables are validated with `check()` and uploaded, device tables pass as staged."""
+    if ints[0].is_cuda:
+        return (*ints, *floats)
+    check()
+    return (*(t.to(dev, torch.int32, non_blocking=True) for t in ints),
+            *(t.to(dev, torch.float32, non_blocking=True) for t in floats))
+
+
 def wave_augment_ragged(bank, idx, start, shift, amp, mix, L, out=None, yy=None, win_mean=None, labels=True):
     """Crop / pad + gain + roll + wave-mix of a batch gathered from a ragged resident bank, and its mixed label rows
     (include/eat_hip.h: eat_wave_augment_ragged) -> (out (B, L), yy (B, 2C) = [labels | ones]).  bank: the dict of
@@ -1924,10 +1922,8 @@ def wave_augment_ragged(bank, idx, start, shift, amp, mix, L, out=None, yy=None,
     n_bank, L = lengths.numel(), int(L)
     B = torch.as_tensor(mix).numel()
     dev = waves.device
-    if not idx.is_cuda:
-        check_ragged_draws(idx, start, shift, bank["lengths_cpu"], L)
-        idx, start, shift = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, start, shift))
-        amp, mix = (t.to(dev, torch.float32, non_blocking=True) for t in (amp, mix))
+    idx, start, shift, amp, mix = _stage_draws(dev, lambda: check_ragged_draws(idx, start, shift, bank["lengths_cpu"], L),
+                                               (idx, start, shift), (amp, mix))
     if waves.dim() != 1 or offsets.dtype != torch.int64 or not offsets.is_cuda or offsets.numel() != n_bank:
         raise _lib.EatHipError("wave_augment_ragged: waves must be flat and offsets an int64 GPU tensor of one value per clip")
     if clip_sum.dtype != torch.float64 or not clip_sum.is_cuda or clip_sum.numel() != n_bank:
@@ -2732,6 +2728,20 @@ def check_eval_draws(idx, start, lengths_cpu):
         raise ValueError("sed_targets: a window start lies outside its clip")
 
 
+def _event_bank_operands(fn, bank):
+    """`sed.load_bank`'s event table, checked from metadata -> (events or None, E, event_offsets, lengths, n_bank, K, strong or None)."""
+    events, eo, lengths, strong = bank["events"], bank["event_offsets"], bank["lengths"], bank.get("strong")
+    n_bank, dev = lengths.numel(), lengths.device
+    if (events.dtype != torch.int32 or events.dim() != 2 or events.shape[1] != 3 or not events.is_contiguous()
+            or events.device != dev):
+        raise _lib.EatHipError(f"{fn}: events must be a contiguous (E, 3) int32 tensor on {dev}")
+    if eo.dtype != torch.int64 or eo.numel() != n_bank + 1 or not eo.is_contiguous() or eo.device != dev:
+        raise _lib.EatHipError(f"{fn}: event_offsets must be a contiguous int64 tensor of N + 1 = {n_bank + 1} values on {dev}")
+    p_strong = None if strong is None else _glue_operand(strong, f"{fn}: strong", torch.uint8, lengths, n=n_bank)
+    E = events.shape[0]
+    return events.data_ptr() if E else None, E, eo.data_ptr(), lengths, n_bank, len(bank["classes"]), p_strong
+
+
 def sed_targets(bank, idx, start, shift, mix, L, R, T, Tp=None, out=None, train=True):
     """Frame targets y (B, K, Tp) of the batch that `wave_augment_ragged` builds from the same tables (include/eat_sed.h:
     eat_sed_targets).  bank: the dict of `sed.load_bank` (events (E, 3) int32, event_offsets (N + 1) int64, lengths on the
@@ -2740,35 +2750,54 @@ def sed_targets(bank, idx, start, shift, mix, L, R, T, Tp=None, out=None, train=
     (the static buffers of a captured step) must have been validated before they were staged.  L samples per window, R per
     frame, T frames, Tp >= T the row pitch (default `pitch4(T)`)."""
     fn = "sed_targets"
-    events, eo, lengths = bank["events"], bank["event_offsets"], bank["lengths"]
-    n_bank, K = lengths.numel(), len(bank["classes"])
+    lengths = bank["lengths"]
     L, R, T = int(L), int(R), int(T)
     Tp = pitch4(T) if Tp is None else int(Tp)
     B = torch.as_tensor(mix).numel()
     dev = lengths.device
     if L < 1 or R < 1 or T < 1 or Tp < T or B < 1:
         raise _lib.EatHipError(f"{fn}: need B, L, R, T >= 1 and Tp >= T (got B={B} L={L} R={R} T={T} Tp={Tp})")
-    if not idx.is_cuda:
+
+    def check():
         if train:
             check_ragged_draws(idx, start, shift, bank["lengths_cpu"], L)
         else:
             check_eval_draws(idx, start, bank["lengths_cpu"])
             if torch.as_tensor(shift).numel() != 2 * B or bool((torch.as_tensor(shift).abs() >= L).any()):
                 raise ValueError(f"{fn}: shift must hold 2B values inside (-{L}, {L})")
-        idx, start, shift = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, start, shift))
-        mix = mix.to(dev, torch.float32, non_blocking=True)
-    if (events.dtype != torch.int32 or events.dim() != 2 or events.shape[1] != 3 or not events.is_contiguous()
-            or events.device != dev):
-        raise _lib.EatHipError(f"{fn}: events must be a contiguous (E, 3) int32 tensor on {dev}")
-    if eo.dtype != torch.int64 or eo.numel() != n_bank + 1 or not eo.is_contiguous() or eo.device != dev:
-        raise _lib.EatHipError(f"{fn}: event_offsets must be a contiguous int64 tensor of N + 1 = {n_bank + 1} values on {dev}")
+
+    idx, start, shift, mix = _stage_draws(dev, check, (idx, start, shift), (mix,))
+    p_ev, E, p_eo, lengths, n_bank, K, _ = _event_bank_operands(fn, bank)
     p_mix = _glue_operand(mix, f"{fn}: mix", torch.float32, lengths, n=B)
     y = _head_out(out, f"{fn}: out", (B, K, Tp), lengths)
-    E = events.shape[0]
-    _lib.call("eat_sed_targets", events.data_ptr() if E else None, E, eo.data_ptr(), _dev_int32(lengths, "lengths", n_bank), n_bank,
+    _lib.call("eat_sed_targets", p_ev, E, p_eo, _dev_int32(lengths, "lengths", n_bank), n_bank,
               K, _dev_int32(idx, "idx", 2 * B), _dev_int32(start, "start", 2 * B), _dev_int32(shift, "shift", 2 * B), p_mix, B,
               L, R, T, Tp, _on_gpu(y, f"{fn}: out"), _stream())
     return y.view(B, K, Tp)
+
+
+def _frame_geometry(fn, z, T, Kp):
+    """The (B, K, Tp) logits of `frame_bce_fwd_bwd` / `weak_frame_bce_fwd_bwd` with T frames and Kp >= K rows -> (B, K, Tp, T, Kp)."""
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.numel() < 1:
+        raise _lib.EatHipError(f"{fn}: z must be a non-empty (B, K, Tp) tensor, got {tuple(getattr(z, 'shape', ()))}")
+    B, K, Tp = z.shape
+    T = int(T)
+    Kp = K if Kp is None else int(Kp)
+    if T < 1 or Tp < T or Kp < K:
+        raise _lib.EatHipError(f"{fn}: need 1 <= T <= Tp and Kp >= K (got T={T} Tp={Tp} K={K} Kp={Kp})")
+    return B, K, Tp, T, Kp
+
+
+def _frame_loss_buffers(fn, z, K, Kp, sums, n_sums, n_ws, grad, dbias):
+    """After every operand is checked: `sums` (>= n_sums fp32) with its fp64 workspace of n_ws values, dlogits (B, Kp, Tp) and
+    dbias (K) -> (sums pointer, ws, dl, db); what is not asked for is None."""
+    p_sums = ws = None
+    if sums is not None:
+        p_sums = _glue_operand(sums, f"{fn}: sums", torch.float32, z, at_least=n_sums)
+        ws = torch.empty(n_ws, device=z.device, dtype=torch.float64)
+    dl = torch.empty((z.shape[0], Kp, z.shape[2]), device=z.device, dtype=torch.float32) if grad else None
+    db = torch.empty((K,), device=z.device, dtype=torch.float32) if dbias else None
+    return p_sums, ws, dl, db
 
 
 def frame_bce_fwd_bwd(z, y, T, perm=None, lam=None, nframes=None, sums=None, grad=True, Kp=None, dbias=False, counts=None,
@@ -2779,13 +2808,7 @@ def frame_bce_fwd_bwd(z, y, T, perm=None, lam=None, nframes=None, sums=None, gra
     columns.  `sums` (>= 1 fp32) += the mean; `counts` (K, 3) int64 += (tp, fp, fn) of sigmoid(z) >= thr (K) against
     y > 0.5 (not with perm); `rows` (B T, K) fp32 receives the logits as the row-major score matrix of `metrics.ap_auc`."""
     fn = "frame_bce_fwd_bwd"
-    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.numel() < 1:
-        raise _lib.EatHipError(f"{fn}: z must be a non-empty (B, K, Tp) tensor, got {tuple(getattr(z, 'shape', ()))}")
-    B, K, Tp = z.shape
-    T = int(T)
-    Kp = K if Kp is None else int(Kp)
-    if T < 1 or Tp < T or Kp < K:
-        raise _lib.EatHipError(f"{fn}: need 1 <= T <= Tp and Kp >= K (got T={T} Tp={Tp} K={K} Kp={Kp})")
+    B, K, Tp, T, Kp = _frame_geometry(fn, z, T, Kp)
     _glue_operand(z, f"{fn}: z", torch.float32, z)
     p_y = _glue_operand(y, f"{fn}: y", torch.float32, z, n=B * K * Tp)
     p_perm, p_lam = _mix_operands(fn, perm, lam, B, z)
@@ -2799,12 +2822,7 @@ def frame_bce_fwd_bwd(z, y, T, perm=None, lam=None, nframes=None, sums=None, gra
         p_counts = _glue_operand(counts, f"{fn}: counts", torch.int64, z, n=3 * K)
         p_thr = _glue_operand(thr, f"{fn}: thr", torch.float32, z, n=K)
     p_rows = None if rows is None else _glue_operand(rows, f"{fn}: rows", torch.float32, z, n=B * T * K)
-    p_sums = ws = None
-    if sums is not None:
-        p_sums = _glue_operand(sums, f"{fn}: sums", torch.float32, z, at_least=1)
-        ws = torch.empty(K + 1, device=z.device, dtype=torch.float64)
-    dl = torch.empty((B, Kp, Tp), device=z.device, dtype=torch.float32) if grad else None
-    db = torch.empty((K,), device=z.device, dtype=torch.float32) if dbias else None
+    p_sums, ws, dl, db = _frame_loss_buffers(fn, z, K, Kp, sums, 1, K + 1, grad, dbias)
     _lib.call("eat_frame_bce_fwd_bwd", _on_gpu(z, f"{fn}: z"), p_y, p_perm, p_lam, p_nf, p_thr, B, K, T, Tp, Kp, p_sums,
               None if dl is None else dl.data_ptr(), None if db is None else db.data_ptr(), p_counts, p_rows,
               None if ws is None else ws.data_ptr(), _stream())
@@ -2875,30 +2893,22 @@ def sed_clip_targets(bank, idx, start, mix, L, out=None, framed_out=None):
     CPU tensors are validated here with `check_ragged_draws` and uploaded; device tensors (the static buffers of a captured
     step) must have been validated before they were staged.  L samples per window.  -> (w, framed)."""
     fn = "sed_clip_targets"
-    events, eo, lengths, strong = bank["events"], bank["event_offsets"], bank["lengths"], bank.get("strong")
-    n_bank, K = lengths.numel(), len(bank["classes"])
+    lengths = bank["lengths"]
     L = int(L)
     B = torch.as_tensor(mix).numel()
     dev = lengths.device
     if L < 1 or B < 1:
         raise _lib.EatHipError(f"{fn}: need B, L >= 1 (got B={B} L={L})")
-    if not idx.is_cuda:
-        check_ragged_draws(idx, start, torch.zeros_like(torch.as_tensor(idx)), bank["lengths_cpu"], L)
-        idx, start = (t.to(dev, torch.int32, non_blocking=True) for t in (idx, start))
-        mix = mix.to(dev, torch.float32, non_blocking=True)
-    if (events.dtype != torch.int32 or events.dim() != 2 or events.shape[1] != 3 or not events.is_contiguous()
-            or events.device != dev):
-        raise _lib.EatHipError(f"{fn}: events must be a contiguous (E, 3) int32 tensor on {dev}")
-    if eo.dtype != torch.int64 or eo.numel() != n_bank + 1 or not eo.is_contiguous() or eo.device != dev:
-        raise _lib.EatHipError(f"{fn}: event_offsets must be a contiguous int64 tensor of N + 1 = {n_bank + 1} values on {dev}")
-    p_strong = None if strong is None else _glue_operand(strong, f"{fn}: strong", torch.uint8, lengths, n=n_bank)
+    idx, start, mix = _stage_draws(
+        dev, lambda: check_ragged_draws(idx, start, torch.zeros_like(torch.as_tensor(idx)), bank["lengths_cpu"], L), (idx, start),
+        (mix,))
+    p_ev, E, p_eo, lengths, n_bank, K, p_strong = _event_bank_operands(fn, bank)
     p_mix = _glue_operand(mix, f"{fn}: mix", torch.float32, lengths, n=B)
     w = _head_out(out, f"{fn}: out", (B, K), lengths)
     if framed_out is None:
         framed_out = torch.empty((B,), device=dev, dtype=torch.int32)
     p_framed = _glue_operand(framed_out, f"{fn}: framed_out", torch.int32, lengths, n=B)
-    E = events.shape[0]
-    _lib.call("eat_sed_clip_targets", events.data_ptr() if E else None, E, eo.data_ptr(), _dev_int32(lengths, "lengths", n_bank),
+    _lib.call("eat_sed_clip_targets", p_ev, E, p_eo, _dev_int32(lengths, "lengths", n_bank),
               n_bank, K, _dev_int32(idx, "idx", 2 * B), _dev_int32(start, "start", 2 * B), p_mix, p_strong, B, L,
               _on_gpu(w, f"{fn}: out"), p_framed, _stream())
     return w.view(B, K), framed_out
@@ -2912,14 +2922,8 @@ def weak_frame_bce_fwd_bwd(z, y, w, framed, T, perm=None, lam=None, weak_weight=
     -> (dlogits (B, Kp, Tp) or None with grad=False, dbias (K) or None): d loss / d z with exactly-zero pad rows and columns.
     `sums` (>= 3 fp32) += (loss, frame term, clip term); `clip_prob` (B, K) fp32 receives the pooled probabilities."""
     fn = "weak_frame_bce_fwd_bwd"
-    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.numel() < 1:
-        raise _lib.EatHipError(f"{fn}: z must be a non-empty (B, K, Tp) tensor, got {tuple(getattr(z, 'shape', ()))}")
-    B, K, Tp = z.shape
-    T = int(T)
-    Kp = K if Kp is None else int(Kp)
+    B, K, Tp, T, Kp = _frame_geometry(fn, z, T, Kp)
     weak_weight, eps = float(weak_weight), float(eps)
-    if T < 1 or Tp < T or Kp < K:
-        raise _lib.EatHipError(f"{fn}: need 1 <= T <= Tp and Kp >= K (got T={T} Tp={Tp} K={K} Kp={Kp})")
     if not 0.0 <= weak_weight < float("inf"):
         raise _lib.EatHipError(f"{fn}: weak_weight must be finite and not negative (got {weak_weight})")
     if not 0.0 < eps < 0.5:
@@ -2930,12 +2934,7 @@ def weak_frame_bce_fwd_bwd(z, y, w, framed, T, perm=None, lam=None, weak_weight=
     p_framed = _glue_operand(framed, f"{fn}: framed", torch.int32, z, n=B)
     p_perm, p_lam = _mix_operands(fn, perm, lam, B, z)
     p_cp = None if clip_prob is None else _glue_operand(clip_prob, f"{fn}: clip_prob", torch.float32, z, n=B * K)
-    p_sums = ws = None
-    if sums is not None:
-        p_sums = _glue_operand(sums, f"{fn}: sums", torch.float32, z, at_least=3)
-        ws = torch.empty(2 * K + 1, device=z.device, dtype=torch.float64)
-    dl = torch.empty((B, Kp, Tp), device=z.device, dtype=torch.float32) if grad else None
-    db = torch.empty((K,), device=z.device, dtype=torch.float32) if dbias else None
+    p_sums, ws, dl, db = _frame_loss_buffers(fn, z, K, Kp, sums, 3, 2 * K + 1, grad, dbias)
     _lib.call("eat_weak_frame_bce_fwd_bwd", _on_gpu(z, f"{fn}: z"), p_y, p_w, p_framed, p_perm, p_lam, weak_weight, eps, B, K, T,
               Tp, Kp, p_sums, None if dl is None else dl.data_ptr(), None if db is None else db.data_ptr(), p_cp,
               None if ws is None else ws.data_ptr(), _stream())
