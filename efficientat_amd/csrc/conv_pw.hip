@@ -26,7 +26,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void gbl_void;
 
-constexpr int kKC = 32;          // max k rows per LDS stage
 constexpr int kTileN = 256;      // columns per block
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
@@ -53,6 +52,7 @@ __global__ void pw_prepack_kernel(const float* __restrict__ w, const float* __re
 }
 
 // LDS stage = [A: (kc/4)*MTW fragment rows of 64 floats, padded to 256][X: kc rows x 256][scale: kc x NS]
+// (pw_fwd_plan.h sizes the launch with the same two expressions)
 __host__ __device__ inline int a_stage_floats(int mtw, int kc) { return (((kc >> 2) * mtw * 64) + 255) & ~255; }
 __host__ __device__ inline int stage_floats(int mtw, int kc, int ns) {
   return a_stage_floats(mtw, kc) + kc * kTileN + ((kc * ns + 3) & ~3);
@@ -87,7 +87,7 @@ constexpr int kPipeKC = 16;
 
 // TF: the conv input is act_in(tf.a[k] * x + tf.b[k]) evaluated between the LDS read and the MFMA (training: BatchNorm +
 // activation of the depthwise conv fused into the project conv; see conv_pw_bf16.hip)
-struct PwTf { const float* a; const float* b; int act; };
+using PwTf = eat::InTf;
 
 template <int MTW, bool PIPE, bool TF>
 __global__ __launch_bounds__(256, 2) void pw_conv_kernel(
@@ -343,44 +343,18 @@ __global__ __launch_bounds__(1024) void linear_kernel(const float* __restrict__ 
 }
 
 template <int MTW>
-int launch_pw(hipStream_t s, const float* x, const float* wp, const float* bias, const float* in_scale,
-              const float* res, float* y, float* pool, int B, int Ci, int Co, int S, int MT, int MC, int act,
-              bool per_sample, PwTf tf, const float* x2, int c1, float* stats, eat::PwGStat gs) {
-  const long long N = (long long)B * S;
-  const int tps = per_sample ? (S + kTileN - 1) / kTileN : 0;
-  const int n_tiles = per_sample ? B * tps : (int)((N + kTileN - 1) / kTileN);
-  const long long wp_bstride = (long long)(Ci / 4) * MT * 64;
-  int NS = kTileN / S + 2;
-  if (NS > B) NS = B;
-  if (!in_scale) NS = 0;
-  const bool pipe = kPipeKC * NS <= 64;
-  int kc, n_stages;
-  size_t smem;
-  if (pipe) {
-    kc = kPipeKC;
-    const int n_chunks = (Ci + kc - 1) / kc;
-    n_stages = n_chunks < 3 ? n_chunks : 3;
-    // the scale slot is a fixed 64-float piece in this mode
-    smem = (size_t)n_stages * (a_stage_floats(MTW, kc) + kc * kTileN + (in_scale ? 64 : 0)) * sizeof(float);
-  } else {
-    // generic: <= 32 rows per stage, chunks balanced, multiple of 4
-    const int n_chunks = (Ci + kKC - 1) / kKC;
-    kc = (((Ci + n_chunks - 1) / n_chunks) + 3) & ~3;
-    n_stages = ((Ci + kc - 1) / kc) > 1 ? 2 : 1;
-    smem = (size_t)n_stages * stage_floats(MTW, kc, NS) * sizeof(float);
+int launch_pw(const eat::PwFwdReq& r, const eat::pw::PwPlan& p) {
+  auto kern = p.tf ? (p.pipe ? pw_conv_kernel<MTW, true, true> : pw_conv_kernel<MTW, false, true>)
+                   : (p.pipe ? pw_conv_kernel<MTW, true, false> : pw_conv_kernel<MTW, false, false>);
+  if (p.lds_bytes > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes);
+    if (e != hipSuccess) return eat::fail(EAT_ELAUNCH, "%s: cannot reserve %d B of LDS: %s", r.who, p.lds_bytes, hipGetErrorString(e));
   }
-  if (stats && smem < (size_t)10 * MTW * 16 * sizeof(float)) smem = (size_t)10 * MTW * 16 * sizeof(float);   // wave partials + (a, b)
-  if (smem > 160 * 1024) return eat::fail(EAT_EINVAL, "eat_pw_conv_fwd: LDS stage too large (%zu B)", smem);
-  auto kern = tf.a ? (pipe ? pw_conv_kernel<MTW, true, true> : pw_conv_kernel<MTW, false, true>)
-                   : (pipe ? pw_conv_kernel<MTW, true, false> : pw_conv_kernel<MTW, false, false>);
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return eat::fail(EAT_ELAUNCH, "eat_pw_conv_fwd: cannot reserve %zu B of LDS: %s", smem, hipGetErrorString(e));
-  }
-  const int tiles8 = (n_tiles + 7) / 8 * 8;
-  hipLaunchKernelGGL(kern, dim3(tiles8 * MC), dim3(256), smem, s, x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, MT,
-                     MC, n_tiles, NS, kc, n_stages, act, tps, wp_bstride, tf, x2, c1, stats, gs);
-  return eat::check_launch("eat_pw_conv_fwd");
+  hipLaunchKernelGGL(kern, dim3(p.grid[0]), dim3(256), p.lds_bytes, r.stream, reinterpret_cast<const float*>(r.x),
+                     reinterpret_cast<const float*>(r.wp), r.bias, r.in_scale, r.res, reinterpret_cast<float*>(r.y), r.pool, r.B,
+                     r.Ci, r.Co, r.S, p.MT, p.MC, p.n_tiles, p.NS, p.kc, p.n_stages, r.act, p.tps, p.wp_bstride, r.tf, r.x2, r.c1,
+                     r.stats, r.gs);
+  return eat::check_launch(r.who);
 }
 
 }  // namespace
@@ -406,38 +380,56 @@ extern "C" int eat_pw_prepack_t(const float* w_t, const float* row_scale, float*
   return pw_prepack_impl(w_t, row_scale, wp, Co, Ci, 1, stream);
 }
 
-static int pw_dispatch(const float* x, const float* wp, const float* bias, const float* in_scale, const float* res,
-                       float* y, float* pool, int B, int Ci, int Co, int S, int act, bool per_sample, hipStream_t s,
-                       PwTf tf = PwTf{nullptr, nullptr, 0}, const float* x2 = nullptr, int c1 = 0, float* stats = nullptr,
-                       eat::PwGStat gs = eat::PwGStat{nullptr, nullptr, nullptr, 0}) {
-  if (Ci % 4 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_fwd: Ci=%d must be a multiple of 4", Ci);
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_fwd: bad act %d", act);
-  if (B < 1 || Ci < 4 || Co < 1 || S < 1) return eat::fail(EAT_EINVAL, "eat_pw_conv_fwd: bad shape");
-  const int MT = (Co + 15) / 16;
-  if (S % 4 != 0) {    // planes that do not start on 16-byte boundaries (e.g. 40-mel models): plain 4-byte kernel
-    if (tf.a) return eat::fail(EAT_EINVAL, "eat_pw_conv_tf_fwd: S=%d must be a multiple of 4", S);
-    if (stats) return 1;                           // no epilogue statistics there: the caller runs the separate pass
-    return eat::pw_conv_generic(x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, act, 0,
-                                per_sample ? (long long)(Ci / 4) * MT * 64 * (long long)sizeof(float) : 0, s);
-  }
-  // Row chunking.  Every block re-reads its 256-column x tile, and a CU takes in only ~10 B/clk, so
-  // the tile must be tall: up to 8 m-tiles (128 rows) per block.
-  const int MC = (MT + 7) / 8;                    // row chunks
-  const int mtw = (MT + MC - 1) / MC;             // balanced m-tiles per block
-#define EAT_PW_CASE(n) case n: return launch_pw<n>(s, x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, MT, (MT + n - 1) / n, act, per_sample, tf, x2, c1, stats, gs);
-  switch (mtw) {
+namespace eat {
+
+int pw_lds_f32_launch(const PwFwdReq& r, const pw::PwPlan& p) {
+#define EAT_PW_CASE(n) case n: return launch_pw<n>(r, p);
+  switch (p.mtw) {
     EAT_PW_CASE(1) EAT_PW_CASE(2) EAT_PW_CASE(3) EAT_PW_CASE(4) EAT_PW_CASE(5)
     EAT_PW_CASE(6) EAT_PW_CASE(7) EAT_PW_CASE(8)
-    default: return eat::fail(EAT_EINVAL, "eat_pw_conv_fwd: internal tiling error");
+    default: return fail(EAT_EINVAL, "%s: internal tiling error", r.who);
   }
 #undef EAT_PW_CASE
 }
+
+// The one route of the forward 1x1 convs: the argument rules, the plan (pw_fwd_plan.h), the launcher of the planned kernel.
+int pw_conv_run(const PwFwdReq& req) {
+  PwFwdReq r = req;
+  if (r.ci_x == 0) r.ci_x = r.Ci;
+  if (!r.x2) r.c1 = 0;
+  pw::PwKey k{};
+  k.B = r.B; k.Ci = r.Ci; k.Co = r.Co; k.S = r.S; k.ci_x = r.ci_x; k.c1 = r.c1;
+  k.x_store = r.x_store; k.y_store = r.y_store; k.pack = r.pack; k.per_sample = r.per_sample;
+  k.operands = r.x && r.wp && r.bias;
+  k.y = r.y != nullptr; k.scale = r.in_scale != nullptr; k.res = r.res != nullptr; k.pool = r.pool != nullptr;
+  k.tf = r.tf.a && r.tf.b; k.tf_half = (r.tf.a == nullptr) != (r.tf.b == nullptr);
+  k.stats = r.stats != nullptr; k.gstat = r.gs.z != nullptr;
+  k.act = r.act; k.tf_act = r.tf.act; k.gs_act = r.gs.act;
+  if (const char* why = pw::check(k))
+    return fail(EAT_EINVAL, "%s: %s (B=%d Ci=%d Co=%d S=%d c1=%d ci_x=%d act=%d tf_act=%d g_act=%d)", r.who, why, r.B, r.Ci, r.Co,
+                r.S, r.c1, r.ci_x, r.act, r.tf.act, r.gs.act);
+  const pw::PwPlan p = pw::plan(k, eat_pw_stream_mode(-1));
+  if (p.lds_bytes > pw::kLdsLimit) return fail(EAT_EINVAL, "%s: LDS stage too large (%d B; planes of %d positions)", r.who, p.lds_bytes, r.S);
+  switch (p.route) {
+    case pw::Route::none: return 1;
+    case pw::Route::generic: return pw_generic_launch(r, p);
+    case pw::Route::lds_f32: return pw_lds_f32_launch(r, p);
+    case pw::Route::lds_b16: return pw_lds_b16_launch(r, p);
+    default: return pw_stream_launch(r, p);
+  }
+}
+
+}  // namespace eat
 
 extern "C" int eat_pw_conv_fwd(const float* x, const float* wp, const float* bias, const float* in_scale,
                                const float* res, float* y, float* pool, int B, int Ci, int Co, int S, int act,
                                eat_stream_t stream) {
   eat::clear_stale_error();
-  return pw_dispatch(x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, act, false, (hipStream_t)stream);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = act;
+  r.x = x; r.wp = wp; r.bias = bias; r.in_scale = in_scale; r.res = res; r.y = y; r.pool = pool;
+  return eat::pw_conv_run(r);
 }
 
 // Train-mode project conv (models/mn/block_types.py:167-171 after :150-162): the conv input is
@@ -448,14 +440,12 @@ extern "C" int eat_pw_conv_tf_fwd(const float* x, const float* tf_a, const float
                                   int Ci, int Co, int S, int act, eat_stream_t stream) {
   eat::clear_stale_error();
   if (!tf_a || !tf_b) return eat::fail(EAT_EINVAL, "eat_pw_conv_tf_fwd: tf_a and tf_b are required");
-  if (tf_act < 0 || tf_act > 2 || act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_tf_fwd: bad activation code");
-  if (Ci % 8 != 0 || S % 4 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_tf_fwd: needs Ci %% 8 == 0 and S %% 4 == 0 (Ci=%d, S=%d)", Ci, S);
-  if (B < 1 || Co < 1) return eat::fail(EAT_EINVAL, "eat_pw_conv_tf_fwd: bad shape");
-  if (wmode == 0)
-    return pw_dispatch(x, reinterpret_cast<const float*>(wp), bias, in_scale, res, y, nullptr, B, Ci, Co, S, act, false,
-                       (hipStream_t)stream, PwTf{tf_a, tf_b, tf_act});
-  return eat::pw_conv_bf16_tf(x, tf_a, tf_b, tf_act, wp, bias, in_scale, res, y, B, Ci, Co, S, act, wmode == 2 ? 1 : 0,
-                              (hipStream_t)stream);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_tf_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = act;
+  r.x = x; r.wp = wp; r.pack = eat::pw::pack_of(wmode); r.bias = bias; r.tf = eat::InTf{tf_a, tf_b, tf_act};
+  r.in_scale = in_scale; r.res = res; r.y = y;
+  return eat::pw_conv_run(r);
 }
 
 // 1x1 conv over the channels of TWO tensors of the same (B, *, S) geometry: y = W [x1 ; x2] + bias (+ res), W = (Co,
@@ -465,19 +455,23 @@ extern "C" int eat_pw_conv_cat_fwd(const float* x1, int C1, const float* x2, int
                                    const float* bias, const float* res, float* y, int B, int Co, int S, int act,
                                    eat_stream_t stream) {
   eat::clear_stale_error();
-  if (!x1 || !x2 || C1 < 4 || C2 < 4 || C1 % 4 || C2 % 4 || S % 4)
-    return eat::fail(EAT_EINVAL, "eat_pw_conv_cat_fwd: needs C1, C2, S multiples of 4 (C1=%d, C2=%d, S=%d)", C1, C2, S);
-  if (act < 0 || act > 2 || B < 1 || Co < 1) return eat::fail(EAT_EINVAL, "eat_pw_conv_cat_fwd: bad arguments");
-  if (wmode == 0)
-    return pw_dispatch(x1, reinterpret_cast<const float*>(wp), bias, nullptr, res, y, nullptr, B, C1 + C2, Co, S, act, false,
-                       (hipStream_t)stream, PwTf{nullptr, nullptr, 0}, x2, C1);
-  return eat::pw_conv_bf16_cat(x1, C1, x2, C2, wp, bias, res, y, B, Co, S, act, wmode == 2 ? 1 : 0, (hipStream_t)stream);
+  if (!x1 || !x2 || C1 < 4 || C2 < 4)
+    return eat::fail(EAT_EINVAL, "eat_pw_conv_cat_fwd: needs two sources of at least 4 channels (C1=%d, C2=%d)", C1, C2);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_cat_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = C1 + C2; r.Co = Co; r.S = S; r.act = act;
+  r.x = x1; r.x2 = x2; r.c1 = C1; r.wp = wp; r.pack = eat::pw::pack_of(wmode); r.bias = bias; r.res = res; r.y = y;
+  return eat::pw_conv_run(r);
 }
 
 extern "C" int eat_pw_conv_dyn_fwd(const float* x, const float* wp_b, const float* bias, const float* res, float* y,
                                    int B, int Ci, int Co, int S, int act, eat_stream_t stream) {
   eat::clear_stale_error();
-  return pw_dispatch(x, wp_b, bias, nullptr, res, y, nullptr, B, Ci, Co, S, act, true, (hipStream_t)stream);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_dyn_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = act;
+  r.x = x; r.wp = wp_b; r.per_sample = true; r.bias = bias; r.res = res; r.y = y;
+  return eat::pw_conv_run(r);
 }
 
 // Train-mode 1x1 conv (no bias / activation / residual: z = W x) with the partial sums of z for the BatchNorm that follows
@@ -485,23 +479,19 @@ extern "C" int eat_pw_conv_dyn_fwd(const float* x, const float* wp_b, const floa
 // pack per sample (eat_dyn_pw_pack / eat_dyn_pw_pack_bf16); tf_a / tf_b / tf_act, in_scale: as eat_pw_conv_tf_fwd (NULL:
 // none).  part: eat_pw_conv_stat_tiles(B, S, per_sample) * 2 * Co floats, layout [tile][2][Co] = eat_bn_finalize_partials
 // with outer = tiles, inner = 1.  Returns 1 (and launches nothing) for geometries without the epilogue (S % 4 != 0).
-extern "C" int eat_pw_conv_stat_tiles(int B, int S, int per_sample) {
-  return per_sample ? B * ((S + kTileN - 1) / kTileN) : (int)(((long long)B * S + kTileN - 1) / kTileN);
-}
+extern "C" int eat_pw_conv_stat_tiles(int B, int S, int per_sample) { return eat::pw::stat_tiles(B, S, per_sample != 0); }
 
 extern "C" int eat_pw_conv_stats_fwd(const float* x, const void* wp, int wmode, int per_sample, const float* tf_a,
                                      const float* tf_b, int tf_act, const float* in_scale, const float* zero_bias, float* y,
                                      float* part, int B, int Ci, int Co, int S, eat_stream_t stream) {
   eat::clear_stale_error();
-  if (!x || !wp || !y || !part || !zero_bias) return eat::fail(EAT_EINVAL, "eat_pw_conv_stats_fwd: missing operand");
-  if ((tf_a == nullptr) != (tf_b == nullptr) || tf_act < 0 || tf_act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_stats_fwd: bad transform");
-  if (tf_a && Ci % 8 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_stats_fwd: the on-load transform needs Ci %% 8 == 0");
-  if (S % 4 != 0) return 1;
-  if (wmode == 0)
-    return pw_dispatch(x, reinterpret_cast<const float*>(wp), zero_bias, in_scale, nullptr, y, nullptr, B, Ci, Co, S, EAT_ACT_NONE,
-                       per_sample != 0, (hipStream_t)stream, PwTf{tf_a, tf_b, tf_act}, nullptr, 0, part);
-  return eat::pw_conv_bf16_stats(x, wp, wmode == 2 ? 1 : 0, per_sample, tf_a, tf_b, tf_act, in_scale, zero_bias, y, part, B, Ci,
-                                 Co, S, (hipStream_t)stream);
+  if (!y || !part) return eat::fail(EAT_EINVAL, "eat_pw_conv_stats_fwd: missing operand");
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_stats_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = EAT_ACT_NONE;
+  r.x = x; r.wp = wp; r.pack = eat::pw::pack_of(wmode); r.per_sample = per_sample != 0; r.bias = zero_bias;
+  r.tf = eat::InTf{tf_a, tf_b, tf_act}; r.in_scale = in_scale; r.y = y; r.stats = part;
+  return eat::pw_conv_run(r);
 }
 
 // Data-gradient GEMM of a project conv (y = dxs = W^T dz_p; wp = the transposed pack, wmode as above, no per-sample form)
@@ -512,15 +502,14 @@ extern "C" int eat_pw_conv_gstats_fwd(const float* x, const void* wp, int wmode,
                                       const float* gz, const float* g_a, const float* g_b, int g_act, float* part, int B,
                                       int Ci, int Co, int S, eat_stream_t stream) {
   eat::clear_stale_error();
-  if (!x || !wp || !y || !part || !zero_bias || !gz || !g_a || !g_b)
-    return eat::fail(EAT_EINVAL, "eat_pw_conv_gstats_fwd: missing operand");
-  if (g_act < 0 || g_act > 2 || (wmode != 0 && wmode != 2)) return eat::fail(EAT_EINVAL, "eat_pw_conv_gstats_fwd: bad act / wmode");
-  if (S % 4 != 0) return 1;
-  const eat::PwGStat gs{gz, g_a, g_b, g_act};
-  if (wmode == 0)
-    return pw_dispatch(x, reinterpret_cast<const float*>(wp), zero_bias, nullptr, nullptr, y, nullptr, B, Ci, Co, S, EAT_ACT_NONE,
-                       false, (hipStream_t)stream, PwTf{nullptr, nullptr, 0}, nullptr, 0, part, gs);
-  return eat::pw_conv_bf16_stats(x, wp, 1, 0, nullptr, nullptr, 0, nullptr, zero_bias, y, part, B, Ci, Co, S, (hipStream_t)stream, gs);
+  if (!y || !part || !gz || !g_a || !g_b) return eat::fail(EAT_EINVAL, "eat_pw_conv_gstats_fwd: missing operand");
+  if (wmode != 0 && wmode != 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_gstats_fwd: no plain-bf16 pack (wmode=%d)", wmode);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_gstats_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = EAT_ACT_NONE;
+  r.x = x; r.wp = wp; r.pack = eat::pw::pack_of(wmode); r.bias = zero_bias; r.y = y; r.stats = part;
+  r.gs = eat::PwGStat{gz, g_a, g_b, g_act};
+  return eat::pw_conv_run(r);
 }
 
 extern "C" int eat_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int K, int N,

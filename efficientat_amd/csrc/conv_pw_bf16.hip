@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void pw_prepack_multi_kernel(const PrepackDesc
 // TF: the conv input is act_in(tf_a[k] * x + tf_b[k]) evaluated on the way from LDS to the MFMA operand (training: the
 // BatchNorm + activation of the depthwise conv fused into the project conv - the activated tensor is never written;
 // models/mn/block_types.py:150-171 under model.train()); the SE scale (in_scale) multiplies the transformed value.
-struct PwTf { const float* a; const float* b; int act; };
+using PwTf = eat::InTf;
 
 // XT / YT: storage type of x / y (act_io.h).  XT = bf16 (the wide tensors of the bf16-storage training plan): a chunk is
 // staged as 32 rows x 512 B (one LDS-DMA instruction = two rows), a lane reads its 4 columns of 8 rows as 8-byte pieces and
@@ -323,60 +323,29 @@ __global__ __launch_bounds__(256, 2) void pw_conv_bf16_kernel(
   }
 }
 
-
-template <int MTW, int NPROD, typename XT = float, typename YT = float>
-int launch(hipStream_t s, const XT* x, const __bf16* wp, const float* bias, const float* in_scale, const float* res,
-           YT* y, float* pool, int B, int Ci, int Co, int S, int MT, int MC, int act, int ci_x, PwTf tf,
-           const float* x2, int c1, bool per_sample, float* stats, eat::PwGStat gs) {
-  constexpr bool XB = eat::Io<XT>::kBf;
-  const long long N = (long long)B * S;
-  if (N > 0x7fff0000LL) return eat::fail(EAT_EINVAL, "eat_pw_conv_bf16_fwd: B*S = %lld exceeds the 32-bit column index", N);
-  const int tps = per_sample ? (S + kTileN - 1) / kTileN : 0;
-  const int n_tiles = per_sample ? B * tps : (int)((N + kTileN - 1) / kTileN);
-  int NS = kTileN / S + 2;
-  if (NS > B) NS = B;
-  if (!in_scale) NS = 0;
-  const int sc_bytes = in_scale ? ((kKC * NS + 63) / 64) * 256 : 0;
-  constexpr int NP2 = NPROD == 3 ? 2 : 1;
-  const long long wp_bstride = (long long)((Ci + kKC - 1) / kKC) * MT * NP2 * 512;
-  // Two LDS stages (chunk c+1 in flight under the MFMAs of chunk c) when two such blocks fit a CU or when
-  // there are not enough blocks for two per CU anyway; otherwise ONE stage, so that a second resident
-  // block hides the load latency and the store phase instead (measured on MI355X, B=256: 80->480 95 vs
-  // 135 us, 160->960 48 vs 83 us; the K-heavy 960->160 with 256 blocks keeps two stages: 45 vs 56 us).
-  const size_t stage = (size_t)(MTW * NP2 * 1024 + kKC * kTileN * ((XB && !x2) ? 2 : 4) + sc_bytes);
-  const int n_blocks = ((n_tiles + 7) / 8 * 8) * MC;
-  const int n_stages = (2 * stage <= 78 * 1024 || n_blocks < 2 * 256) ? 2 : 1;
-  const size_t smem = n_stages * stage;
-  // (the on-load transform exists for fp32 -> fp32 and bf16 -> fp32 / bf16: the project conv of the training plans)
-  constexpr bool TFOK = std::is_same<YT, float>::value || XB;
-  if (tf.a && !TFOK) return eat::fail(EAT_EINVAL, "eat_pw_conv: the on-load transform needs an fp32 output or a bf16 input");
-  auto kern = (tf.a && TFOK) ? (n_stages == 2 ? pw_conv_bf16_kernel<MTW, NPROD, 2, TFOK, XT, YT> : pw_conv_bf16_kernel<MTW, NPROD, 1, TFOK, XT, YT>)
-                   : (n_stages == 2 ? pw_conv_bf16_kernel<MTW, NPROD, 2, false, XT, YT> : pw_conv_bf16_kernel<MTW, NPROD, 1, false, XT, YT>);
-  if (smem > 160 * 1024) return eat::fail(EAT_EINVAL, "eat_pw_conv_bf16_fwd: LDS stage too large (%zu B; planes of %d positions)", smem, S);
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return eat::fail(EAT_ELAUNCH, "eat_pw_conv_bf16_fwd: cannot reserve %zu B of LDS: %s", smem, hipGetErrorString(e));
+template <int MTW, int NPROD, typename XT, typename YT>
+int launch(const eat::PwFwdReq& r, const eat::pw::PwPlan& p) {
+  // (the on-load transform exists for fp32 -> fp32 and bf16 -> fp32 / bf16: pw_fwd_plan.h refuses the rest)
+  constexpr bool TFOK = std::is_same<YT, float>::value || eat::Io<XT>::kBf;
+  auto kern = (p.tf && TFOK) ? (p.n_stages == 2 ? pw_conv_bf16_kernel<MTW, NPROD, 2, TFOK, XT, YT> : pw_conv_bf16_kernel<MTW, NPROD, 1, TFOK, XT, YT>)
+                             : (p.n_stages == 2 ? pw_conv_bf16_kernel<MTW, NPROD, 2, false, XT, YT> : pw_conv_bf16_kernel<MTW, NPROD, 1, false, XT, YT>);
+  if (p.lds_bytes > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes);
+    if (e != hipSuccess) return eat::fail(EAT_ELAUNCH, "%s: cannot reserve %d B of LDS: %s", r.who, p.lds_bytes, hipGetErrorString(e));
   }
-  const int tiles8 = (n_tiles + 7) / 8 * 8;
-  hipLaunchKernelGGL(kern, dim3(tiles8 * MC), dim3(256), smem, s, x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, MT, MC,
-                     n_tiles, NS, act, sc_bytes, ci_x, tf, x2, c1, tps, wp_bstride, stats, gs);
-  return eat::check_launch("eat_pw_conv_bf16_fwd");
+  hipLaunchKernelGGL(kern, dim3(p.grid[0]), dim3(256), p.lds_bytes, r.stream, reinterpret_cast<const XT*>(r.x),
+                     reinterpret_cast<const __bf16*>(r.wp), r.bias, r.in_scale, r.res, reinterpret_cast<YT*>(r.y), r.pool, r.B, r.Ci,
+                     r.Co, r.S, p.MT, p.MC, p.n_tiles, p.NS, r.act, p.sc_bytes, r.ci_x, r.tf, r.x2, r.c1, p.tps, p.wp_bstride,
+                     r.stats, r.gs);
+  return eat::check_launch(r.who);
 }
 
-template <int NPROD, typename XT = float, typename YT = float>
-int dispatch(hipStream_t s, const XT* x, const __bf16* wp, const float* bias, const float* in_scale, const float* res,
-             YT* y, float* pool, int B, int Ci, int Co, int S, int act, int ci_x, PwTf tf = PwTf{nullptr, nullptr, 0},
-             const float* x2 = nullptr, int c1 = 0, bool per_sample = false, float* stats = nullptr,
-             eat::PwGStat gs = eat::PwGStat{nullptr, nullptr, nullptr, 0}) {
-  const int MT = (Co + 15) / 16;
-  // (K-concat launches with few output rows - 128 x 1920 -> 320 @ 4x32: 192 blocks of 240 chunks - do NOT gain from more,
-  // smaller row chunks: every block re-streams its x tile once per bank through L2, 425 -> 480 us with 448 blocks)
-  const int MC = (MT + 7) / 8;
-  const int mtw = (MT + MC - 1) / MC;
-#define EAT_CASE(n) case n: return launch<n, NPROD, XT, YT>(s, x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, MT, (MT + n - 1) / n, act, ci_x, tf, x2, c1, per_sample, stats, gs);
-  switch (mtw) {
+template <int NPROD, typename XT, typename YT>
+int launch_rows(const eat::PwFwdReq& r, const eat::pw::PwPlan& p) {
+#define EAT_CASE(n) case n: return launch<n, NPROD, XT, YT>(r, p);
+  switch (p.mtw) {
     EAT_CASE(1) EAT_CASE(2) EAT_CASE(3) EAT_CASE(4) EAT_CASE(5) EAT_CASE(6) EAT_CASE(7) EAT_CASE(8)
-    default: return eat::fail(EAT_EINVAL, "eat_pw_conv_bf16_fwd: internal tiling error");
+    default: return eat::fail(EAT_EINVAL, "%s: internal tiling error", r.who);
   }
 #undef EAT_CASE
 }
@@ -411,72 +380,37 @@ extern "C" int eat_pw_prepack_multi(const void* table, int n, int max_threads, e
   return eat::check_launch("eat_pw_prepack_multi");
 }
 
+// the kernel's instances: split or plain operands on fp32 tensors, plain operands where x and / or y is stored in bf16
+int eat::pw_lds_b16_launch(const PwFwdReq& r, const pw::PwPlan& p) {
+  const bool xb = r.x_store == pw::Store::b16, yb = r.y_store == pw::Store::b16;
+  if (!xb && !yb) return p.nprod == 3 ? launch_rows<3, float, float>(r, p) : launch_rows<1, float, float>(r, p);
+  if (!xb) return launch_rows<1, float, eat::bf16_t>(r, p);
+  return yb ? launch_rows<1, eat::bf16_t, eat::bf16_t>(r, p) : launch_rows<1, eat::bf16_t, float>(r, p);
+}
+
 extern "C" int eat_pw_conv_bf16_fwd(const float* x, const void* wp, const float* bias, const float* in_scale,
                                     const float* res, float* y, float* pool, int B, int Ci, int Co, int S, int act,
                                     int split, eat_stream_t stream) {
   eat::clear_stale_error();
-  if (Ci % 4 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_bf16_fwd: Ci=%d must be a multiple of 4", Ci);
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_bf16_fwd: bad act %d", act);
-  if (B < 1 || Co < 1 || S < 1) return eat::fail(EAT_EINVAL, "eat_pw_conv_bf16_fwd: bad shape");
-  const __bf16* w16 = reinterpret_cast<const __bf16*>(wp);
-  hipStream_t s = (hipStream_t)stream;
-  if (S % 4 != 0)      // planes that do not start on 16-byte boundaries: plain 4-byte kernel on the same packs
-    return eat::pw_conv_generic(x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, act, split ? 2 : 1, 0, s);
-  {
-    const int rc = eat::pw_stream_try(x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, act, split, Ci, s);
-    if (rc != 1) return rc;
-  }
-  return split ? dispatch<3>(s, x, w16, bias, in_scale, res, y, pool, B, Ci, Co, S, act, Ci)
-               : dispatch<1>(s, x, w16, bias, in_scale, res, y, pool, B, Ci, Co, S, act, Ci);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_bf16_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = act;
+  r.x = x; r.wp = wp; r.pack = split ? eat::pw::Pack::b16x2 : eat::pw::Pack::b16; r.bias = bias; r.in_scale = in_scale;
+  r.res = res; r.y = y; r.pool = pool;
+  return eat::pw_conv_run(r);
 }
-
-// 1x1 conv whose input is act_in(tf_a[k] x + tf_b[k]) [* in_scale[b,k]] evaluated on load (see PwTf above)
-namespace eat {
-int pw_conv_bf16_tf(const float* x, const float* tf_a, const float* tf_b, int tf_act, const void* wp, const float* bias,
-                    const float* in_scale, const float* res, float* y, int B, int Ci, int Co, int S, int act, int split,
-                    hipStream_t s) {
-  const PwTf tf{tf_a, tf_b, tf_act};
-  const __bf16* w16 = reinterpret_cast<const __bf16*>(wp);
-  return split ? dispatch<3>(s, x, w16, bias, in_scale, res, y, nullptr, B, Ci, Co, S, act, Ci, tf)
-               : dispatch<1>(s, x, w16, bias, in_scale, res, y, nullptr, B, Ci, Co, S, act, Ci, tf);
-}
-}  // namespace eat
-
-// train-mode conv z = W x with the statistics epilogue (eat_pw_conv_stats_fwd, conv_pw.hip)
-namespace eat {
-int pw_conv_bf16_stats(const float* x, const void* wp, int split, int per_sample, const float* tf_a, const float* tf_b,
-                       int tf_act, const float* in_scale, const float* zero_bias, float* y, float* part, int B, int Ci, int Co,
-                       int S, hipStream_t s, PwGStat gs) {
-  const PwTf tf{tf_a, tf_b, tf_act};
-  const __bf16* w16 = reinterpret_cast<const __bf16*>(wp);
-  return split ? dispatch<3>(s, x, w16, zero_bias, in_scale, nullptr, y, nullptr, B, Ci, Co, S, EAT_ACT_NONE, Ci, tf, nullptr, 0,
-                             per_sample != 0, part, gs)
-               : dispatch<1>(s, x, w16, zero_bias, in_scale, nullptr, y, nullptr, B, Ci, Co, S, EAT_ACT_NONE, Ci, tf, nullptr, 0,
-                             per_sample != 0, part, gs);
-}
-}  // namespace eat
-
-// 1x1 conv over the concatenated channels of two tensors (see the kernel's x2 / c1)
-namespace eat {
-int pw_conv_bf16_cat(const float* x1, int c1, const float* x2, int c2, const void* wp, const float* bias, const float* res,
-                     float* y, int B, int Co, int S, int act, int split, hipStream_t s) {
-  const __bf16* w16 = reinterpret_cast<const __bf16*>(wp);
-  const PwTf none{nullptr, nullptr, 0};
-  return split ? dispatch<3>(s, x1, w16, bias, nullptr, res, y, nullptr, B, c1 + c2, Co, S, act, c1 + c2, none, x2, c1)
-               : dispatch<1>(s, x1, w16, bias, nullptr, res, y, nullptr, B, c1 + c2, Co, S, act, c1 + c2, none, x2, c1);
-}
-}  // namespace eat
 
 // DyMN dynamic 1x1 conv with per-sample weights on split bf16 operands: wp_b = eat_dyn_pw_pack_bf16's (B, KK*MT*2*512)
 // hi / lo fragments (models/dymn/dy_block.py:111-127; the fp32-fragment form is eat_pw_conv_dyn_fwd).  Ci % 4 == 0, S % 4 == 0.
 extern "C" int eat_pw_conv_dyn_bf16_fwd(const float* x, const void* wp_b, const float* bias, const float* res, float* y,
                                         int B, int Ci, int Co, int S, int act, eat_stream_t stream) {
   eat::clear_stale_error();
-  if (Ci % 4 != 0 || S % 4 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_bf16_fwd: Ci=%d and S=%d must be multiples of 4", Ci, S);
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_bf16_fwd: bad act %d", act);
-  if (B < 1 || Co < 1 || !wp_b) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_bf16_fwd: bad arguments");
-  return dispatch<3>((hipStream_t)stream, x, reinterpret_cast<const __bf16*>(wp_b), bias, nullptr, res, y, nullptr, B, Ci, Co,
-                     S, act, Ci, PwTf{nullptr, nullptr, 0}, nullptr, 0, true);
+  if (S % 4 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_bf16_fwd: S=%d must be a multiple of 4", S);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_dyn_bf16_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = act;
+  r.x = x; r.wp = wp_b; r.pack = eat::pw::Pack::b16x2; r.per_sample = true; r.bias = bias; r.res = res; r.y = y;
+  return eat::pw_conv_run(r);
 }
 
 // DyMN dynamic 1x1 conv WITHOUT per-sample weights (models/dymn/dy_block.py:103-131):
@@ -487,17 +421,13 @@ extern "C" int eat_pw_conv_kcat_fwd(const float* x, const void* wp, const float*
                                     const float* res, float* y, int B, int Ci, int nbank, int Co, int S, int act,
                                     eat_stream_t stream) {
   eat::clear_stale_error();
-  if (Ci % 32 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_kcat_fwd: Ci=%d must be a multiple of 32", Ci);
-  if (S % 4 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_kcat_fwd: S=%d must be a multiple of 4", S);
-  if (nbank < 1 || B < 1 || Co < 1 || !att_scale) return eat::fail(EAT_EINVAL, "eat_pw_conv_kcat_fwd: bad arguments");
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_kcat_fwd: bad act %d", act);
-  {
-    const int rc = eat::pw_stream_try(x, wp, bias, att_scale, res, y, nullptr, B, nbank * Ci, Co, S, act, 1, Ci,
-                                      (hipStream_t)stream);
-    if (rc != 1) return rc;
-  }
-  return dispatch<3>((hipStream_t)stream, x, reinterpret_cast<const __bf16*>(wp), bias, att_scale, res, y, nullptr, B,
-                     nbank * Ci, Co, S, act, Ci);
+  if (Ci < 32 || Ci % 32 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_kcat_fwd: Ci=%d must be a multiple of 32", Ci);
+  if (nbank < 1 || !att_scale) return eat::fail(EAT_EINVAL, "eat_pw_conv_kcat_fwd: needs nbank >= 1 (nbank=%d) and att_scale", nbank);
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_kcat_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = nbank * Ci; r.Co = Co; r.S = S; r.act = act; r.ci_x = Ci;
+  r.x = x; r.wp = wp; r.pack = eat::pw::Pack::b16x2; r.bias = bias; r.in_scale = att_scale; r.res = res; r.y = y;
+  return eat::pw_conv_run(r);
 }
 
 // ---- 1x1 conv of the bf16-STORAGE training plan (act_io.h; BASELINE configs[2], the reference's 16-bit mixed precision,
@@ -515,38 +445,25 @@ extern "C" int eat_pw_conv_b16_fwd(const void* x, int x_b16, const float* x2, in
                                    void* y, int y_b16, float* stats_part, const void* gz, const float* g_a, const float* g_b,
                                    int g_act, int B, int Ci, int Co, int S, int act, eat_stream_t stream) {
   eat::clear_stale_error();
-  if (!x || !wp || !bias || !y) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: missing operand");
-  if (B < 1 || Co < 1 || Ci < 4 || Ci % 4 != 0 || S < 8 || S % 8 != 0)
-    return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: Ci=%d must be a multiple of 4 and S=%d a multiple of 8", Ci, S);
-  if (act < 0 || act > 2 || tf_act < 0 || tf_act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: bad act");
-  if ((tf_a == nullptr) != (tf_b == nullptr)) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: tf_a and tf_b go together");
-  if (tf_a && Ci % 8 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: the on-load transform needs Ci %% 8 == 0 (Ci=%d)", Ci);
-  const __bf16* w16 = reinterpret_cast<const __bf16*>(wp);
-  const PwTf tf{tf_a, tf_b, tf_act};
-  hipStream_t s = (hipStream_t)stream;
-  if (!x_b16 && y_b16) {
-    if (x2 || tf_a || in_scale || res || stats_part)
-      return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: a bf16 output takes a plain conv only");
-    return dispatch<1, float, eat::bf16_t>(s, reinterpret_cast<const float*>(x), w16, bias, nullptr, nullptr,
-                                           reinterpret_cast<eat::bf16_t*>(y), nullptr, B, Ci, Co, S, act, Ci);
-  }
-  if (x_b16 && !y_b16) {
-    if (x2 && (c1 < 32 || c1 % 32 != 0 || c1 >= Ci || tf_a || in_scale || stats_part))
-      return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: two-source form needs c1 %% 32 == 0 (c1=%d) and no transform / scale / statistics", c1);
-    return dispatch<1, eat::bf16_t, float>(s, reinterpret_cast<const eat::bf16_t*>(x), w16, bias, in_scale, res,
-                                           reinterpret_cast<float*>(y), nullptr, B, Ci, Co, S, act, Ci, tf, x2, c1, false,
-                                           stats_part);
-  }
-  if (gz && !(x_b16 && y_b16 && stats_part && g_a && g_b && g_act >= 0 && g_act <= 2 && !tf_a && !in_scale))
+  if (!y) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: missing operand");
+  if (S % 8 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: S=%d must be a multiple of 8", S);
+  if (!x_b16 && !y_b16) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: at least one of x / y is a bf16 tensor");
+  if (!x_b16 && (x2 || tf_a || in_scale || res || stats_part))
+    return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: a bf16 output of an fp32 input takes a plain conv only");
+  if (x_b16 && !y_b16 && x2 && (c1 < 32 || c1 >= Ci || tf_a || in_scale || stats_part))
+    return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: two-source form needs c1 %% 32 == 0 (c1=%d) and no transform / scale / statistics", c1);
+  if (x_b16 && y_b16 && (x2 || res)) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: bf16 -> bf16 takes no second source / residual");
+  // gz != NULL: stats_part receives the BatchNorm-backward partials of pw_epilogue_gstats (gz = the bf16 z_d) instead
+  if (x_b16 && y_b16 && gz && !(stats_part && g_a && g_b && !tf_a && !in_scale))
     return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: the BatchNorm-backward epilogue (gz) goes with a plain bf16 -> bf16 conv and stats_part");
-  if (x_b16 && y_b16) {
-    if (x2 || res) return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: bf16 -> bf16 takes no second source / residual");
-    // gz != NULL: stats_part receives the BatchNorm-backward partials of pw_epilogue_gstats (gz = the bf16 z_d) instead
-    return dispatch<1, eat::bf16_t, eat::bf16_t>(s, reinterpret_cast<const eat::bf16_t*>(x), w16, bias, in_scale, nullptr,
-                                                 reinterpret_cast<eat::bf16_t*>(y), nullptr, B, Ci, Co, S, act, Ci, tf, nullptr, 0,
-                                                 false, stats_part, eat::PwGStat{gz, g_a, g_b, g_act});
-  }
-  return eat::fail(EAT_EINVAL, "eat_pw_conv_b16_fwd: at least one of x / y is a bf16 tensor");
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_b16_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = act;
+  r.x = x; r.x_store = x_b16 ? eat::pw::Store::b16 : eat::pw::Store::f32; r.x2 = x2; r.c1 = c1;
+  r.wp = wp; r.pack = eat::pw::Pack::b16; r.bias = bias; r.tf = eat::InTf{tf_a, tf_b, tf_act}; r.in_scale = in_scale; r.res = res;
+  r.y = y; r.y_store = y_b16 ? eat::pw::Store::b16 : eat::pw::Store::f32; r.stats = stats_part;
+  if (x_b16 && y_b16 && gz) r.gs = eat::PwGStat{gz, g_a, g_b, g_act};
+  return eat::pw_conv_run(r);
 }
 
 // ---- per-sample-weight 1x1 conv of the bf16-STORAGE plan for DyMN (models/dymn/dy_block.py:103-131 with a 1x1 kernel, under the
@@ -559,21 +476,14 @@ extern "C" int eat_pw_conv_b16_fwd(const void* x, int x_b16, const float* x2, in
 extern "C" int eat_pw_conv_dyn_b16_fwd(const void* x, int x_b16, const void* wp_b, const float* bias, const float* res, void* y,
                                        int y_b16, float* stats_part, int B, int Ci, int Co, int S, int act, eat_stream_t stream) {
   eat::clear_stale_error();
-  if (!x || !wp_b || !bias || !y) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: missing operand");
-  if (B < 1 || Co < 1 || Ci < 4 || Ci % 4 != 0 || S < 8 || S % 8 != 0)
-    return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: Ci=%d must be a multiple of 4 and S=%d a multiple of 8", Ci, S);
-  if (act < 0 || act > 2) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: bad act %d", act);
+  if (!y) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: missing operand");
+  if (S % 8 != 0) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: S=%d must be a multiple of 8", S);
   if ((x_b16 != 0) == (y_b16 != 0)) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: exactly one of x / y is the bf16 (wide) tensor");
-  const __bf16* w16 = reinterpret_cast<const __bf16*>(wp_b);
-  const PwTf none{nullptr, nullptr, 0};
-  hipStream_t s = (hipStream_t)stream;
-  if (y_b16) {
-    if (res) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: a bf16 output takes no residual");
-    return dispatch<1, float, eat::bf16_t>(s, reinterpret_cast<const float*>(x), w16, bias, nullptr, nullptr,
-                                           reinterpret_cast<eat::bf16_t*>(y), nullptr, B, Ci, Co, S, act, Ci, none, nullptr, 0, true,
-                                           stats_part);
-  }
-  return dispatch<1, eat::bf16_t, float>(s, reinterpret_cast<const eat::bf16_t*>(x), w16, bias, nullptr, res,
-                                         reinterpret_cast<float*>(y), nullptr, B, Ci, Co, S, act, Ci, none, nullptr, 0, true,
-                                         stats_part);
+  if (y_b16 && res) return eat::fail(EAT_EINVAL, "eat_pw_conv_dyn_b16_fwd: a bf16 output takes no residual");
+  eat::PwFwdReq r{};
+  r.who = "eat_pw_conv_dyn_b16_fwd"; r.stream = (hipStream_t)stream;
+  r.B = B; r.Ci = Ci; r.Co = Co; r.S = S; r.act = act;
+  r.x = x; r.x_store = x_b16 ? eat::pw::Store::b16 : eat::pw::Store::f32; r.wp = wp_b; r.pack = eat::pw::Pack::b16; r.per_sample = true;
+  r.bias = bias; r.res = res; r.y = y; r.y_store = y_b16 ? eat::pw::Store::b16 : eat::pw::Store::f32; r.stats = stats_part;
+  return eat::pw_conv_run(r);
 }

@@ -66,21 +66,12 @@ __global__ __launch_bounds__(64) void pw_conv_generic_kernel(
 
 }  // namespace
 
-namespace eat {
-
-// wmode: 0 = fp32 pack, 1 = bf16 pack, 2 = bf16 hi/lo pack; wp_bstride_bytes != 0: per-sample weights
-int pw_conv_generic(const float* x, const void* wp, const float* bias, const float* in_scale, const float* res, float* y,
-                    float* pool, int B, int Ci, int Co, int S, int act, int wmode, long long wp_bstride_bytes,
-                    hipStream_t s) {
-  const int MT = (Co + 15) / 16;
-  dim3 grid((S + 63) / 64, MT, B);
-  if (wmode == 0)
-    hipLaunchKernelGGL(pw_conv_generic_kernel<0>, grid, dim3(64), 0, s, x, wp, bias, in_scale, res, y, pool, Ci, Co, S, MT, act, wp_bstride_bytes);
-  else if (wmode == 1)
-    hipLaunchKernelGGL(pw_conv_generic_kernel<1>, grid, dim3(64), 0, s, x, wp, bias, in_scale, res, y, pool, Ci, Co, S, MT, act, wp_bstride_bytes);
-  else
-    hipLaunchKernelGGL(pw_conv_generic_kernel<2>, grid, dim3(64), 0, s, x, wp, bias, in_scale, res, y, pool, Ci, Co, S, MT, act, wp_bstride_bytes);
-  return check_launch("eat_pw_conv_fwd (generic plane size)");
+// one launch per pack format; per-sample weights: the plan's stride between two samples' packs, in bytes here
+int eat::pw_generic_launch(const PwFwdReq& r, const pw::PwPlan& p) {
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+  const long long wp_bstride_bytes = p.wp_bstride * (r.pack == pw::Pack::f32 ? 4 : 2);
+  auto kern = r.pack == pw::Pack::f32 ? pw_conv_generic_kernel<0> : r.pack == pw::Pack::b16 ? pw_conv_generic_kernel<1> : pw_conv_generic_kernel<2>;
+  hipLaunchKernelGGL(kern, grid, dim3(64), 0, r.stream, reinterpret_cast<const float*>(r.x), r.wp, r.bias, r.in_scale, r.res,
+                     reinterpret_cast<float*>(r.y), r.pool, r.Ci, r.Co, r.S, p.MT, r.act, wp_bstride_bytes);
+  return check_launch(r.who);
 }
-
-}  // namespace eat

@@ -22,7 +22,7 @@
 //                      into registers) right after chunk c has been converted, the A fragments of chunk c+1 replace
 //                      those of chunk c as the MFMAs consume them.  Epilogue = pw_epilogue.h.
 //
-// Both are reached through eat_pw_conv_bf16_fwd (conv_pw_bf16.hip) - `EAT_PW_STREAM` selects them (see pw_stream_try).
+// Both are reached through eat_pw_conv_bf16_fwd (conv_pw_bf16.hip) - `EAT_PW_STREAM` selects them (pw_fwd_plan.h).
 #include <atomic>
 #include <cstdlib>
 #include "eat_common.h"
@@ -274,72 +274,52 @@ __global__ __launch_bounds__(256, (MTW <= 2 ? 3 : 2)) void pw_kstream_kernel(
 }
 
 template <int NCH, int NPROD>
-int launch_expand(hipStream_t s, const float* x, const void* wp, const float* bias, float* y, int B, int Ci, int Co, int S,
-                  int act) {
-  const int MT = (Co + 15) / 16;
-  const int n_tiles = (int)(((long long)B * S + kTileN - 1) / kTileN);
-  // all rows in one block when the column tiles alone fill the chip twice; otherwise split the rows (x is re-read
-  // from the XCD's L2 by the other m-chunks)
-  int MC = 1;
-  while (n_tiles * MC < 448 && (MT + 2 * MC - 1) / (2 * MC) >= 4) MC *= 2;
-  while ((MT + MC - 1) / MC > 64) ++MC;                      // s_bias holds 64 m-tiles
-  const int MTB = (MT + MC - 1) / MC;
-  MC = (MT + MTB - 1) / MTB;
-  const int tiles8 = (n_tiles + 7) / 8 * 8;
-  auto kern = act == EAT_ACT_NONE ? pw_expand_kernel<NCH, NPROD, true> : pw_expand_kernel<NCH, NPROD, false>;
-  hipLaunchKernelGGL(kern, dim3(tiles8 * MC), dim3(256), 0, s, x, reinterpret_cast<const bf16x8*>(wp), bias, y, B, Ci,
-                     Co, S, MT, MTB, MC, n_tiles, act);
-  return eat::check_launch("eat_pw_conv_bf16_fwd (expand)");
+int launch_expand(const eat::PwFwdReq& r, const eat::pw::PwPlan& p) {
+  auto kern = r.act == EAT_ACT_NONE ? pw_expand_kernel<NCH, NPROD, true> : pw_expand_kernel<NCH, NPROD, false>;
+  hipLaunchKernelGGL(kern, dim3(p.grid[0]), dim3(256), 0, r.stream, reinterpret_cast<const float*>(r.x),
+                     reinterpret_cast<const bf16x8*>(r.wp), r.bias, reinterpret_cast<float*>(r.y), r.B, r.Ci, r.Co, r.S, p.MT, p.mtw,
+                     p.MC, p.n_tiles, r.act);
+  return eat::check_launch(r.who);
 }
 
 template <int MTW, int NPROD>
-int launch_kstream(hipStream_t s, const float* x, const void* wp, const float* bias, const float* in_scale,
-                   const float* res, float* y, float* pool, int B, int Ci, int Co, int S, int MT, int act, int ci_x) {
-  const int MC = (MT + MTW - 1) / MTW;
-  const int n_tiles = (int)(((long long)B * S + kTileN - 1) / kTileN);
-  const int tiles8 = (n_tiles + 7) / 8 * 8;
-  auto kern = in_scale ? pw_kstream_kernel<MTW, NPROD, true> : pw_kstream_kernel<MTW, NPROD, false>;
-  hipLaunchKernelGGL(kern, dim3(tiles8 * MC), dim3(256), 0, s, x, reinterpret_cast<const bf16x8*>(wp), bias, in_scale,
-                     res, y, pool, B, Ci, Co, S, MT, MC, n_tiles, act, ci_x);
-  return eat::check_launch("eat_pw_conv_bf16_fwd (kstream)");
+int launch_kstream(const eat::PwFwdReq& r, const eat::pw::PwPlan& p) {
+  auto kern = r.in_scale ? pw_kstream_kernel<MTW, NPROD, true> : pw_kstream_kernel<MTW, NPROD, false>;
+  hipLaunchKernelGGL(kern, dim3(p.grid[0]), dim3(256), 0, r.stream, reinterpret_cast<const float*>(r.x),
+                     reinterpret_cast<const bf16x8*>(r.wp), r.bias, r.in_scale, r.res, reinterpret_cast<float*>(r.y), r.pool, r.B,
+                     r.Ci, r.Co, r.S, p.MT, p.MC, p.n_tiles, r.act, r.ci_x);
+  return eat::check_launch(r.who);
 }
 
 template <int NPROD>
-int try_stream(hipStream_t s, const float* x, const void* wp, const float* bias, const float* in_scale, const float* res,
-               float* y, float* pool, int B, int Ci, int Co, int S, int act, int mode, int ci_x) {
-  const int n_chunks = (Ci + kKC - 1) / kKC;
-  if ((mode & 1) && ci_x == Ci && !in_scale && !res && !pool && y && n_chunks <= 4 && Co >= 2 * Ci &&
-      (long long)B * Co * S * 4 < 0x7fffffffLL) {
-    switch (n_chunks) {
-      case 1: return launch_expand<1, NPROD>(s, x, wp, bias, y, B, Ci, Co, S, act);
-      case 2: return launch_expand<2, NPROD>(s, x, wp, bias, y, B, Ci, Co, S, act);
-      case 3: return launch_expand<3, NPROD>(s, x, wp, bias, y, B, Ci, Co, S, act);
-      default: return launch_expand<4, NPROD>(s, x, wp, bias, y, B, Ci, Co, S, act);
+int launch_stream(const eat::PwFwdReq& r, const eat::pw::PwPlan& p) {
+  if (p.route == eat::pw::Route::expand) {
+    switch (p.n_chunks) {
+      case 1: return launch_expand<1, NPROD>(r, p);
+      case 2: return launch_expand<2, NPROD>(r, p);
+      case 3: return launch_expand<3, NPROD>(r, p);
+      case 4: return launch_expand<4, NPROD>(r, p);
+      default: break;
     }
-  }
-  // bit 1 (the default): project-shaped layers where the K-streaming kernel measured faster in the mn10 forward at
-  // B = 256 - long reductions (C_in >= 160) that need no more row chunks than the LDS-staged kernel (<= 6 m-tiles, or as
-  // many chunks of <= 6 as of <= 8): 240->80 36->28 us, 672->160 41->28, 960->160 59->38; NOT 120->40 @ 16x125 (4
-  // chunks of K: 82 vs 86 us) and NOT 7 m-tiles (4 + 3 against one block of 7: 480->112 76 vs 87 us).
-  // bit 2: every other layer as row chunks of the K-streaming kernel (A/B and tests).
-  const int MT = (Co + 15) / 16;
-  const bool measured_win = Co <= 2 * Ci && Ci >= 160 && (MT + 5) / 6 == (MT + 7) / 8;
-  if (ci_x != Ci ? (mode & 8) != 0 : (((mode & 2) && measured_win) || (mode & 4))) {
-    const int MC = (MT + 5) / 6;                             // at most 6 m-tiles of accumulators + fragments per wave
-    const int mtw = (MT + MC - 1) / MC;
-#define EAT_CASE(n) \
-  case n: return launch_kstream<n, NPROD>(s, x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, MT, act, ci_x);
-    switch (mtw) {
+  } else {
+#define EAT_CASE(n) case n: return launch_kstream<n, NPROD>(r, p);
+    switch (p.mtw) {
       EAT_CASE(1) EAT_CASE(2) EAT_CASE(3) EAT_CASE(4) EAT_CASE(5) EAT_CASE(6)
       default: break;
     }
 #undef EAT_CASE
   }
-  return 1;
+  return eat::fail(EAT_EINVAL, "%s: internal tiling error", r.who);
 }
 
 }  // namespace
 
+int eat::pw_stream_launch(const PwFwdReq& r, const pw::PwPlan& p) {
+  return p.nprod == 3 ? launch_stream<3>(r, p) : launch_stream<1>(r, p);
+}
+
+// EAT_PW_STREAM / eat_pw_stream_mode: bit 0 = expand kernel, bit 1 = K-streaming kernel for project-shaped layers, bit 2 =
+// K-streaming kernel for whatever is left, bit 3 = K-streaming kernel for DyMN's K-concat launches (pw_fwd_plan.h: StreamMode)
 namespace {
 std::atomic<int>& stream_mode() {
   static std::atomic<int> mode{getenv("EAT_PW_STREAM") ? atoi(getenv("EAT_PW_STREAM")) & 15 : 2};
@@ -350,20 +330,3 @@ std::atomic<int>& stream_mode() {
 extern "C" int eat_pw_stream_mode(int mode) {
   return mode >= 0 ? stream_mode().exchange(mode & 15) : stream_mode().load();
 }
-
-namespace eat {
-
-// Returns 1 when the shape (or the EAT_PW_STREAM switch: bit 0 = expand kernel, bit 1 = k-stream kernel for project-shaped
-// layers, bit 2 = k-stream kernel for whatever is left, bit 3 = k-stream kernel for DyMN's K-concat launches) leaves the
-// layer to the LDS-staged kernel of conv_pw_bf16.hip; otherwise the launch status.  Caller has checked S % 4 == 0,
-// Ci % 4 == 0 (and ci_x % 32 == 0, in_scale != NULL when ci_x != Ci).
-int pw_stream_try(const float* x, const void* wp, const float* bias, const float* in_scale, const float* res, float* y,
-                  float* pool, int B, int Ci, int Co, int S, int act, int split, int ci_x, hipStream_t s) {
-  const int mode = stream_mode().load(std::memory_order_relaxed);
-  if (!mode) return 1;
-  if ((long long)B * S > 0x7fff0000LL) return 1;
-  return split ? try_stream<3>(s, x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, act, mode, ci_x)
-               : try_stream<1>(s, x, wp, bias, in_scale, res, y, pool, B, Ci, Co, S, act, mode, ci_x);
-}
-
-}  // namespace eat

@@ -5,6 +5,7 @@
 #include <cstdio>
 
 #include "../../include/eat_hip.h"
+#include "pw_fwd_plan.h"
 
 namespace eat {
 
@@ -78,17 +79,6 @@ int bn_stats_partial(const float* z, int B, int C, int S, float* part, hipStream
 int act_grad_sum(const float* dy, const float* z, const float* a, const float* b, int act, float* g, float* gpart, int B,
                  int C, int S, hipStream_t s);
 
-// conv_pw_generic.hip: 1x1 conv for plane sizes that are not a multiple of 4 (same packed weights / epilogue contract;
-// wmode 0 = fp32 pack, 1 = bf16 pack, 2 = bf16 hi/lo pack; wp_bstride_bytes != 0 selects per-sample weights)
-int pw_conv_generic(const float* x, const void* wp, const float* bias, const float* in_scale, const float* res, float* y,
-                    float* pool, int B, int Ci, int Co, int S, int act, int wmode, long long wp_bstride_bytes,
-                    hipStream_t s);
-
-// conv_pw_bf16.hip: 1x1 conv on the bf16 packs whose input is act_in(tf_a[k] x + tf_b[k]) evaluated on load
-int pw_conv_bf16_tf(const float* x, const float* tf_a, const float* tf_b, int tf_act, const void* wp, const float* bias,
-                    const float* in_scale, const float* res, float* y, int B, int Ci, int Co, int S, int act, int split,
-                    hipStream_t s);
-
 // BatchNorm-backward statistics in a 1x1 conv's epilogue (pw_epilogue.h: pw_epilogue_gstats): z = the tensor whose
 // BatchNorm + activation backward is being reduced (layout of the conv output), a / b = that BatchNorm's folded affine
 struct PwGStat { const void* z; const float* a; const float* b; int act; };
@@ -96,18 +86,6 @@ struct PwGStat { const void* z; const float* a; const float* b; int act; };
 // (train_fuse.hip), from the BatchNorm's (a, b): the zero of the pre-activation.  ONE expression, so that the epilogue subtracts
 // and the finish adds back the same fp32 number.
 __host__ __device__ __forceinline__ float gstat_center(float a, float b) { return a != 0.0f ? -b / a : 0.0f; }
-
-int pw_conv_bf16_stats(const float* x, const void* wp, int split, int per_sample, const float* tf_a, const float* tf_b,
-                       int tf_act, const float* in_scale, const float* zero_bias, float* y, float* part, int B, int Ci, int Co,
-                       int S, hipStream_t s, PwGStat gs = PwGStat{nullptr, nullptr, nullptr, 0});
-
-int pw_conv_bf16_cat(const float* x1, int c1, const float* x2, int c2, const void* wp, const float* bias, const float* res,
-                     float* y, int B, int Co, int S, int act, int split, hipStream_t s);
-
-// conv_pw_stream.hip: barrier-free bf16 1x1 kernels (x or the output tile resident in registers); returns 1 when the
-// shape / the EAT_PW_STREAM switch leaves the layer to conv_pw_bf16.hip
-int pw_stream_try(const float* x, const void* wp, const float* bias, const float* in_scale, const float* res, float* y,
-                  float* pool, int B, int Ci, int Co, int S, int act, int split, int ci_x, hipStream_t s);
 
 // ---- dw_plane.hip: the register-resident depthwise kernels.  Each dispatcher takes one request, filled by field name
 // (value-initialise it: every optional field is then NULL / 0), and returns 1 when no kernel covers it: the caller falls back.
@@ -146,6 +124,32 @@ struct DwDgrad2Req {
   DwGeom dim; const float* dz; const float* w; const float* res; float* dx; int per_plane_w; const DwEpi* epi; hipStream_t stream;
 };
 int dw_tile_dgrad2_try(const DwDgrad2Req& r);
+
+// ---- the forward 1x1 (pointwise) convolutions: every entry point fills one request by field name (value-initialise it: every
+// optional field is then NULL / 0) and hands it to pw_conv_run, which checks it, asks pw_fwd_plan.h for the route and launches.
+struct PwFwdReq {
+  int B, Ci, Co, S;                          // Ci: the whole reduction axis (both sources / every bank)
+  const void* x; pw::Store x_store;
+  const float* x2; int c1;                   // two-source form: x has c1 channels, x2 (fp32) the other Ci - c1; NULL: one source
+  int ci_x;                                  // K-concat form: channels of x, the reduction axis is Ci / ci_x copies; 0: plain
+  const void* wp; pw::Pack pack; bool per_sample;
+  const float* bias;
+  InTf tf;                                   // act(a[k] * x + b[k]) evaluated on load; a == NULL: none
+  const float* in_scale; const float* res;
+  void* y; pw::Store y_store;
+  float* pool; int act;
+  float* stats; PwGStat gs;                  // [tile][2][Co] partials of the statistics epilogue; gs.z: its BatchNorm-backward form
+  hipStream_t stream;
+  const char* who;                           // the entry point, for messages
+};
+// conv_pw.hip: check -> plan -> launch; 1 = no kernel with the statistics epilogue for this geometry, nothing launched
+int pw_conv_run(const PwFwdReq& r);
+// one launcher per file: the template switch over the plan (conv_pw.hip, conv_pw_bf16.hip, conv_pw_stream.hip: expand and
+// K-streaming kernels, conv_pw_generic.hip)
+int pw_lds_f32_launch(const PwFwdReq& r, const pw::PwPlan& p);
+int pw_lds_b16_launch(const PwFwdReq& r, const pw::PwPlan& p);
+int pw_stream_launch(const PwFwdReq& r, const pw::PwPlan& p);
+int pw_generic_launch(const PwFwdReq& r, const pw::PwPlan& p);
 
 }  // namespace eat
 

@@ -520,6 +520,32 @@ def dw_conv_wgrad_tf(dz, x, in_a, in_b, in_act, k, stride):
     return dw
 
 
+def _pack_wmode(wp, per_sample=False):
+    """`wmode` of the 1x1 entry points for a weight pack: 0 = fp32, 1 = plain bf16, 2 = bf16 hi / lo (per-sample bf16 packs
+    are hi / lo)."""
+    if wp.dtype == torch.float32:
+        return 0
+    return 2 if (per_sample or getattr(wp, "_eat_split", False)) else 1
+
+
+def _stat_partials(B, S, Co, device, per_sample=False):
+    """The [tile][2][Co] partial sums a 1x1 conv's statistics epilogue writes -> (part, tiles)."""
+    tiles = int(_lib.lib().eat_pw_conv_stat_tiles(B, S, 1 if per_sample else 0))
+    return torch.empty((tiles * 2 * Co,), device=device, dtype=torch.float32), tiles
+
+
+def _gstat_finish(part, tiles, Co, st, sums):
+    """BatchNorm-backward sums (2 Co,) float64 from the partials of a `gstats` epilogue; st = (a, b, mean, invstd)."""
+    a, b, mean, invstd = st
+    if sums is None:
+        sums = torch.empty((2 * Co,), device=part.device, dtype=torch.float64)
+    nws = int(_lib.lib().eat_bn_bwd_sums_ws_doubles(tiles, Co))
+    ws = torch.empty((nws,), device=part.device, dtype=torch.float64) if nws else None
+    _lib.call("eat_bn_bwd_sums_from_tiles", part.data_ptr(), tiles, Co, mean.data_ptr(), invstd.data_ptr(), a.data_ptr(),
+              b.data_ptr(), None if ws is None else ws.data_ptr(), sums.data_ptr(), _stream())
+    return sums
+
+
 def pw_tf_eligible(Ci, S):
     """Geometry of the on-load BatchNorm + activation of the 1x1 kernels (eat_pw_conv_tf_fwd / eat_pw_conv_wgrad_tf)."""
     return Ci % 8 == 0 and S % 4 == 0
@@ -528,7 +554,7 @@ def pw_tf_eligible(Ci, S):
 def pw_conv_tf(x, tf, wp, bias, Co, act, in_scale=None, res=None):
     """1x1 conv of act_in(tf_a[k] x + tf_b[k]) [* in_scale] evaluated on load; tf = (a, b, act_in); wp from `pw_prepack`."""
     B, Ci, F, T = x.shape
-    wmode = 0 if wp.dtype == torch.float32 else (2 if getattr(wp, "_eat_split", False) else 1)
+    wmode = _pack_wmode(wp)
     y = torch.empty((B, Co, F, T), device=x.device, dtype=torch.float32)
     _lib.call("eat_pw_conv_tf_fwd", _dev(x, "x"), tf[0].data_ptr(), tf[1].data_ptr(), tf[2], wp.data_ptr(), wmode,
               _dev(bias, "bias"), _opt(in_scale, "in_scale"), _opt(res, "res"), y.data_ptr(), B, Ci, Co, F * T, act,
@@ -541,7 +567,7 @@ def pw_conv_cat(x1, x2, wp, bias, Co, act, res=None):
     wp = pw_prepack of the (Co, C1 + C2) matrix."""
     B, C1, F, T = x1.shape
     C2 = x2.shape[1]
-    wmode = 0 if wp.dtype == torch.float32 else (2 if getattr(wp, "_eat_split", False) else 1)
+    wmode = _pack_wmode(wp)
     y = torch.empty((B, Co, F, T), device=x1.device, dtype=torch.float32)
     _lib.call("eat_pw_conv_cat_fwd", _dev(x1, "x"), C1, _dev(x2, "x2"), C2, wp.data_ptr(), wmode, _dev(bias, "bias"),
               _opt(res, "res"), y.data_ptr(), B, Co, F * T, act, _stream())
@@ -1162,10 +1188,9 @@ def pw_conv_stats(x, wp, Co, per_sample=False, tf=None, in_scale=None):
     `pw_prepack` / `dyn_pw_pack*` (per_sample=True: one pack per sample); tf = (a, b, act): input transform on load."""
     B, Ci, F, T = x.shape
     S = F * T
-    wmode = 0 if wp.dtype == torch.float32 else (2 if (per_sample or getattr(wp, "_eat_split", False)) else 1)   # (per-sample bf16 packs are hi / lo)
-    tiles = int(_lib.lib().eat_pw_conv_stat_tiles(B, S, 1 if per_sample else 0))
+    wmode = _pack_wmode(wp, per_sample)
     y = torch.empty((B, Co, F, T), device=x.device, dtype=torch.float32)
-    part = torch.empty((tiles * 2 * Co,), device=x.device, dtype=torch.float32)
+    part, tiles = _stat_partials(B, S, Co, x.device, per_sample)
     a, b, act = tf if tf is not None else (None, None, 0)
     rc = _lib.call_rc("eat_pw_conv_stats_fwd", _dev(x, "x"), wp.data_ptr(), wmode, 1 if per_sample else 0, _opt(a, "tf_a"),
                       _opt(b, "tf_b"), act, _opt(in_scale, "in_scale"), zeros_vec.get(Co, x.device).data_ptr(), y.data_ptr(),
@@ -1182,29 +1207,17 @@ def pw_conv_gstats(x, wp, Co, z, st, act, sums=None):
     where the epilogue does not exist (S % 4 != 0, plain-bf16 / fp32-free packs: the caller runs the separate pass)."""
     B, Ci, F, T = x.shape
     S = F * T
-    if wp.dtype == torch.float32:
-        wmode = 0
-    elif getattr(wp, "_eat_split", False):
-        wmode = 2
-    else:
+    wmode = _pack_wmode(wp)
+    if wmode == 1 or S % 4 != 0 or z.dtype != torch.float32:
         return None, None
-    if S % 4 != 0 or z.dtype != torch.float32:
-        return None, None
-    a, b, mean, invstd = st
-    tiles = int(_lib.lib().eat_pw_conv_stat_tiles(B, S, 0))
     y = torch.empty((B, Co, F, T), device=x.device, dtype=torch.float32)
-    part = torch.empty((tiles * 2 * Co,), device=x.device, dtype=torch.float32)
+    part, tiles = _stat_partials(B, S, Co, x.device)
     rc = _lib.call_rc("eat_pw_conv_gstats_fwd", _dev(x, "x"), wp.data_ptr(), wmode, zeros_vec.get(Co, x.device).data_ptr(),
-                      y.data_ptr(), _dev(z, "z"), a.data_ptr(), b.data_ptr(), act, part.data_ptr(), B, Ci, Co, S, _stream())
+                      y.data_ptr(), _dev(z, "z"), st[0].data_ptr(), st[1].data_ptr(), act, part.data_ptr(), B, Ci, Co, S,
+                      _stream())
     if rc == 1:
         return None, None
-    if sums is None:
-        sums = torch.empty((2 * Co,), device=x.device, dtype=torch.float64)
-    nws = int(_lib.lib().eat_bn_bwd_sums_ws_doubles(tiles, Co))
-    ws = torch.empty((nws,), device=x.device, dtype=torch.float64) if nws else None
-    _lib.call("eat_bn_bwd_sums_from_tiles", part.data_ptr(), tiles, Co, mean.data_ptr(), invstd.data_ptr(), a.data_ptr(),
-              b.data_ptr(), None if ws is None else ws.data_ptr(), sums.data_ptr(), _stream())
-    return y, sums
+    return y, _gstat_finish(part, tiles, Co, st, sums)
 
 
 # ---- round 4: fused training passes of the dynamic block (csrc/dymn.hip, csrc/dw_plane.hip)
@@ -1449,10 +1462,7 @@ def pw_conv_b16(x, wp, bias, Co, act, tf=None, in_scale=None, res=None, x2=None,
     Ci = C1 + (x2.shape[1] if x2 is not None else 0)
     y16 = out_b16 or not x16                       # (fp32 in: always a bf16 output; bf16 in: fp32, or bf16 for z_p)
     y = torch.empty((B, Co, F, T), device=x.device, dtype=torch.bfloat16 if y16 else torch.float32)
-    part = None
-    if stats or gstat is not None:
-        tiles = int(_lib.lib().eat_pw_conv_stat_tiles(B, S, 0))
-        part = torch.empty((tiles * 2 * Co,), device=x.device, dtype=torch.float32)
+    part, tiles = _stat_partials(B, S, Co, x.device) if stats or gstat is not None else (None, 0)
     a, b, tact = tf if tf is not None else (None, None, 0)
     # gstat = (z_d bf16, (a, b, mean, invstd), act, sums or None): bf16 -> bf16 project data gradient with the depthwise
     # BatchNorm's backward sums in the epilogue -> (y, sums (2 Co,) float64), see pw_conv_gstats
@@ -1463,12 +1473,7 @@ def pw_conv_b16(x, wp, bias, Co, act, tf=None, in_scale=None, res=None, x2=None,
               None if gz is None else _dev16(gz, "gz"), _opt(gst[0], "g_a"), _opt(gst[1], "g_b"), gact, B, Ci, Co, S, act,
               _stream())
     if gstat is not None:
-        sums = gsums if gsums is not None else torch.empty((2 * Co,), device=x.device, dtype=torch.float64)
-        nws = int(_lib.lib().eat_bn_bwd_sums_ws_doubles(tiles, Co))
-        ws = torch.empty((nws,), device=x.device, dtype=torch.float64) if nws else None
-        _lib.call("eat_bn_bwd_sums_from_tiles", part.data_ptr(), tiles, Co, gst[2].data_ptr(), gst[3].data_ptr(),
-                  gst[0].data_ptr(), gst[1].data_ptr(), None if ws is None else ws.data_ptr(), sums.data_ptr(), _stream())
-        return y, sums
+        return y, _gstat_finish(part, tiles, Co, gst, gsums)
     return (y, (part, tiles, 1)) if stats else y
 
 
@@ -1521,10 +1526,7 @@ def pw_conv_dyn_b16(x, wp_b, Co, act, res=None, stats=False):
     S = F * T
     x16 = _is16(x)
     y = torch.empty((B, Co, F, T), device=x.device, dtype=torch.float32 if x16 else torch.bfloat16)
-    part = None
-    if stats:
-        tiles = int(_lib.lib().eat_pw_conv_stat_tiles(B, S, 1))
-        part = torch.empty((tiles * 2 * Co,), device=x.device, dtype=torch.float32)
+    part, tiles = _stat_partials(B, S, Co, x.device, per_sample=True) if stats else (None, 0)
     _lib.call("eat_pw_conv_dyn_b16_fwd", _dev16(x, "x") if x16 else _dev(x, "x"), 1 if x16 else 0, wp_b.data_ptr(),
               zeros_vec.get(Co, x.device).data_ptr(), _opt(res, "res"), y.data_ptr(), 0 if x16 else 1,
               None if part is None else part.data_ptr(), B, Ci, Co, S, act, _stream())
