@@ -179,7 +179,8 @@ class _BlockState:
     inp: torch.Tensor                     # block input (fp32)
     b16: bool                             # this block's wide tensors (z_e, z_d, y_d; backward: dxs, g) are bf16 in HBM
     merged_res_ok: bool                   # the merged depthwise backward can serve the block's residual connection
-    z_e: torch.Tensor = None              # expand conv (all four None in a block without one): its output,
+    z_e: torch.Tensor = None              # expand conv (all five None in a block without one): its output,
+    W_e: torch.Tensor = None              # the weights its statistics and backward coefficients describe (`_expand_weights`),
     st_e: tuple = None                    # its BatchNorm state (a, b, mean, invstd),
     Tm: torch.Tensor = None               # T = W Gc (None with a frozen BatchNorm)
     sx: torch.Tensor = None               # and the channel sums of the block input
@@ -246,10 +247,19 @@ def _act(blk):
     return HSWISH if blk.cnf.use_hs else RELU
 
 
+def _expand_weights(conv):
+    """The (C_exp, C_in) matrix that the expand conv multiplies by: under precision 'bf16' its kernels round the weights to
+    bf16, so the BatchNorm statistics taken from the Gram matrix and the backward's coefficients must describe W rounded -
+    with the fp32 weights they describe a product the conv never forms (relative 2^-9 / sqrt(C_in) per channel, which the
+    narrow models, C_in = 8 ... 40 at widths 0.1 ... 0.5, do not average away)."""
+    W = conv.weight.flatten(1)
+    return W.bfloat16().float() if ops.precision.mode == "bf16" else W
+
+
 def _expand_fwd(blk, bi, rec, inp16, sx, plan, store16):
     """Expand conv; its BatchNorm + activation are left to the depthwise conv: -> tf = (a, b, act) to evaluate on load."""
     cnf, cna, inp = blk.cnf, blk.block[blk.i_expand], rec.inp
-    W = cna[0].weight.flatten(1)
+    W = rec.W_e = _expand_weights(cna[0]) if cna[1].training else cna[0].weight.flatten(1)
     n_e = inp.shape[0] * inp.shape[2] * inp.shape[3]
     if cna[1].training:
         # centred Gram matrix of the block input (reproducible; x - mean on load: the variance is not a
@@ -285,7 +295,7 @@ def _expand_bwd(blk, i, rec, g_e, gparts, res_grad, wgrad, g):
     cnf, cna, inp, st_e, b16 = blk.cnf, blk.block[blk.i_expand], rec.inp, rec.st_e, rec.b16
     pre = f"features.{i + 1}.block.{blk.i_expand}"
     Ci, Ce = cnf.input_channels, cnf.expanded_channels
-    W = cna[0].weight.flatten(1)
+    W = rec.W_e
     frozen = getattr(st_e[2], "_eat_frozen", False)
     n_e = inp.shape[0] * inp.shape[2] * inp.shape[3]
     Gx = wgrad(g_e, inp)
@@ -481,8 +491,9 @@ def _block_fwd(blk, bi, inp, inp16, sx, nxt, stem_fused, plan, store16):
     plan, _cast_narrow); sx: channel sums of `inp` (blocks with expand conv)."""
     cnf = blk.cnf
     # the backward's merged depthwise kernel has no residual input: of the residual blocks without expand conv it serves only the
-    # fused stem's consumer (the stem's backward kernel adds the two gradients on load); any other (custom
-    # inverted_residual_setting) takes the separate fp32 passes there, which read fp32 tensors: no bf16 storage either
+    # fused stem's consumer (the stem's backward kernel adds the two gradients on load); any other - block 2 of the released
+    # mn01 (width 0.1: 8 -> 8 -> 8, 3x3 / stride 1), or a custom inverted_residual_setting - takes the separate fp32 passes
+    # there, which read fp32 tensors: no bf16 storage either (tests/test_gpu_widths.py pins both)
     merged_res_ok = blk.i_expand is not None or not blk.use_res_connect or (bi == 0 and stem_fused)
     # bf16 storage of this block's wide tensors (z_e, z_d, y_d; backward: dxs, g) where the kernels cover its geometry
     # (a block without expand conv: its depthwise conv reads the fp32 block input and its backward hands an fp32

@@ -233,14 +233,19 @@ def test_oracle_dymn_variants_match_reference(tag, golden_dir):
 
 # ---------------------------------------------------------------- BASELINE widths: mn40 (configs[2]), dymn20 (configs[3])
 WIDTHS = {"mn40": ("mn", 4.0), "dymn20": ("dymn", 2.0)}
+# ... and the other released widths (oracle/make_golden.py:golden_more_widths, one fixture per model: width_<tag>_ref.npz)
+MORE_WIDTHS = {"mn01": ("mn", 0.1), "mn02": ("mn", 0.2), "mn04": ("mn", 0.4), "mn05": ("mn", 0.5), "mn20": ("mn", 2.0),
+               "mn30": ("mn", 3.0), "dymn04": ("dymn", 0.4)}
+ALL_WIDTHS = {**WIDTHS, **MORE_WIDTHS}
 
 
 def width_state(tag, golden_dir):
-    """(state_dict, golden npz) of the reference-generated fixture of `oracle/make_golden.py:golden_widths`."""
+    """(state_dict, golden npz) of the reference-generated fixture of `oracle/make_golden.py:golden_widths` /
+    `golden_more_widths`."""
     import contextlib
     import io
-    kind, width = WIDTHS[tag]
-    g = np.load(os.path.join(golden_dir, "widths_ref.npz"))
+    kind, width = ALL_WIDTHS[tag]
+    g = np.load(os.path.join(golden_dir, "widths_ref.npz" if tag in WIDTHS else f"width_{tag}_ref.npz"))
     if kind == "mn":
         from efficientat_amd.mn import get_model
     else:
@@ -258,12 +263,13 @@ def width_state(tag, golden_dir):
     return model, sd, g
 
 
-@pytest.mark.parametrize("tag", list(WIDTHS))
+@pytest.mark.parametrize("tag", list(ALL_WIDTHS))
 def test_oracle_at_baseline_widths_matches_reference(tag, golden_dir):
-    """models/mn/model.py:326-367 (width_mult=4.0) / models/dymn/model.py:289-361 (width_mult=2.0): eval logits and one
-    train-mode step (DynamicConv temperature 30, the reference's initial value) of the unmodified reference."""
+    """models/mn/model.py:326-367 (width_mult=4.0) / models/dymn/model.py:289-361 (width_mult=2.0) and the other released
+    widths (mn01 ... mn30, dymn04): eval logits and one train-mode step (DynamicConv temperature 30, the reference's
+    initial value) of the unmodified reference."""
     import torch.nn.functional as F
-    kind, width = WIDTHS[tag]
+    kind, width = ALL_WIDTHS[tag]
     _, sd, g = width_state(tag, golden_dir)
     x = O.mel_forward(synth.parity_clips(96000, seed=45)).unsqueeze(1)
     fwd = (lambda s, xm, **k: O.mn_forward(s, xm, width_mult=width, **k)) if kind == "mn" else \
@@ -275,7 +281,8 @@ def test_oracle_at_baseline_widths_matches_reference(tag, golden_dir):
         assert np.abs(got.numpy() - ref).max() < 1e-4 * max(1.0, np.abs(ref).max()), key
     sdr = {k: (v.clone().requires_grad_(True) if v.dtype.is_floating_point and not k.endswith(
         ("running_mean", "running_var", "lambdas", "init_v")) else v.clone()) for k, v in sd.items()}
-    kw = dict(train=True, stats={})
+    stats = {}
+    kw = dict(train=True, stats=stats)
     if kind == "dymn":
         kw["temperature"] = 30.0
     tl, _ = fwd(sdr, x, **kw)
@@ -290,3 +297,8 @@ def test_oracle_at_baseline_widths_matches_reference(tag, golden_dir):
         ref = float(g[f"{tag}/gnorm/{name}"])
         if ref > 1e-4 * gmax:
             assert abs(float(v.grad.norm()) - ref) < 2e-2 * ref, name
+    # the BatchNorm running buffers after the step (the bar of _check_train)
+    assert stats and len(stats) == sum(k.startswith(f"{tag}/bn_after/") for k in g.files)
+    for k, v in stats.items():
+        ref = g[f"{tag}/bn_after/{k}"]
+        assert np.abs(v.numpy() - ref).max() < 1e-4 * max(1.0, np.abs(ref).max()), k
