@@ -2154,6 +2154,80 @@ def embed_pool(fmaps, lo, hi, out=None):
     return out
 
 
+# ------------------------------------------------------------------ query-by-example search (include/eat_search.h)
+SEARCH_MAX_K, SEARCH_MAX_Q = 128, 1024
+# geometry of csrc/search.hip (kBlocks, kMaxGroup, kWaves x rows_per_wave), for callers that size a bank to it
+SEARCH_BLOCKS, SEARCH_GROUP = 256, 16
+
+
+def search_tile_rows(group):
+    """Bank rows that one block of the scan takes per step when `group` queries (a power of two up to 16) are resident."""
+    return 8 * 8                   # kWaves x rows_per_wave(group): the same for every group today
+
+
+_SEARCH_WS = {}              # (device, Q, k) -> workspace of eat_embed_search_ws_bytes(Q, k) bytes
+
+
+def rows_normalize(x, out=None):
+    """x (N, D) -> x / sqrt(sum_d x^2) per row, fp32; a row whose sum of squares is 0 becomes zeros.  out: None, x itself (in
+    place) or another (N, D) tensor that does not overlap x."""
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise _lib.EatHipError(f"rows_normalize: x must be (N, D >= 1), got {tuple(x.shape)}")
+    px = _dev(x, "x")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.device != x.device:
+        raise _lib.EatHipError(f"rows_normalize: out must be {tuple(x.shape)} on {x.device} (got {tuple(out.shape)} on {out.device})")
+    _lib.call("eat_rows_normalize", px, x.shape[0], x.shape[1], _dev(out, "out"), _stream())
+    return out
+
+
+def check_skip(skip, Q):
+    """Host-side validation of the exclusion table of `embed_search` (a CPU array): (Q, 2) integers lo, hi that fit int32
+    -> contiguous int32 CPU tensor.  The kernel clamps both bounds into [0, N]; lo >= hi excludes nothing."""
+    try:
+        t = torch.as_tensor(skip)
+    except (ValueError, TypeError) as e:
+        raise _lib.EatHipError(f"embed_search: ragged skip table ({e})") from None
+    if t.dim() != 2 or tuple(t.shape) != (Q, 2):
+        raise _lib.EatHipError(f"embed_search: skip must be ({Q}, 2): lo, hi per query (got {tuple(t.shape)})")
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise _lib.EatHipError("embed_search: skip bounds must be integers")
+    t = t.to(torch.int64).cpu()
+    if bool(((t < -2 ** 31) | (t > 2 ** 31 - 1)).any()):
+        raise _lib.EatHipError("embed_search: skip bounds must fit int32")
+    return t.to(torch.int32).contiguous()
+
+
+def embed_search(bank, queries, k, skip=None):
+    """The k rows of `bank` (N, D) of largest dot product with each row of `queries` (Q, D), both L2-normalised already
+    (`rows_normalize`) -> (score (Q, k) fp32, index (Q, k) int32): descending score, equal scores by ascending row; where
+    fewer than k rows are eligible the remaining slots hold (-inf, -1).  skip: None or a CPU (Q, 2) table lo, hi - rows
+    [lo, hi) are not eligible for that query (`check_skip`).  1 <= k <= 128, 1 <= Q <= 1024; no (Q, N) matrix exists at
+    any time, the bank is read once per group of up to 16 queries."""
+    if bank.dim() != 2 or queries.dim() != 2 or bank.shape[1] != queries.shape[1] or bank.shape[1] < 1:
+        raise _lib.EatHipError(f"embed_search: bank (N, D) and queries (Q, D) must share D >= 1 (got {tuple(bank.shape)}, "
+                               f"{tuple(queries.shape)})")
+    pb, pq = _dev(bank, "x"), _dev(queries, "queries")
+    if queries.device != bank.device:
+        raise _lib.EatHipError(f"embed_search: bank lives on {bank.device}, queries on {queries.device}")
+    (N, D), Q, k, dev = bank.shape, queries.shape[0], int(k), bank.device
+    if not 1 <= k <= SEARCH_MAX_K or not 1 <= Q <= SEARCH_MAX_Q or N < 1:
+        raise _lib.EatHipError(f"embed_search: need 1 <= k <= {SEARCH_MAX_K}, 1 <= Q <= {SEARCH_MAX_Q} and N >= 1 "
+                               f"(got k={k}, Q={Q}, N={N})")
+    skip_d = None if skip is None else check_skip(skip, Q).to(dev)
+    ws = _SEARCH_WS.get((dev, Q, k))
+    if ws is None:
+        if len(_SEARCH_WS) >= 64:
+            _SEARCH_WS.clear()
+        ws = _SEARCH_WS[(dev, Q, k)] = torch.empty(_lib.lib().eat_embed_search_ws_bytes(Q, k), device=dev, dtype=torch.uint8)
+    score = torch.empty((Q, k), device=dev, dtype=torch.float32)
+    index = torch.empty((Q, k), device=dev, dtype=torch.int32)
+    _lib.call("eat_embed_search", pb, N, D, pq, Q, k, None if skip_d is None else skip_d.data_ptr(), ws.data_ptr(), ws.numel(),
+              score.data_ptr(), index.data_ptr(), _stream())
+    return score, index
+
+
 # ------------------------------------------------------------------ attention-pooling head (models/mn/attention_pooling.py:9-56)
 def pitch4(T):
     """Row pitch of the head's (B, rows, T) tensors: T rounded up to a multiple of 4 (16-byte row pieces of the 1x1 kernels)."""

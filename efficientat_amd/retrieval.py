@@ -1,0 +1,285 @@
+"""Query-by-example search over audio embeddings: which rows of an index sound like this query.
+
+An `EmbeddingIndex` is a resident matrix of L2-normalised embeddings (N, D) - scene embeddings, one row per recording, or
+timestamp embeddings, one row every hop_ms of each recording (efficientat_amd/embeddings.py) - plus host bookkeeping per
+row: the file it came from and its time.  Rows of one file are contiguous, so a file is a row range.  `search` returns,
+per query, the k rows of largest cosine score in descending order, equal scores by ascending row, optionally leaving out
+one file's rows (the query's own).  Normalisation and the fused score + top-k are ``eat_rows_normalize`` and
+``eat_embed_search`` (include/eat_search.h, csrc/search.hip): no (Q, N) score matrix exists at any time, and there is no
+CPU path - an index without a device keeps books, saves and loads, and refuses to search.
+
+On disk an index is a directory: ``emb.npy`` (N, D) fp32 rows as stored (normalised), ``file.npy`` (N,) int32 file id per
+row, ``time_ms.npy`` (N,) float64 (-1 for a scene row), ``names.txt`` one file name per line, ``meta.json``.
+"""
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+VERSION = 1
+KINDS = ("scene", "timestamps")
+META_KEYS = ("version", "D", "kind", "model_name", "layers", "clip_seconds", "hop_ms", "width_ms")
+
+
+def _default_meta(D):
+    return {"version": VERSION, "D": int(D), "kind": "scene", "model_name": None, "layers": None, "clip_seconds": None,
+            "hop_ms": None, "width_ms": None}
+
+
+class EmbeddingIndex:
+    """D       embedding size
+    device  where the bank lives; None: on the CPU, for bookkeeping, `save` and `load` only - `add` then stores the rows AS
+            GIVEN (rows downloaded from another index; nothing normalises on the CPU) and `search` raises EatHipError
+    meta    entries of `META_KEYS` to record (kind, model_name, layers, clip_seconds, hop_ms, width_ms)"""
+
+    def __init__(self, D, device=None, meta=None):
+        if int(D) < 1:
+            raise ValueError(f"EmbeddingIndex: need D >= 1 (got {D})")
+        self.D = int(D)
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise ValueError(f"EmbeddingIndex: device must be a GPU or None (got {self.device})")
+        if self.device is not None and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.meta = _default_meta(self.D)
+        for key, value in (meta or {}).items():
+            if key not in META_KEYS:
+                raise ValueError(f"EmbeddingIndex: unknown meta entry '{key}' (known: {', '.join(META_KEYS)})")
+            self.meta[key] = value
+        if self.meta["version"] != VERSION or self.meta["D"] != self.D or self.meta["kind"] not in KINDS:
+            raise ValueError(f"EmbeddingIndex: meta needs version = {VERSION}, D = {self.D} and kind in {KINDS} (got {self.meta})")
+        self.names = []
+        self._ranges = {}                                        # name -> (lo, hi)
+        self._file = np.zeros(0, dtype=np.int32)
+        self._time = np.zeros(0, dtype=np.float64)
+        self._bank = torch.empty((0, self.D), dtype=torch.float32, device=self.device or "cpu")
+        self._n = 0
+
+    # -- bookkeeping -----------------------------------------------------------------------------------------------------
+    def __len__(self):
+        return self._n
+
+    @property
+    def bank(self):
+        """The rows as stored, (N, D) fp32 on the index's device (a view of the resident buffer)."""
+        return self._bank[:self._n]
+
+    @property
+    def file_ids(self):
+        return self._file
+
+    @property
+    def time_ms(self):
+        return self._time
+
+    def row_range(self, name):
+        if name not in self._ranges:
+            raise ValueError(f"EmbeddingIndex: no file named '{name}' in the index")
+        return self._ranges[name]
+
+    def add(self, emb, name, times_ms=None):
+        """One file's rows: emb (n >= 1, D), times_ms None (scene rows) or (n,) >= 0 -> the row range (lo, hi).  On a device
+        the rows are L2-normalised by `ops.rows_normalize` straight into the resident bank, which grows by doubling."""
+        name = str(name)
+        if name in self._ranges:
+            raise ValueError(f"EmbeddingIndex: a file named '{name}' is in the index already")
+        if name == "" or "\n" in name or "\r" in name:
+            raise ValueError(f"EmbeddingIndex: a file name must be one non-empty line (got {name!r})")
+        emb = torch.as_tensor(emb)
+        if emb.dim() == 1:
+            emb = emb.unsqueeze(0)
+        if emb.dim() != 2 or emb.shape[0] < 1 or emb.shape[1] != self.D:
+            raise ValueError(f"EmbeddingIndex: rows of '{name}' must be (n >= 1, {self.D}) (got {tuple(emb.shape)})")
+        n = emb.shape[0]
+        if times_ms is None:
+            times = np.full(n, -1.0, dtype=np.float64)
+        else:
+            times = np.asarray(times_ms, dtype=np.float64).reshape(-1)
+            if times.shape != (n,) or not bool(np.isfinite(times).all()) or bool((times < 0).any()):
+                raise ValueError(f"EmbeddingIndex: times_ms of '{name}' must be {n} finite values >= 0")
+        kind = "scene" if times_ms is None else "timestamps"
+        if self._n > 0 and kind != self.meta["kind"]:
+            raise ValueError(f"EmbeddingIndex: '{name}' brings {kind} rows into an index of {self.meta['kind']} rows")
+        if self._n + n > 2 ** 31 - 1:
+            raise ValueError("EmbeddingIndex: more than 2^31 - 1 rows")
+        self.meta["kind"] = kind
+        lo, hi = self._n, self._n + n
+        if hi > self._bank.shape[0]:
+            grown = torch.empty((max(hi, 2 * self._bank.shape[0], 64), self.D), dtype=torch.float32, device=self._bank.device)
+            grown[:lo] = self._bank[:lo]
+            self._bank = grown
+        emb = emb.to(device=self._bank.device, dtype=torch.float32).contiguous()
+        if self.device is None:
+            self._bank[lo:hi] = emb
+        else:
+            with torch.cuda.device(self.device):
+                ops.rows_normalize(emb, out=self._bank[lo:hi])
+        self._file = np.concatenate((self._file, np.full(n, len(self.names), dtype=np.int32)))
+        self._time = np.concatenate((self._time, times))
+        self.names.append(name)
+        self._ranges[name] = (lo, hi)
+        self._n = hi
+        return lo, hi
+
+    # -- search ----------------------------------------------------------------------------------------------------------
+    def check_extractor(self, extractor):
+        """ValueError unless the extractor's (D, layers, clip_seconds) are those the index was built with (entries that meta
+        does not record - None - are not compared)."""
+        got = {"D": int(extractor.scene_embedding_size), "layers": [int(i) for i in extractor.layers],
+               "clip_seconds": float(extractor.clip_seconds)}
+        for key, value in got.items():
+            want = self.meta[key]
+            if want is not None and (list(want) if key == "layers" else want) != value:
+                raise ValueError(f"EmbeddingIndex: the index was built with {key} = {want}, the extractor has {key} = {value}: "
+                                 f"their embeddings do not compare")
+
+    def search(self, queries, k, exclude=None, extractor=None):
+        """queries (Q, D), k -> (score (Q, k) fp32, index (Q, k) int32) on the device: the k rows of largest cosine score per
+        query in descending order, equal scores by ascending row, (-inf, -1) where fewer than k rows are eligible.
+        exclude: per query, None or the name of a file whose rows are not eligible.  The queries are normalised by the
+        kernel that normalised the bank.  extractor: where the queries come from, checked by `check_extractor`."""
+        if self.device is None:
+            raise _lib.EatHipError("EmbeddingIndex.search needs the index on a GPU: efficientat_amd has no CPU path "
+                                   "(load it with device='cuda')")
+        if extractor is not None:
+            self.check_extractor(extractor)
+        if self._n < 1:
+            raise ValueError("EmbeddingIndex: the index is empty")
+        queries = torch.as_tensor(queries)
+        if queries.dim() == 1:
+            queries = queries.unsqueeze(0)
+        if queries.dim() != 2 or queries.shape[1] != self.D or queries.shape[0] < 1:
+            raise ValueError(f"EmbeddingIndex: queries must be (Q >= 1, {self.D}) (got {tuple(queries.shape)})")
+        Q = queries.shape[0]
+        skip = None
+        if exclude is not None:
+            exclude = [exclude] * Q if isinstance(exclude, str) else list(exclude)
+            if len(exclude) != Q:
+                raise ValueError(f"EmbeddingIndex: exclude must hold one name or None per query ({Q}), got {len(exclude)}")
+            skip = [(0, 0) if name is None else self.row_range(name) for name in exclude]
+        with torch.cuda.device(self.device):
+            qn = ops.rows_normalize(queries.to(device=self.device, dtype=torch.float32).contiguous())
+            return ops.embed_search(self.bank, qn, k, skip)
+
+    def hits(self, score, index):
+        """(score, index) of `search` -> per query a host list of {"name", "time_ms" (None for a scene row), "row", "score"},
+        best first, without the -1 slots."""
+        score, index = torch.as_tensor(score).cpu().numpy(), torch.as_tensor(index).cpu().numpy()
+        if score.shape != index.shape or score.ndim != 2:
+            raise ValueError(f"EmbeddingIndex.hits: score and index must share one (Q, k) shape (got {score.shape}, {index.shape})")
+        if bool(((index < -1) | (index >= self._n)).any()):
+            raise ValueError(f"EmbeddingIndex.hits: a row index outside [-1, {self._n})")
+        out = []
+        for s_row, i_row in zip(score, index):
+            found = []
+            for s, i in zip(s_row, i_row):
+                if i >= 0:
+                    t = float(self._time[i])
+                    found.append({"name": self.names[self._file[i]], "time_ms": None if t < 0 else t, "row": int(i), "score": float(s)})
+            out.append(found)
+        return out
+
+    # -- disk ------------------------------------------------------------------------------------------------------------
+    def save(self, path):
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "emb.npy"), self.bank.cpu().numpy())
+        np.save(os.path.join(path, "file.npy"), self._file)
+        np.save(os.path.join(path, "time_ms.npy"), self._time)
+        with open(os.path.join(path, "names.txt"), "w") as f:
+            f.write("".join(name + "\n" for name in self.names))
+        with open(os.path.join(path, "meta.json"), "w") as f:
+            json.dump({key: self.meta[key] for key in META_KEYS}, f, indent=1)
+            f.write("\n")
+
+    @classmethod
+    def load(cls, path, device=None):
+        """The index that `save` wrote into the directory `path`, its rows as stored (not normalised again: a search gives
+        the bits it gave before).  ValueError, naming the path, for anything that `save` could not have written."""
+        def bad(what):
+            return ValueError(f"EmbeddingIndex.load: {path}: {what}")
+
+        def read(name, reader):
+            full = os.path.join(path, name)
+            if not os.path.isfile(full):
+                raise bad(f"{name} is missing")
+            try:
+                return reader(full)
+            except (ValueError, OSError, EOFError, UnicodeDecodeError) as e:
+                raise bad(f"{name} is unreadable ({e})") from None
+
+        def text(full):
+            with open(full) as f:
+                return f.read()
+
+        try:
+            meta = json.loads(read("meta.json", text))
+        except json.JSONDecodeError as e:
+            raise bad(f"meta.json is not JSON ({e})") from None
+        if not isinstance(meta, dict) or set(meta) != set(META_KEYS):
+            raise bad(f"meta.json must hold exactly the entries {', '.join(META_KEYS)}")
+        if meta["version"] != VERSION:
+            raise bad(f"meta.json has version {meta['version']!r}, this code reads version {VERSION}")
+        if not isinstance(meta["D"], int) or isinstance(meta["D"], bool) or meta["D"] < 1 or meta["kind"] not in KINDS:
+            raise bad(f"meta.json needs an integer D >= 1 and kind in {KINDS} (got D = {meta['D']!r}, kind = {meta['kind']!r})")
+        D = meta["D"]
+        emb = read("emb.npy", lambda p: np.load(p, allow_pickle=False))
+        file = read("file.npy", lambda p: np.load(p, allow_pickle=False))
+        time = read("time_ms.npy", lambda p: np.load(p, allow_pickle=False))
+        names = read("names.txt", text).split("\n")
+        if names[-1] != "":
+            raise bad("names.txt does not end with a newline")
+        names = names[:-1]
+        if emb.ndim != 2 or emb.shape[1] != D or emb.dtype != np.float32:
+            raise bad(f"emb.npy must be (N, {D}) float32 (got {emb.shape} {emb.dtype})")
+        N = emb.shape[0]
+        if file.shape != (N,) or file.dtype != np.int32:
+            raise bad(f"file.npy must be ({N},) int32 (got {file.shape} {file.dtype})")
+        if time.shape != (N,) or time.dtype != np.float64:
+            raise bad(f"time_ms.npy must be ({N},) float64 (got {time.shape} {time.dtype})")
+        if not bool(np.isfinite(emb).all()):
+            raise bad("emb.npy holds a value that is not finite")
+        if len(set(names)) != len(names) or any(name == "" for name in names):
+            raise bad("names.txt holds an empty or a repeated name")
+        if bool(((file < 0) | (file >= len(names))).any()):
+            raise bad(f"file.npy holds a file id outside [0, {len(names)})")
+        # every file has rows, and they are contiguous: the ids go 0, .., 0, 1, .., 1, 2, ..
+        steps = np.diff(file.astype(np.int64))
+        if (N == 0) != (len(names) == 0) or (N > 0 and (file[0] != 0 or file[-1] != len(names) - 1
+                                                        or not bool(((steps == 0) | (steps == 1)).all()))):
+            raise bad("the rows of each file must be contiguous, in the order of names.txt, and every file must have rows")
+        scene = meta["kind"] == "scene"
+        if not bool(np.isfinite(time).all()) or (scene and not bool((time == -1.0).all())) or (not scene and bool((time < 0).any())):
+            raise bad(f"time_ms.npy must hold -1 for every row of a scene index and times >= 0 otherwise (kind = {meta['kind']})")
+        index = cls(D, device=device, meta=meta)
+        index._bank = torch.from_numpy(np.ascontiguousarray(emb)).to(index.device or "cpu")
+        index._n = N
+        index._file, index._time, index.names = file.copy(), time.copy(), names
+        bounds = np.flatnonzero(np.diff(file)) + 1 if N else np.zeros(0, dtype=np.int64)
+        los = [0] + [int(b) for b in bounds]
+        his = [int(b) for b in bounds] + [N]
+        index._ranges = {name: (lo, hi) for name, lo, hi in zip(names, los, his)}
+        return index
+
+    # -- from audio ------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_recordings(cls, extractor, waves, names, timestamps=False, hop_ms=50.0, width_ms=160.0, model_name=None):
+        """An index on the extractor's device of the recordings `waves` (what `EmbeddingExtractor.scene_embeddings` takes)
+        named `names`: their scene embeddings, or with timestamps=True their timestamp embeddings (hop_ms, width_ms).  A
+        scene query searched in a timestamp index finds where the query occurs: choose width_ms near the query's length."""
+        names = [str(n) for n in names]
+        if len(names) != len(waves):
+            raise ValueError(f"EmbeddingIndex.from_recordings: {len(waves)} recordings, {len(names)} names")
+        meta = {"kind": "timestamps" if timestamps else "scene", "model_name": model_name,
+                "layers": [int(i) for i in extractor.layers], "clip_seconds": float(extractor.clip_seconds),
+                "hop_ms": float(hop_ms) if timestamps else None, "width_ms": float(width_ms) if timestamps else None}
+        index = cls(extractor.scene_embedding_size, device=extractor.device, meta=meta)
+        if timestamps:
+            for name, (emb, t_ms) in zip(names, extractor.timestamp_embeddings(waves, hop_ms=hop_ms, width_ms=width_ms)):
+                index.add(emb, name, t_ms)
+        else:
+            for name, emb in zip(names, extractor.scene_embeddings(waves)):
+                index.add(emb, name)
+        return index
