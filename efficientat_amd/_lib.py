@@ -1,6 +1,6 @@
 """ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h, include/eat_embed.h,
 include/eat_attn.h, include/eat_detect.h, include/eat_sed.h, include/eat_event_score.h, include/eat_psds.h,
-include/eat_weak_sed.h, include/eat_median_bank.h and include/eat_search.h).
+include/eat_weak_sed.h, include/eat_median_bank.h, include/eat_search.h and include/eat_search_q8.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -39,6 +39,8 @@ WEAK_SED_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_weak_sed.h
 MEDIAN_BANK_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_median_bank.h")
 # query-by-example search's entry points (efficientat_amd/retrieval.py): likewise
 SEARCH_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_search.h")
+# the 8-bit search index's entry points (efficientat_amd/retrieval.py, storage="q8"): likewise
+SEARCH_Q8_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_search_q8.h")
 
 
 class EatHipError(RuntimeError):
@@ -103,6 +105,8 @@ with open(MEDIAN_BANK_HEADER_PATH) as _f:
     MEDIAN_BANK_PROTOTYPES = parse_prototypes(_f.read())               # likewise
 with open(SEARCH_HEADER_PATH) as _f:
     SEARCH_PROTOTYPES = parse_prototypes(_f.read())                    # likewise
+with open(SEARCH_Q8_HEADER_PATH) as _f:
+    SEARCH_Q8_PROTOTYPES = parse_prototypes(_f.read())                 # likewise
 
 _lib = None
 
@@ -120,7 +124,8 @@ def lib():
                                           + list(ATTN_PROTOTYPES.items()) + list(DETECT_PROTOTYPES.items())
                                           + list(SED_PROTOTYPES.items()) + list(EVENT_SCORE_PROTOTYPES.items())
                                           + list(PSDS_PROTOTYPES.items()) + list(WEAK_SED_PROTOTYPES.items())
-                                          + list(MEDIAN_BANK_PROTOTYPES.items()) + list(SEARCH_PROTOTYPES.items())):
+                                          + list(MEDIAN_BANK_PROTOTYPES.items()) + list(SEARCH_PROTOTYPES.items())
+                                          + list(SEARCH_Q8_PROTOTYPES.items())):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

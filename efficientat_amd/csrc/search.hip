@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "eat_common.h"
+#include "search_topk.h"
 #include "../../include/eat_search.h"
 
 namespace {
@@ -39,17 +40,7 @@ constexpr long long kLdsBytes = 160 * 1024;
 
 constexpr int rows_per_wave(int G) { return 8; }                       // R: rows a wavefront multiplies at once
 
-// LDS written by one lane of the wavefront is read by another: order the two (no barrier instruction is needed inside a wave)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the order of results: larger score first, equal scores by ascending index; the pad (-inf, -1) is last of all
-__device__ __forceinline__ bool better(float s, int i, float ts, int ti) {
-  return s > ts || (s == ts && (unsigned)i < (unsigned)ti);
-}
+using namespace eat;             // search_topk.h: better, list_insert, list_offer, search_merge_kernel, row_sumsq
 
 // elements d .. d + 3 of a row (zeros from D on).  VEC: one 16-byte load (D % 4 == 0, 16-byte aligned rows).
 // TAIL = false: the caller knows d + 3 < D.
@@ -111,24 +102,6 @@ __device__ __forceinline__ float transpose_sum(const float (&a)[V], int lane) {
     for (int o = O; o >= 1; o /= 2) v += __shfl_xor(v, o, 64);
     return v;
   }
-}
-
-// (s, i) into the sorted list (ls, li) of k entries, whose last entry it beats; the whole wavefront calls it
-__device__ __forceinline__ void list_insert(float* ls, int* li, int k, float s, int i, int lane) {
-  const int i0 = lane, i1 = lane + 64;
-  const bool a0 = i0 < k && better(ls[i0], li[i0], s, i);
-  const bool a1 = i1 < k && better(ls[i1], li[i1], s, i);
-  const int pos = __popcll(__ballot(a0)) + __popcll(__ballot(a1));        // entries ahead of (s, i); pos <= k - 1
-  float s0 = 0.0f, s1 = 0.0f;
-  int j0 = 0, j1 = 0;
-  if (i0 < k && i0 > pos) { s0 = ls[i0 - 1]; j0 = li[i0 - 1]; }
-  if (i1 < k && i1 > pos) { s1 = ls[i1 - 1]; j1 = li[i1 - 1]; }
-  wave_sync();
-  if (i0 < k && i0 > pos) { ls[i0] = s0; li[i0] = j0; }
-  if (i1 < k && i1 > pos) { ls[i1] = s1; li[i1] = j1; }
-  if (i0 == pos) { ls[i0] = s; li[i0] = i; }
-  if (i1 == pos) { ls[i1] = s; li[i1] = i; }
-  wave_sync();
 }
 
 // LDS of one stage-1 block: G x Dp floats of queries (QLDS), G x k (score, index), 2 x G x tile-rows scores, G x (lo, hi)
@@ -219,14 +192,7 @@ __global__ __launch_bounds__(kThreads) void search_scan_kernel(const float* __re
       const long long row = t * TR + lane;
       const float s = lane < TR ? sc[(buf * G + g) * TR + lane] : 0.0f;
       const bool eligible = lane < TR && row < N && !(row >= s_lo[g] && row < s_hi[g]);
-      unsigned long long pass = __ballot(eligible && better(s, (int)row, ls[k - 1], li[k - 1]));
-      while (pass != 0) {                                             // wave-uniform; ascending row
-        const int j = __ffsll((long long)pass) - 1;
-        pass &= pass - 1;
-        const float cs = __shfl(s, j, 64);
-        const int ci = (int)(t * TR + j);
-        if (better(cs, ci, ls[k - 1], li[k - 1])) list_insert(ls, li, k, cs, ci, lane);
-      }
+      list_offer(ls, li, k, s, t * TR, eligible, lane);
     }
   }
   __syncthreads();
@@ -238,44 +204,6 @@ __global__ __launch_bounds__(kThreads) void search_scan_kernel(const float* __re
   }
 }
 
-// one block per query of the group: score / index (Qg, k) from ws [Qg][kBlocks][k], each list sorted
-__global__ __launch_bounds__(kBlocks) void search_merge_kernel(const float* __restrict__ ws_s, const int* __restrict__ ws_i,
-                                                               int k, float* __restrict__ score, int* __restrict__ index) {
-  __shared__ float w_s[2][kBlocks / 64];
-  __shared__ int w_i[2][kBlocks / 64], w_t[2][kBlocks / 64];
-  const int g = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const size_t base = ((size_t)g * kBlocks + tid) * k;
-  int head = 0;
-  float s = ws_s[base];
-  int i = ws_i[base];
-  for (int r = 0; r < k; ++r) {
-    float bs = s;
-    int bi = i, bt = tid;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float os = __shfl_xor(bs, o, 64);
-      const int oi = __shfl_xor(bi, o, 64), ot = __shfl_xor(bt, o, 64);
-      if (better(os, oi, bs, bi) || (os == bs && oi == bi && ot < bt)) { bs = os; bi = oi; bt = ot; }
-    }
-    const int p = r & 1;                                              // slots of round r are rewritten in round r + 2,
-    if (lane == 0) { w_s[p][wave] = bs; w_i[p][wave] = bi; w_t[p][wave] = bt; }      // past the barrier of round r + 1
-    __syncthreads();
-    bs = w_s[p][0]; bi = w_i[p][0]; bt = w_t[p][0];
-#pragma unroll
-    for (int w = 1; w < kBlocks / 64; ++w)
-      if (better(w_s[p][w], w_i[p][w], bs, bi)) { bs = w_s[p][w]; bi = w_i[p][w]; bt = w_t[p][w]; }      // ties: the lower wave
-    if (tid == 0) {
-      score[(size_t)g * k + r] = bs;
-      index[(size_t)g * k + r] = bi;
-    }
-    if (tid == bt) {                                                  // pop the winner's list
-      ++head;
-      s = head < k ? ws_s[base + head] : -INFINITY;
-      i = head < k ? ws_i[base + head] : -1;
-    }
-  }
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(256) void rows_normalize_kernel(const float* x, long long N, int D_, float* out) {
   const unsigned D = (unsigned)D_;
@@ -283,20 +211,7 @@ __global__ __launch_bounds__(256) void rows_normalize_kernel(const float* x, lon
   for (long long n = (long long)blockIdx.x * 4 + wave; n < N; n += (long long)gridDim.x * 4) {       // a wavefront per row
     const float* r = x + n * (long long)D;
     float* o = out + n * (long long)D;
-    float ss = 0.0f;
-    if constexpr (VEC) {
-      for (unsigned d = 4u * lane; d < D; d += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(r + d);
-        ss = __builtin_fmaf(v.x, v.x, ss);
-        ss = __builtin_fmaf(v.y, v.y, ss);
-        ss = __builtin_fmaf(v.z, v.z, ss);
-        ss = __builtin_fmaf(v.w, v.w, ss);
-      }
-    } else {                                 // the same elements per lane in the same order: the same bits as the 16-byte path
-      for (unsigned d = 4u * lane; d < D; d += 256)
-        for (unsigned j = d; j < min(d + 4u, D); ++j) ss = __builtin_fmaf(r[j], r[j], ss);
-    }
-    ss = eat::wave_sum(ss);                  // every load of the row has landed here: out may be x
+    const float ss = row_sumsq<VEC>(r, D, lane);      // every load of the row has landed here: out may be x
     const float norm = sqrtf(ss);
     const bool zero = !(ss > 0.0f);
     if constexpr (VEC) {
@@ -389,7 +304,7 @@ extern "C" int eat_embed_search(const float* bank, long long N, int D, const flo
     const ScanArgs a{bank, N, D, queries + (size_t)q0 * D, Qg, k, skip ? skip + 2 * q0 : nullptr, ws_s, ws_i, (hipStream_t)stream};
     const int rc = vec ? launch_scan_g<true>(a, G, qlds) : launch_scan_g<false>(a, G, qlds);
     if (rc != EAT_OK) return rc;
-    hipLaunchKernelGGL(search_merge_kernel, dim3(Qg), dim3(kBlocks), 0, (hipStream_t)stream, ws_s, ws_i, k, score + (size_t)q0 * k,
+    hipLaunchKernelGGL(search_merge_kernel<kBlocks>, dim3(Qg), dim3(kBlocks), 0, (hipStream_t)stream, ws_s, ws_i, k, score + (size_t)q0 * k,
                        index + (size_t)q0 * k);
     const int rc2 = eat::check_launch("eat_embed_search");
     if (rc2 != EAT_OK) return rc2;

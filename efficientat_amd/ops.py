@@ -2228,6 +2228,87 @@ def embed_search(bank, queries, k, skip=None):
     return score, index
 
 
+# ------------------------------------------------------------------ the 8-bit search index (include/eat_search_q8.h)
+SEARCH_Q8_MAX_D = 131072
+# geometry of csrc/search_q8.hip (kBlocks, kMaxGroup, kTileRows = 16 rows per wavefront x 8 wavefronts)
+SEARCH_Q8_BLOCKS, SEARCH_Q8_GROUP, SEARCH_Q8_TILE_ROWS = 256, 64, 128
+
+_SEARCH_Q8_WS = {}           # (device, Q, k) -> workspace of eat_embed_search_q8_ws_bytes(Q, k) bytes
+
+
+def q8_ld(D):
+    """Row stride in bytes of q8 codes of D values: D rounded up to a multiple of 16."""
+    return (int(D) + 15) // 16 * 16
+
+
+def _dev_q8(fn, codes, scale, D, what):
+    """Checks one q8 matrix - codes (N, ld) int8 with ld >= D a multiple of 16, scale (N,) fp32 -> (codes pointer, ld)."""
+    if codes.dim() != 2 or not codes.is_cuda or codes.dtype != torch.int8 or not codes.is_contiguous():
+        raise _lib.EatHipError(f"{fn}: {what} codes must be a contiguous (N, ld) int8 GPU tensor (got {codes.dtype}, "
+                               f"{tuple(codes.shape)}, on {codes.device})")
+    ld = codes.shape[1]
+    if ld < D or ld % 16 != 0 or codes.data_ptr() % 16 != 0:
+        raise _lib.EatHipError(f"{fn}: {what} codes need a 16-byte aligned base and a row stride that is a multiple of 16, "
+                               f"at least D = {D} (got {ld})")
+    if scale.shape != (codes.shape[0],) or scale.device != codes.device:
+        raise _lib.EatHipError(f"{fn}: {what} scale must be ({codes.shape[0]},) on {codes.device} (got {tuple(scale.shape)} "
+                               f"on {scale.device})")
+    _dev(scale, f"{what} scale")
+    return codes.data_ptr(), ld
+
+
+def rows_quantize_q8(x, normalize=True, codes=None, scale=None):
+    """x (N, D) fp32 -> (codes (N, ld) int8, scale (N,) fp32), ld = `q8_ld(D)`: row n stands for scale[n] * codes[n, :D].
+    normalize: divide each row by its L2 norm first, with the bits of `rows_normalize`.  scale = max |row| / 127,
+    code = rint(value / scale) in [-127, 127]; a zero row has scale 0 and zero codes; bytes [D, ld) are stored as zeros.
+    codes, scale: None or where to store (rows of a resident bank)."""
+    if x.dim() != 2 or not 1 <= x.shape[1] <= SEARCH_Q8_MAX_D:
+        raise _lib.EatHipError(f"rows_quantize_q8: x must be (N, 1 <= D <= {SEARCH_Q8_MAX_D}), got {tuple(x.shape)}")
+    px = _dev(x, "x")
+    N, D = x.shape
+    if codes is None:
+        codes = torch.empty((N, q8_ld(D)), device=x.device, dtype=torch.int8)
+    if scale is None:
+        scale = torch.empty((N,), device=x.device, dtype=torch.float32)
+    if codes.shape[0] != N or codes.device != x.device:
+        raise _lib.EatHipError(f"rows_quantize_q8: codes must have {N} rows on {x.device} (got {tuple(codes.shape)} on {codes.device})")
+    pc, ld = _dev_q8("rows_quantize_q8", codes, scale, D, "output")
+    _lib.call("eat_rows_quantize_q8", px, N, D, 1 if normalize else 0, pc, ld, scale.data_ptr(), _stream())
+    return codes, scale
+
+
+def embed_search_q8(codes, scale, D, qcodes, qscale, k, skip=None):
+    """`embed_search` over a q8 bank: codes (N, ld) int8 and scale (N,), queries qcodes (Q, qld) and qscale (Q,), both of D
+    values (`rows_quantize_q8`) -> (score (Q, k) fp32, index (Q, k) int32).  score = float(integer dot product of the codes)
+    * (qscale * scale): exact integer arithmetic on the matrix cores, so equal rows tie exactly.  The bank is read once per
+    group of up to 64 queries."""
+    D, k = int(D), int(k)
+    if not 1 <= D <= SEARCH_Q8_MAX_D:
+        raise _lib.EatHipError(f"embed_search_q8: need 1 <= D <= {SEARCH_Q8_MAX_D} (got {D})")
+    pb, ld = _dev_q8("embed_search_q8", codes, scale, D, "bank")
+    pq, qld = _dev_q8("embed_search_q8", qcodes, qscale, D, "query")
+    if qcodes.device != codes.device:
+        raise _lib.EatHipError(f"embed_search_q8: bank lives on {codes.device}, queries on {qcodes.device}")
+    if codes.device.index != torch.cuda.current_device():
+        raise _lib.EatHipError(f"embed_search_q8: the bank lives on {codes.device} but the current device is "
+                               f"cuda:{torch.cuda.current_device()}")
+    N, Q, dev = codes.shape[0], qcodes.shape[0], codes.device
+    if not 1 <= k <= SEARCH_MAX_K or not 1 <= Q <= SEARCH_MAX_Q or N < 1:
+        raise _lib.EatHipError(f"embed_search_q8: need 1 <= k <= {SEARCH_MAX_K}, 1 <= Q <= {SEARCH_MAX_Q} and N >= 1 "
+                               f"(got k={k}, Q={Q}, N={N})")
+    skip_d = None if skip is None else check_skip(skip, Q).to(dev)
+    ws = _SEARCH_Q8_WS.get((dev, Q, k))
+    if ws is None:
+        if len(_SEARCH_Q8_WS) >= 64:
+            _SEARCH_Q8_WS.clear()
+        ws = _SEARCH_Q8_WS[(dev, Q, k)] = torch.empty(_lib.lib().eat_embed_search_q8_ws_bytes(Q, k), device=dev, dtype=torch.uint8)
+    score = torch.empty((Q, k), device=dev, dtype=torch.float32)
+    index = torch.empty((Q, k), device=dev, dtype=torch.int32)
+    _lib.call("eat_embed_search_q8", pb, ld, scale.data_ptr(), N, D, pq, qld, qscale.data_ptr(), Q, k,
+              None if skip_d is None else skip_d.data_ptr(), ws.data_ptr(), ws.numel(), score.data_ptr(), index.data_ptr(), _stream())
+    return score, index
+
+
 # ------------------------------------------------------------------ attention-pooling head (models/mn/attention_pooling.py:9-56)
 def pitch4(T):
     """Row pitch of the head's (B, rows, T) tensors: T rounded up to a multiple of 4 (16-byte row pieces of the 1x1 kernels)."""

@@ -10,6 +10,12 @@ CPU path - an index without a device keeps books, saves and loads, and refuses t
 
 On disk an index is a directory: ``emb.npy`` (N, D) fp32 rows as stored (normalised), ``file.npy`` (N,) int32 file id per
 row, ``time_ms.npy`` (N,) float64 (-1 for a scene row), ``names.txt`` one file name per line, ``meta.json``.
+
+storage="q8" keeps a quarter of the bytes: each normalised row as int8 codes and one fp32 scale (``eat_rows_quantize_q8``,
+include/eat_search_q8.h), searched by ``eat_embed_search_q8`` with exact integer dot products - up to 64 queries per pass
+over the bank instead of 16.  Scores are those of the quantised rows: within about 1e-3 of the cosine at D = 2184 (DESIGN
+1.2b).  On disk ``codes.npy`` (N, D) int8 and ``scale.npy`` (N,) float32 take the place of ``emb.npy``, and ``meta.json`` has
+version 2 and one more entry, "storage": "q8".  The fp32 index is the default and writes what it always wrote.
 """
 import json
 import os
@@ -20,6 +26,8 @@ import torch
 from . import _lib, ops
 
 VERSION = 1
+VERSION_Q8 = 2               # meta.json of a q8 index: META_KEYS and "storage"
+STORAGES = ("fp32", "q8")
 KINDS = ("scene", "timestamps")
 META_KEYS = ("version", "D", "kind", "model_name", "layers", "clip_seconds", "hop_ms", "width_ms")
 
@@ -33,29 +41,42 @@ class EmbeddingIndex:
     """D       embedding size
     device  where the bank lives; None: on the CPU, for bookkeeping, `save` and `load` only - `add` then stores the rows AS
             GIVEN (rows downloaded from another index; nothing normalises on the CPU) and `search` raises EatHipError
-    meta    entries of `META_KEYS` to record (kind, model_name, layers, clip_seconds, hop_ms, width_ms)"""
+    meta    entries of `META_KEYS` to record (kind, model_name, layers, clip_seconds, hop_ms, width_ms)
+    storage "fp32": the rows as they are; "q8": int8 codes and one scale per row - rows are quantised by a kernel, so without
+            a device a q8 index loads, saves and keeps books, and `add` raises EatHipError like `search`"""
 
-    def __init__(self, D, device=None, meta=None):
+    def __init__(self, D, device=None, meta=None, storage="fp32"):
         if int(D) < 1:
             raise ValueError(f"EmbeddingIndex: need D >= 1 (got {D})")
+        if storage not in STORAGES:
+            raise ValueError(f"EmbeddingIndex: storage must be one of {STORAGES} (got {storage!r})")
+        if storage == "q8" and int(D) > ops.SEARCH_Q8_MAX_D:
+            raise ValueError(f"EmbeddingIndex: q8 storage needs D <= {ops.SEARCH_Q8_MAX_D} (got {D})")
+        self.storage = storage
         self.D = int(D)
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
             raise ValueError(f"EmbeddingIndex: device must be a GPU or None (got {self.device})")
         if self.device is not None and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.meta = _default_meta(self.D)
+        version = VERSION_Q8 if storage == "q8" else VERSION
+        self.meta = dict(_default_meta(self.D), version=version)
         for key, value in (meta or {}).items():
             if key not in META_KEYS:
                 raise ValueError(f"EmbeddingIndex: unknown meta entry '{key}' (known: {', '.join(META_KEYS)})")
             self.meta[key] = value
-        if self.meta["version"] != VERSION or self.meta["D"] != self.D or self.meta["kind"] not in KINDS:
-            raise ValueError(f"EmbeddingIndex: meta needs version = {VERSION}, D = {self.D} and kind in {KINDS} (got {self.meta})")
+        if self.meta["version"] != version or self.meta["D"] != self.D or self.meta["kind"] not in KINDS:
+            raise ValueError(f"EmbeddingIndex: meta needs version = {version}, D = {self.D} and kind in {KINDS} (got {self.meta})")
         self.names = []
         self._ranges = {}                                        # name -> (lo, hi)
         self._file = np.zeros(0, dtype=np.int32)
         self._time = np.zeros(0, dtype=np.float64)
-        self._bank = torch.empty((0, self.D), dtype=torch.float32, device=self.device or "cpu")
+        self._bank = self._codes = self._scale = None             # fp32: _bank (cap, D); q8: _codes (cap, ld) int8, _scale (cap,)
+        if storage == "q8":
+            self._codes = torch.empty((0, ops.q8_ld(self.D)), dtype=torch.int8, device=self.device or "cpu")
+            self._scale = torch.empty((0,), dtype=torch.float32, device=self.device or "cpu")
+        else:
+            self._bank = torch.empty((0, self.D), dtype=torch.float32, device=self.device or "cpu")
         self._n = 0
 
     # -- bookkeeping -----------------------------------------------------------------------------------------------------
@@ -64,8 +85,24 @@ class EmbeddingIndex:
 
     @property
     def bank(self):
-        """The rows as stored, (N, D) fp32 on the index's device (a view of the resident buffer)."""
+        """The rows as stored, (N, D) fp32 on the index's device (a view of the resident buffer); fp32 storage only."""
+        if self.storage != "fp32":
+            raise ValueError(f"EmbeddingIndex: an index of storage '{self.storage}' has no fp32 bank (see `codes` and `scales`)")
         return self._bank[:self._n]
+
+    @property
+    def codes(self):
+        """q8 storage: the codes as stored, (N, ld) int8 with ld = D rounded up to 16 and zeros from column D on (a view)."""
+        if self.storage != "q8":
+            raise ValueError(f"EmbeddingIndex: an index of storage '{self.storage}' has no codes (see `bank`)")
+        return self._codes[:self._n]
+
+    @property
+    def scales(self):
+        """q8 storage: (N,) fp32, row n stands for scales[n] * codes[n, :D] (a view)."""
+        if self.storage != "q8":
+            raise ValueError(f"EmbeddingIndex: an index of storage '{self.storage}' has no scales (see `bank`)")
+        return self._scale[:self._n]
 
     @property
     def file_ids(self):
@@ -82,7 +119,8 @@ class EmbeddingIndex:
 
     def add(self, emb, name, times_ms=None):
         """One file's rows: emb (n >= 1, D), times_ms None (scene rows) or (n,) >= 0 -> the row range (lo, hi).  On a device
-        the rows are L2-normalised by `ops.rows_normalize` straight into the resident bank, which grows by doubling."""
+        the rows are L2-normalised by `ops.rows_normalize` straight into the resident bank, which grows by doubling; a q8
+        index normalises and quantises them in one launch of `ops.rows_quantize_q8`, straight into its codes and scales."""
         name = str(name)
         if name in self._ranges:
             raise ValueError(f"EmbeddingIndex: a file named '{name}' is in the index already")
@@ -105,8 +143,23 @@ class EmbeddingIndex:
             raise ValueError(f"EmbeddingIndex: '{name}' brings {kind} rows into an index of {self.meta['kind']} rows")
         if self._n + n > 2 ** 31 - 1:
             raise ValueError("EmbeddingIndex: more than 2^31 - 1 rows")
+        if self.storage == "q8" and self.device is None:
+            raise _lib.EatHipError("EmbeddingIndex.add needs a q8 index on a GPU: rows are quantised by a kernel and "
+                                   "efficientat_amd has no CPU path (load it with device='cuda')")
         self.meta["kind"] = kind
         lo, hi = self._n, self._n + n
+        if self.storage == "q8":
+            self._add_q8(emb, lo, hi)
+        else:
+            self._add_fp32(emb, lo, hi)
+        self._file = np.concatenate((self._file, np.full(n, len(self.names), dtype=np.int32)))
+        self._time = np.concatenate((self._time, times))
+        self.names.append(name)
+        self._ranges[name] = (lo, hi)
+        self._n = hi
+        return lo, hi
+
+    def _add_fp32(self, emb, lo, hi):
         if hi > self._bank.shape[0]:
             grown = torch.empty((max(hi, 2 * self._bank.shape[0], 64), self.D), dtype=torch.float32, device=self._bank.device)
             grown[:lo] = self._bank[:lo]
@@ -117,12 +170,32 @@ class EmbeddingIndex:
         else:
             with torch.cuda.device(self.device):
                 ops.rows_normalize(emb, out=self._bank[lo:hi])
-        self._file = np.concatenate((self._file, np.full(n, len(self.names), dtype=np.int32)))
-        self._time = np.concatenate((self._time, times))
-        self.names.append(name)
-        self._ranges[name] = (lo, hi)
-        self._n = hi
-        return lo, hi
+
+    def _add_q8(self, emb, lo, hi, normalize=True):
+        cap = self._codes.shape[0]
+        if hi > cap:
+            cap = max(hi, 2 * cap, 64)
+            codes = torch.empty((cap, self._codes.shape[1]), dtype=torch.int8, device=self.device)
+            scale = torch.empty((cap,), dtype=torch.float32, device=self.device)
+            codes[:lo] = self._codes[:lo]
+            scale[:lo] = self._scale[:lo]
+            self._codes, self._scale = codes, scale
+        with torch.cuda.device(self.device):
+            ops.rows_quantize_q8(emb.to(device=self.device, dtype=torch.float32).contiguous(), normalize=normalize,
+                                 codes=self._codes[lo:hi], scale=self._scale[lo:hi])
+
+    def quantized(self):
+        """The q8 index of this fp32 index's stored rows on the same device: they are normalised already, so they are
+        quantised as they are, and the books are copied."""
+        if self.storage != "fp32" or self.device is None:
+            raise ValueError("EmbeddingIndex.quantized: needs an fp32 index on a GPU")
+        meta = {key: value for key, value in self.meta.items() if key != "version"}
+        out = EmbeddingIndex(self.D, device=self.device, meta=meta, storage="q8")
+        if self._n:
+            out._add_q8(self.bank, 0, self._n, normalize=False)
+        out._n = self._n
+        out._file, out._time, out.names, out._ranges = self._file.copy(), self._time.copy(), list(self.names), dict(self._ranges)
+        return out
 
     # -- search ----------------------------------------------------------------------------------------------------------
     def check_extractor(self, extractor):
@@ -140,7 +213,8 @@ class EmbeddingIndex:
         """queries (Q, D), k -> (score (Q, k) fp32, index (Q, k) int32) on the device: the k rows of largest cosine score per
         query in descending order, equal scores by ascending row, (-inf, -1) where fewer than k rows are eligible.
         exclude: per query, None or the name of a file whose rows are not eligible.  The queries are normalised by the
-        kernel that normalised the bank.  extractor: where the queries come from, checked by `check_extractor`."""
+        kernel that normalised the bank (a q8 index quantises them as it quantised its rows, and the scores are those of the
+        quantised vectors).  extractor: where the queries come from, checked by `check_extractor`."""
         if self.device is None:
             raise _lib.EatHipError("EmbeddingIndex.search needs the index on a GPU: efficientat_amd has no CPU path "
                                    "(load it with device='cuda')")
@@ -161,8 +235,11 @@ class EmbeddingIndex:
                 raise ValueError(f"EmbeddingIndex: exclude must hold one name or None per query ({Q}), got {len(exclude)}")
             skip = [(0, 0) if name is None else self.row_range(name) for name in exclude]
         with torch.cuda.device(self.device):
-            qn = ops.rows_normalize(queries.to(device=self.device, dtype=torch.float32).contiguous())
-            return ops.embed_search(self.bank, qn, k, skip)
+            queries = queries.to(device=self.device, dtype=torch.float32).contiguous()
+            if self.storage == "q8":
+                qcodes, qscale = ops.rows_quantize_q8(queries, normalize=True)
+                return ops.embed_search_q8(self.codes, self.scales, self.D, qcodes, qscale, k, skip)
+            return ops.embed_search(self.bank, ops.rows_normalize(queries), k, skip)
 
     def hits(self, score, index):
         """(score, index) of `search` -> per query a host list of {"name", "time_ms" (None for a scene row), "row", "score"},
@@ -185,13 +262,20 @@ class EmbeddingIndex:
     # -- disk ------------------------------------------------------------------------------------------------------------
     def save(self, path):
         os.makedirs(path, exist_ok=True)
-        np.save(os.path.join(path, "emb.npy"), self.bank.cpu().numpy())
+        if self.storage == "q8":
+            np.save(os.path.join(path, "codes.npy"), np.ascontiguousarray(self.codes[:, :self.D].cpu().numpy()))
+            np.save(os.path.join(path, "scale.npy"), self.scales.cpu().numpy())
+        else:
+            np.save(os.path.join(path, "emb.npy"), self.bank.cpu().numpy())
         np.save(os.path.join(path, "file.npy"), self._file)
         np.save(os.path.join(path, "time_ms.npy"), self._time)
         with open(os.path.join(path, "names.txt"), "w") as f:
             f.write("".join(name + "\n" for name in self.names))
         with open(os.path.join(path, "meta.json"), "w") as f:
-            json.dump({key: self.meta[key] for key in META_KEYS}, f, indent=1)
+            meta = {key: self.meta[key] for key in META_KEYS}
+            if self.storage == "q8":
+                meta["storage"] = "q8"
+            json.dump(meta, f, indent=1)
             f.write("\n")
 
     @classmethod
@@ -218,28 +302,58 @@ class EmbeddingIndex:
             meta = json.loads(read("meta.json", text))
         except json.JSONDecodeError as e:
             raise bad(f"meta.json is not JSON ({e})") from None
+        if isinstance(meta, dict) and meta.get("version") == VERSION_Q8:
+            if set(meta) != set(META_KEYS) | {"storage"}:
+                raise bad(f"meta.json of version {VERSION_Q8} must hold exactly the entries {', '.join(META_KEYS)}, storage")
+            if meta["storage"] != "q8":
+                raise bad(f"meta.json of version {VERSION_Q8} needs storage = 'q8' (got {meta['storage']!r})")
+            meta = {key: meta[key] for key in META_KEYS}
+            return cls._load_rest(path, device, meta, "q8", bad, read, text)
         if not isinstance(meta, dict) or set(meta) != set(META_KEYS):
             raise bad(f"meta.json must hold exactly the entries {', '.join(META_KEYS)}")
         if meta["version"] != VERSION:
             raise bad(f"meta.json has version {meta['version']!r}, this code reads version {VERSION}")
+        return cls._load_rest(path, device, meta, "fp32", bad, read, text)
+
+    @classmethod
+    def _load_rest(cls, path, device, meta, storage, bad, read, text):
+        """`load` past meta.json's entries and version: the arrays, and the checks on them."""
         if not isinstance(meta["D"], int) or isinstance(meta["D"], bool) or meta["D"] < 1 or meta["kind"] not in KINDS:
             raise bad(f"meta.json needs an integer D >= 1 and kind in {KINDS} (got D = {meta['D']!r}, kind = {meta['kind']!r})")
         D = meta["D"]
-        emb = read("emb.npy", lambda p: np.load(p, allow_pickle=False))
+        if storage == "q8":
+            if D > ops.SEARCH_Q8_MAX_D:
+                raise bad(f"meta.json of a q8 index needs D <= {ops.SEARCH_Q8_MAX_D} (got {D})")
+            emb = read("codes.npy", lambda p: np.load(p, allow_pickle=False))
+            scale = read("scale.npy", lambda p: np.load(p, allow_pickle=False))
+        else:
+            emb = read("emb.npy", lambda p: np.load(p, allow_pickle=False))
         file = read("file.npy", lambda p: np.load(p, allow_pickle=False))
         time = read("time_ms.npy", lambda p: np.load(p, allow_pickle=False))
         names = read("names.txt", text).split("\n")
         if names[-1] != "":
             raise bad("names.txt does not end with a newline")
         names = names[:-1]
-        if emb.ndim != 2 or emb.shape[1] != D or emb.dtype != np.float32:
+        if storage == "q8":
+            if emb.ndim != 2 or emb.shape[1] != D or emb.dtype != np.int8:
+                raise bad(f"codes.npy must be (N, {D}) int8 (got {emb.shape} {emb.dtype})")
+            if scale.shape != (emb.shape[0],) or scale.dtype != np.float32:
+                raise bad(f"scale.npy must be ({emb.shape[0]},) float32 (got {scale.shape} {scale.dtype})")
+        elif emb.ndim != 2 or emb.shape[1] != D or emb.dtype != np.float32:
             raise bad(f"emb.npy must be (N, {D}) float32 (got {emb.shape} {emb.dtype})")
         N = emb.shape[0]
         if file.shape != (N,) or file.dtype != np.int32:
             raise bad(f"file.npy must be ({N},) int32 (got {file.shape} {file.dtype})")
         if time.shape != (N,) or time.dtype != np.float64:
             raise bad(f"time_ms.npy must be ({N},) float64 (got {time.shape} {time.dtype})")
-        if not bool(np.isfinite(emb).all()):
+        if storage == "q8":
+            if bool((emb == -128).any()):
+                raise bad("codes.npy holds a code outside [-127, 127]")
+            if not bool(np.isfinite(scale).all()) or bool((scale < 0).any()):
+                raise bad("scale.npy holds a scale that is negative or not finite")
+            if bool(((scale == 0)[:, None] & (emb != 0)).any()):
+                raise bad("codes.npy holds non-zero codes in a row whose scale is 0")
+        elif not bool(np.isfinite(emb).all()):
             raise bad("emb.npy holds a value that is not finite")
         if len(set(names)) != len(names) or any(name == "" for name in names):
             raise bad("names.txt holds an empty or a repeated name")
@@ -253,8 +367,14 @@ class EmbeddingIndex:
         scene = meta["kind"] == "scene"
         if not bool(np.isfinite(time).all()) or (scene and not bool((time == -1.0).all())) or (not scene and bool((time < 0).any())):
             raise bad(f"time_ms.npy must hold -1 for every row of a scene index and times >= 0 otherwise (kind = {meta['kind']})")
-        index = cls(D, device=device, meta=meta)
-        index._bank = torch.from_numpy(np.ascontiguousarray(emb)).to(index.device or "cpu")
+        index = cls(D, device=device, meta=meta, storage=storage)
+        if storage == "q8":
+            padded = np.zeros((N, ops.q8_ld(D)), dtype=np.int8)
+            padded[:, :D] = emb
+            index._codes = torch.from_numpy(padded).to(index.device or "cpu")
+            index._scale = torch.from_numpy(scale.copy()).to(index.device or "cpu")
+        else:
+            index._bank = torch.from_numpy(np.ascontiguousarray(emb)).to(index.device or "cpu")
         index._n = N
         index._file, index._time, index.names = file.copy(), time.copy(), names
         bounds = np.flatnonzero(np.diff(file)) + 1 if N else np.zeros(0, dtype=np.int64)
@@ -265,9 +385,11 @@ class EmbeddingIndex:
 
     # -- from audio ------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_recordings(cls, extractor, waves, names, timestamps=False, hop_ms=50.0, width_ms=160.0, model_name=None):
+    def from_recordings(cls, extractor, waves, names, timestamps=False, hop_ms=50.0, width_ms=160.0, model_name=None,
+                        storage="fp32"):
         """An index on the extractor's device of the recordings `waves` (what `EmbeddingExtractor.scene_embeddings` takes)
-        named `names`: their scene embeddings, or with timestamps=True their timestamp embeddings (hop_ms, width_ms).  A
+        named `names`, of the given storage: their scene embeddings, or with timestamps=True their timestamp embeddings (hop_ms,
+        width_ms).  A
         scene query searched in a timestamp index finds where the query occurs: choose width_ms near the query's length."""
         names = [str(n) for n in names]
         if len(names) != len(waves):
@@ -275,7 +397,7 @@ class EmbeddingIndex:
         meta = {"kind": "timestamps" if timestamps else "scene", "model_name": model_name,
                 "layers": [int(i) for i in extractor.layers], "clip_seconds": float(extractor.clip_seconds),
                 "hop_ms": float(hop_ms) if timestamps else None, "width_ms": float(width_ms) if timestamps else None}
-        index = cls(extractor.scene_embedding_size, device=extractor.device, meta=meta)
+        index = cls(extractor.scene_embedding_size, device=extractor.device, meta=meta, storage=storage)
         if timestamps:
             for name, (emb, t_ms) in zip(names, extractor.timestamp_embeddings(waves, hop_ms=hop_ms, width_ms=width_ms)):
                 index.add(emb, name, t_ms)

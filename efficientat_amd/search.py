@@ -1,7 +1,9 @@
 """Command line of query-by-example search (efficientat_amd/retrieval.py):
 
     python -m efficientat_amd.search index --audio_path A.wav B.wav ... --out idx/ [--timestamps [--hop_ms 50 --width_ms 160]]
+                                           [--storage {fp32,q8}]
     python -m efficientat_amd.search query --index idx/ --audio_path q.wav ... [--k 10] [--exclude_self] [--json]
+    python -m efficientat_amd.search convert --index idx/ --out idx_q8/ --storage q8
 
 Both take the model arguments of `python -m efficientat_amd.embed` (--model_name | --checkpoint [--width], --clip_seconds,
 --batch_windows) plus --layers (feature-map indices, default all); `query` refuses an index built with other layers,
@@ -13,7 +15,12 @@ SCENE embedding as the query vector.  Against a scene index that answers "which 
 a timestamp index, "where in these recordings does something like this clip occur" - build that index with --width_ms near
 the query clips' length, so that a row averages about as much sound as the query does.  --exclude_self leaves out the rows
 of the index file with the query's own path.  --json prints one line per query:
-{"audio_path", "hits": [{"name", "time_ms", "score"}, ...]} (time_ms null in a scene index); without it, a small table.
+{"audio_path", "storage", "hits": [{"name", "time_ms", "score"}, ...]} (time_ms null in a scene index); without it, a small
+table.
+
+--storage q8 keeps each row as int8 codes and one scale, a quarter of the bytes on disk and in GPU memory, and searches
+them with integer matrix instructions; scores are those of the quantised vectors.  `query` reads the storage from the
+index.  `convert` writes the q8 index of an existing fp32 index's rows without touching the audio again.
 """
 import argparse
 import contextlib
@@ -41,18 +48,25 @@ def parser():
     pi.add_argument("--timestamps", action="store_true", help="one row every hop_ms instead of one row per file")
     pi.add_argument("--hop_ms", type=float, default=50.0)
     pi.add_argument("--width_ms", type=float, default=160.0)
+    pi.add_argument("--storage", choices=("fp32", "q8"), default="fp32", help="how rows are kept: fp32, or int8 codes + a scale")
     pq = sub.add_parser("query", help="search an index for what sounds like the given WAV files")
     _model_arguments(pq)
     pq.add_argument("--index", type=str, required=True, help="directory that `index` wrote")
     pq.add_argument("--k", type=int, default=10, help="hits per query (1 to 128)")
     pq.add_argument("--exclude_self", action="store_true", help="leave out the index file with the query's own path")
     pq.add_argument("--json", action="store_true", help="one JSON line per query")
+    pc = sub.add_parser("convert", help="write the q8 index of an fp32 index's rows")
+    pc.add_argument("--index", type=str, required=True, help="directory that `index` wrote (fp32)")
+    pc.add_argument("--out", type=str, required=True, help="directory to write")
+    pc.add_argument("--storage", choices=("q8",), required=True, help="storage of the index to write")
     return p
 
 
 def parse(argv=None):
     p = parser()
     args = p.parse_args(argv)
+    if args.command == "convert":
+        return args
     if len(set(args.audio_path)) != len(args.audio_path) and args.command == "index":
         p.error("--audio_path names a file twice: a name is in an index once")
     if args.command == "query" and not 1 <= args.k <= 128:
@@ -84,13 +98,23 @@ def _extractor(args):
 def main(argv=None):
     args = parse(argv)
     from .retrieval import EmbeddingIndex
+    if args.command == "convert":
+        index = EmbeddingIndex.load(args.index, device="cuda")
+        if index.storage != "fp32":
+            print(f"{args.index}: the index has storage {index.storage} already", file=sys.stderr)
+            return 2
+        index = index.quantized()
+        index.save(args.out)
+        print(f"{args.out}: {len(index)} rows x {index.D} of {len(index.names)} files ({index.meta['kind']}, {index.storage})")
+        return 0
     extractor = _extractor(args)
     waves = [extractor.load_waveform(path) for path in args.audio_path]
     if args.command == "index":
         index = EmbeddingIndex.from_recordings(extractor, waves, args.audio_path, timestamps=args.timestamps, hop_ms=args.hop_ms,
-                                               width_ms=args.width_ms, model_name=None if args.checkpoint else args.model_name)
+                                               width_ms=args.width_ms, model_name=None if args.checkpoint else args.model_name,
+                                               storage=args.storage)
         index.save(args.out)
-        print(f"{args.out}: {len(index)} rows x {index.D} of {len(index.names)} files ({index.meta['kind']})")
+        print(f"{args.out}: {len(index)} rows x {index.D} of {len(index.names)} files ({index.meta['kind']}, {index.storage})")
         return 0
 
     index = EmbeddingIndex.load(args.index, device=extractor.device)
@@ -101,7 +125,7 @@ def main(argv=None):
     score, rows = index.search(extractor.scene_embeddings(waves), args.k, exclude=exclude)
     for path, found in zip(args.audio_path, index.hits(score, rows)):
         if args.json:
-            print(json.dumps({"audio_path": path, "hits": [{"name": h["name"], "time_ms": h["time_ms"], "score": h["score"]} for h in found]}))
+            print(json.dumps({"audio_path": path, "storage": index.storage, "hits": [{"name": h["name"], "time_ms": h["time_ms"], "score": h["score"]} for h in found]}))
         else:
             print(path)
             for rank, h in enumerate(found):
