@@ -362,31 +362,80 @@ extern "C" int eat_dw_conv_dyn_dgrad(const float* dz, const float* w_bc, const f
   return dw_dgrad_impl(dz, w_bc, res, dx, B, C, F, T, Fo, To, k, stride, 1, stream);
 }
 
+// Which kernel a weight-gradient call runs on and how it cuts the batch: dw_wgrad_impl launches what this answers and
+// eat_dw_wgrad_split reports it.  (k / stride outside {3, 5} x {1, 2} end on the per-channel kernel's EAT_EINVAL.)
+static void dw_wgrad_plan(int B, int C, int XC, int F, int T, int Fo, int To, int k, int stride, int per_sample,
+                          eat::DwWgradPlan* p) {
+  // register-resident kernels (dw_plane.hip); 1 = geometry not instantiated
+  if (XC == C && eat::dw_plane_wgrad_plan(eat::DwGeom{B, C, F, T, Fo, To, k, stride}, per_sample != 0, p) == 0) return;
+  *p = eat::DwWgradPlan{};
+  p->npw = 1;
+  if (XC == C && !per_sample && (k == 3 || k == 5) && (stride == 1 || stride == 2)) {
+    p->kernel = eat::kDwWgColumn;
+    p->TX = To > 32 ? 64 : 32;
+    const int TY = 256 / p->TX;
+    p->ct = (To + p->TX - 1) / p->TX;
+    // ~2048 blocks, but every thread should walk several planes before the block-wide reduction
+    long long want = (2048 + (long long)C * p->ct - 1) / ((long long)C * p->ct);
+    if (want < 1) want = 1;
+    p->bpb = (int)((B + want - 1) / want);
+    if (p->bpb < 4 * TY) p->bpb = 4 * TY < B ? 4 * TY : B;
+    p->slices = (B + p->bpb - 1) / p->bpb;
+    return;
+  }
+  if (XC == 1 && k == 3 && stride == 2 && !per_sample) {
+    p->kernel = eat::kDwWgStem;
+    // ~2048 blocks: (row chunks) x (samples)
+    p->rpb = (int)(((long long)Fo * B + 2047) / 2048);
+    if (p->rpb < 1) p->rpb = 1;
+    p->chunks = (Fo + p->rpb - 1) / p->rpb;
+    return;
+  }
+  p->kernel = eat::kDwWgChannel;
+  // enough blocks to fill the chip: split the batch when there are few channels
+  int splits = (2048 + C - 1) / C;
+  if (splits > B || per_sample) splits = B;
+  p->bpb = (B + splits - 1) / splits;
+  p->slices = (B + p->bpb - 1) / p->bpb;
+}
+
+// Host helper: the kernel of eat_dw_conv_wgrad / eat_dw_conv_wgrad_tf (per_sample = 0) or eat_dw_conv_dyn_wgrad (1) for a
+// shape - 0 whole-plane, 1 tile, 2 column-walking, 3 stem, 4 per-channel - and its split; -1: the call would be refused
+extern "C" int eat_dw_wgrad_split(int B, int C, int XC, int F, int T, int Fo, int To, int k, int stride, int per_sample,
+                                  int* split, int* parts, int* lane_samples) {
+  if (B < 1 || C < 1 || (XC != C && XC != 1) || (k != 3 && k != 5) || (stride != 1 && stride != 2)) return -1;
+  eat::DwWgradPlan pl;
+  dw_wgrad_plan(B, C, XC, F, T, Fo, To, k, stride, per_sample, &pl);
+  int sp = 0, pa = 0;
+  switch (pl.kernel) {
+    case eat::kDwWgPlane: sp = pl.G; pa = (int)(pl.waves / C); break;
+    case eat::kDwWgTile: sp = pl.G; pa = (int)(pl.waves / ((long long)C * pl.n_rc * pl.n_cs)); break;
+    case eat::kDwWgStem: sp = pl.rpb; pa = pl.chunks; break;
+    default: sp = pl.bpb; pa = pl.slices; break;
+  }
+  if (split) *split = sp;
+  if (parts) *parts = pa;
+  if (lane_samples) *lane_samples = pl.npw;
+  return pl.kernel;
+}
+
 static int dw_wgrad_impl(const float* dz, const float* x, float* dw, int B, int C, int XC, int F, int T, int Fo, int To,
                          int k, int stride, int per_sample, eat_stream_t stream, const float* in_a = nullptr,
                          const float* in_b = nullptr, int in_act = 0) {
   if (XC != C && XC != 1) return eat::fail(EAT_EINVAL, "eat_dw_conv_wgrad: x must have C or 1 channels");
   if (in_a && XC != C) return eat::fail(EAT_EINVAL, "eat_dw_conv_wgrad_tf: needs the column-walking kernel");
-  if (XC == C) {
-    // register-resident kernels (dw_plane.hip): every element loaded once; 1 = geometry not instantiated
+  eat::DwWgradPlan pl;
+  dw_wgrad_plan(B, C, XC, F, T, Fo, To, k, stride, per_sample, &pl);
+  if (pl.kernel == eat::kDwWgPlane || pl.kernel == eat::kDwWgTile) {
+    // register-resident kernels (dw_plane.hip): every element loaded once
     eat::DwWgradReq r{}; r.dim = {B, C, F, T, Fo, To, k, stride};
     r.dz = dz; r.x = x; r.dw = dw; r.per_plane = per_sample; r.tf = {in_a, in_b, in_act}; r.stream = (hipStream_t)stream;
-    const int rc = eat::dw_plane_wgrad_try(r);
-    if (rc != 1) return rc;
+    return eat::dw_plane_wgrad_run(r, pl);
   }
-  if (XC == C && !per_sample && (k == 3 || k == 5) && (stride == 1 || stride == 2)) {
+  if (pl.kernel == eat::kDwWgColumn) {
     // column-walking kernel: block = (column tile, channel, batch slice)
-    const int TX = To > 32 ? 64 : 32, TY = 256 / TX;
-    const int ct = (To + TX - 1) / TX;
-    int bpb = per_sample ? 1 : B;
-    if (!per_sample) {
-      // ~2048 blocks, but every thread should walk several planes before the block-wide reduction
-      long long want = (2048 + (long long)C * ct - 1) / ((long long)C * ct);
-      if (want < 1) want = 1;
-      bpb = (int)((B + want - 1) / want);
-      if (bpb < 4 * TY) bpb = 4 * TY < B ? 4 * TY : B;
-    }
-    dim3 grid(ct, C, (B + bpb - 1) / bpb);
+    const int TX = pl.TX, bpb = pl.bpb;
+    dim3 grid(pl.ct, C, pl.slices);
     hipStream_t s = (hipStream_t)stream;
 #define EAT_WGC(KK, SS) hipLaunchKernelGGL((dw_wgrad_col_kernel<KK, SS>), grid, dim3(256), 0, s, dz, x, dw, B, C, F, T, Fo, To, TX, bpb, per_sample, in_a, in_b, in_act)
     if (k == 3 && stride == 1) EAT_WGC(3, 1);
@@ -396,19 +445,13 @@ static int dw_wgrad_impl(const float* dz, const float* x, float* dw, int B, int 
 #undef EAT_WGC
     return eat::check_launch("eat_dw_conv_wgrad");
   }
-  if (XC == 1 && k == 3 && stride == 2 && !per_sample) {
-    // ~2048 blocks: (row chunks) x (samples)
-    int rpb = (int)(((long long)Fo * B + 2047) / 2048);
-    if (rpb < 1) rpb = 1;
-    hipLaunchKernelGGL(stem_wgrad_kernel<16>, dim3((Fo + rpb - 1) / rpb, B), dim3(256), 0, (hipStream_t)stream, dz, x, dw, C, F, T,
-                       Fo, To, rpb);
+  if (pl.kernel == eat::kDwWgStem) {
+    hipLaunchKernelGGL(stem_wgrad_kernel<16>, dim3(pl.chunks, B), dim3(256), 0, (hipStream_t)stream, dz, x, dw, C, F, T,
+                       Fo, To, pl.rpb);
     return eat::check_launch("eat_dw_conv_wgrad(stem)");
   }
-  // enough blocks to fill the chip: split the batch when there are few channels
-  int splits = (2048 + C - 1) / C;
-  if (splits > B || per_sample) splits = B;
-  const int bpb = (B + splits - 1) / splits;
-  dim3 grid(C, (B + bpb - 1) / bpb);
+  const int bpb = pl.bpb;
+  dim3 grid(C, pl.slices);
   hipStream_t s = (hipStream_t)stream;
 #define EAT_WG(KK, SS) hipLaunchKernelGGL((dw_wgrad_kernel<KK, SS>), grid, dim3(256), 0, s, dz, x, dw, B, C, XC, F, T, Fo, To, bpb, per_sample)
   if (k == 3 && stride == 1) EAT_WG(3, 1);

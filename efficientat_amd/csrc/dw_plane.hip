@@ -963,20 +963,9 @@ __global__ __launch_bounds__(256) void dw_tile_wgrad_kernel(const TileWgArgs a) 
 }
 
 template <int K, int S, int RO>
-int launch_tile_wgrad(TileWgArgs a, hipStream_t s) {
-  constexpr int WMAX = S == 1 ? (K == 3 ? 125 : 124) : (K == 3 ? 63 : 62);
-  a.n_cs = (a.To + WMAX - 1) / WMAX;
-  a.WO = (a.To + a.n_cs - 1) / a.n_cs;
-  a.n_rc = (a.Fo + RO - 1) / RO;
-  int G = 1;
-  if (!a.per_plane) {
-    G = 8;
-    while (G > 1 && (long long)a.C * a.n_rc * a.n_cs * ((a.B + G - 1) / G) < 8192) G >>= 1;
-  }
-  a.G = G;
-  const long long waves = (long long)((a.B + G - 1) / G) * a.C * a.n_rc * a.n_cs;
-  if (waves > 0x7fffffffLL) return 1;
-  hipLaunchKernelGGL((dw_tile_wgrad_kernel<K, S, RO>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
+int launch_tile_wgrad(TileWgArgs a, const eat::DwWgradPlan& pl, hipStream_t s) {
+  a.n_cs = pl.n_cs; a.WO = pl.WO; a.n_rc = pl.n_rc; a.G = pl.G;         // (eat::dw_plane_wgrad_plan, with this RO)
+  hipLaunchKernelGGL((dw_tile_wgrad_kernel<K, S, RO>), dim3((unsigned)((pl.waves + 3) / 4)), dim3(256), 0, s, a);
   return eat::check_launch("eat_dw_conv_wgrad(tile)");
 }
 
@@ -1384,26 +1373,13 @@ __global__ __launch_bounds__(256) void dw_bwd_tile_kernel(const DwBwdArgs a, con
 }
 
 template <int K, int S, int RO>
-int launch_dw_bwd(DwBwdArgs a, const float* w, int* h_inner, hipStream_t s, bool ppw = false) {
+int launch_dw_bwd(DwBwdArgs a, const eat::DwBwdPlan& pl, const float* w, int* h_inner, hipStream_t s, bool ppw = false) {
   const bool bn = a.bn.z != nullptr;
-  constexpr int WMAX = S == 1 ? (K == 3 ? 125 : 124) : 62;
-  const int n_cols = S == 1 ? a.T : a.To, n_rows = S == 1 ? a.F : a.Fo;
-  // small planes (BN instances only): whole rows per lane group, 2 or 4 samples per wave; up to 128 columns: one plane per
-  // wave without halo lanes
-  const int lpp = !bn ? 64 : (a.T <= 32 ? 16 : (a.T <= 64 ? 32 : 64));
-  const bool wr = lpp < 64 || (bn && a.T <= 128);
-  const int npw = 64 / lpp;
-  a.n_cs = wr ? 1 : (n_cols + WMAX - 1) / WMAX;
-  a.WO = (n_cols + a.n_cs - 1) / a.n_cs;
-  a.n_rc = (n_rows + RO - 1) / RO;
-  const int nb = (a.B + npw - 1) / npw;
-  int G = 8;
-  while (G > 1 && (long long)a.C * a.n_rc * a.n_cs * ((nb + G - 1) / G) < 8192) G >>= 1;
-  a.G = G;
-  const long long waves = (long long)((nb + G - 1) / G) * a.C * a.n_rc * a.n_cs;
-  if (waves > 0x7fffffffLL) return 1;
+  const int lpp = pl.lpp;
+  const bool wr = pl.wr != 0;
+  a.n_cs = pl.n_cs; a.WO = pl.WO; a.n_rc = pl.n_rc; a.G = pl.G;         // (eat::dw_bwd_plan, with this RO)
   if (h_inner) *h_inner = a.n_rc * a.n_cs;
-  const dim3 grid((unsigned)((waves + 3) / 4));
+  const dim3 grid((unsigned)((pl.waves + 3) / 4));
   // the BatchNorm-on-load instances of one (taps, storage) kind: by lane-group width, whole rows or column strips
 #define EAT_BWD_BN(PPW_, XT_, ZT_)                                                                                               \
   do {                                                                                                                          \
@@ -1443,24 +1419,93 @@ int launch_dw_bwd(DwBwdArgs a, const float* w, int* h_inner, hipStream_t s, bool
 }
 
 template <int K, int S, int CPL, int LPP, int F>
-int launch_plane_wgrad(const PlaneWgArgs& a0, hipStream_t s) {
+int launch_plane_wgrad(const PlaneWgArgs& a0, const eat::DwWgradPlan& pl, hipStream_t s) {
   PlaneWgArgs a = a0;
-  constexpr int NPW = 64 / LPP;
-  // samples per wave: every wave should multiply several planes before its K*K-value reduction, but keep >= ~8 k waves
-  int G = 1;
-  if (!a.per_plane) {
-    G = 8;
-    while (G > 1 && (long long)a.C * ((a.B + NPW * G - 1) / (NPW * G)) < 8192) G >>= 1;
-  }
-  a.G = G;
-  const long long waves = (long long)a.C * ((a.B + NPW * G - 1) / (NPW * G));
-  hipLaunchKernelGGL((dw_plane_wgrad_kernel<K, S, CPL, LPP, F>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
+  static_assert(64 / LPP == 1 || 64 / LPP == 2, "samples side by side in a wave");
+  a.G = pl.G;                                                           // (eat::dw_plane_wgrad_plan, with this LPP)
+  hipLaunchKernelGGL((dw_plane_wgrad_kernel<K, S, CPL, LPP, F>), dim3((unsigned)((pl.waves + 3) / 4)), dim3(256), 0, s, a);
   return eat::check_launch("eat_dw_conv_wgrad(plane)");
+}
+
+// Samples per wave of the training kernels that sum a weight gradient over the batch: a wave should multiply several planes
+// (G sample groups of one tile) before its K*K-value cross-lane reduction, but the launch keeps >= ~8 k waves.
+// tiles: waves per sample group (channels x tiles of a plane), nb: sample groups in the batch.
+int dw_wave_groups(long long tiles, int nb) {
+  int G = 8;
+  while (G > 1 && tiles * ((nb + G - 1) / G) < 8192) G >>= 1;
+  return G;
 }
 
 }  // namespace
 
 namespace eat {
+
+// the five whole-plane weight-gradient instances <K, S, CPL, LPP, F> (dw_plane_wgrad_run's switch) and -1
+static int plane_wgrad_inst(int k, int stride, int F, int T) {
+  if (k == 3 && stride == 1 && F == 8 && T > 32 && T <= 64) return 0;        // <3, 1, 1, 64, 8>
+  if (k == 5 && stride == 1 && F == 16 && T > 64 && T <= 128) return 1;      // <5, 1, 2, 64, 16>
+  if (k == 5 && stride == 2 && F == 8 && T > 32 && T <= 64) return 2;        // <5, 2, 2, 32, 8>
+  if (k == 3 && stride == 2 && F == 16 && T > 64 && T <= 128) return 3;      // <3, 2, 2, 64, 16>
+  if (k == 5 && stride == 1 && F == 4 && T <= 32) return 4;                  // <5, 1, 1, 32, 4>
+  return -1;
+}
+
+int dw_plane_wgrad_plan(const DwGeom& d, bool per_plane, DwWgradPlan* p) {
+  const int k = d.k, stride = d.stride, F = d.F, T = d.T;
+  *p = DwWgradPlan{};
+  p->npw = 1;
+  if ((long long)d.B * d.C > 0x3fffffffLL) return 1;
+  const bool tile_inst = (k == 3 && (stride == 1 || stride == 2)) || (k == 5 && stride == 2);
+  if (T > 128 && (long long)F * T < (1 << 28) && tile_inst) {              // large planes: tiles of rows x column strips
+    const int wmax = stride == 1 ? (k == 3 ? 125 : 124) : (k == 3 ? 63 : 62);
+    const int ro = stride == 1 ? 16 : 8;                                   // (launch_tile_wgrad's RO)
+    p->kernel = kDwWgTile;
+    p->n_cs = (d.To + wmax - 1) / wmax;
+    p->WO = (d.To + p->n_cs - 1) / p->n_cs;
+    p->n_rc = (d.Fo + ro - 1) / ro;
+    const long long tiles = (long long)d.C * p->n_rc * p->n_cs;
+    p->G = per_plane ? 1 : dw_wave_groups(tiles, d.B);
+    p->waves = (long long)((d.B + p->G - 1) / p->G) * tiles;
+    return p->waves > 0x7fffffffLL ? 1 : 0;
+  }
+  p->inst = plane_wgrad_inst(k, stride, F, T);
+  if (p->inst < 0) return 1;
+  p->kernel = kDwWgPlane;
+  p->npw = (p->inst == 2 || p->inst == 4) ? 2 : 1;                          // 64 / LPP
+  const int nb = (d.B + p->npw - 1) / p->npw;
+  p->G = per_plane ? 1 : dw_wave_groups(d.C, nb);
+  p->waves = (long long)d.C * ((nb + p->G - 1) / p->G);
+  return 0;
+}
+
+int dw_bwd_plan(const DwGeom& d, bool bn, DwBwdPlan* p) {
+  const int k = d.k, stride = d.stride, F = d.F, T = d.T, Fo = d.Fo, To = d.To;
+  *p = DwBwdPlan{};
+  if ((long long)d.B * d.C > 0x3fffffffLL || (long long)F * T >= (1 << 28)) return 1;
+  // Measured (MI355X, B = 256): the merged kernel wins on the LARGE planes (64x500 -> 32x250: 1.03 vs 1.47 ms, 32x250:
+  // 0.35 vs 0.53 ms) and loses on the small late-layer planes, where the whole-plane kernels pack one or two planes per
+  // wave with every lane busy (4x32 planes: 0.69 vs 0.35 ms; a wave of this kernel would use 18 of its 64 lanes)
+  if (!bn && T <= 128) return 1;                       // (with the BatchNorm backward on load the small planes gain: fewer passes)
+  if (stride == 1 && (Fo != F || To != T)) return 1;
+  if ((k != 3 && k != 5) || (stride != 1 && stride != 2)) return 1;
+  // 5x5 on planes of <= 4 (output) rows, the last stage of the network: tiles of 4 rows (half the multiply work of RO = 8)
+  p->ro = (bn && k == 5 && (stride == 1 ? F : Fo) <= 4 && T <= 64) ? 4 : 8;      // (RO = 16 needs 246 VGPRs)
+  const int wmax = stride == 1 ? (k == 3 ? 125 : 124) : 62;
+  const int n_cols = stride == 1 ? T : To, n_rows = stride == 1 ? F : Fo;
+  // small planes (BN instances only): whole rows per lane group, 2 or 4 samples per wave; up to 128 columns: one plane per
+  // wave without halo lanes
+  p->lpp = !bn ? 64 : (T <= 32 ? 16 : (T <= 64 ? 32 : 64));
+  p->wr = (p->lpp < 64 || (bn && T <= 128)) ? 1 : 0;
+  const int npw = 64 / p->lpp;
+  p->n_cs = p->wr ? 1 : (n_cols + wmax - 1) / wmax;
+  p->WO = (n_cols + p->n_cs - 1) / p->n_cs;
+  p->n_rc = (n_rows + p->ro - 1) / p->ro;
+  const int nb = (d.B + npw - 1) / npw;
+  const long long tiles = (long long)d.C * p->n_rc * p->n_cs;
+  p->G = dw_wave_groups(tiles, nb);
+  p->waves = (long long)((nb + p->G - 1) / p->G) * tiles;
+  return p->waves > 0x7fffffffLL ? 1 : 0;
+}
 
 // (the kernels' argument structs type every wide tensor float* and an instance reinterprets it by its XT / YT / ZT: here, next
 // to the launch_* that picks the instance, is the one place where a request's void* becomes that float*)
@@ -1492,22 +1537,25 @@ int dw_plane_try(const DwFwdReq& r) {
   return 1;
 }
 
-int dw_plane_wgrad_try(const DwWgradReq& r) {
+int dw_plane_wgrad_run(const DwWgradReq& r, const DwWgradPlan& p) {
   const DwGeom& d = r.dim;
   const int k = d.k, stride = d.stride, F = d.F, T = d.T;
-  if ((long long)d.B * d.C > 0x3fffffffLL) return 1;
-  if (T > 128 && (long long)F * T < (1 << 28)) {
+  if (p.kernel == kDwWgTile) {
     TileWgArgs ta{r.dz, r.x, r.dw, d.B, d.C, F, T, d.Fo, d.To, 0, 0, 0, 1, r.per_plane, r.tf};
-    if (k == 3 && stride == 1) return launch_tile_wgrad<3, 1, 16>(ta, r.stream);
-    if (k == 3 && stride == 2) return launch_tile_wgrad<3, 2, 8>(ta, r.stream);
-    if (k == 5 && stride == 2) return launch_tile_wgrad<5, 2, 8>(ta, r.stream);
+    if (k == 3 && stride == 1) return launch_tile_wgrad<3, 1, 16>(ta, p, r.stream);
+    if (k == 3 && stride == 2) return launch_tile_wgrad<3, 2, 8>(ta, p, r.stream);
+    if (k == 5 && stride == 2) return launch_tile_wgrad<5, 2, 8>(ta, p, r.stream);
+    return 1;
   }
+  if (p.kernel != kDwWgPlane) return 1;
   PlaneWgArgs a{r.dz, r.x, r.dw, d.B, d.C, T, d.To, 1, r.per_plane, r.tf};
-  if (k == 3 && stride == 1 && F == 8 && T > 32 && T <= 64) return launch_plane_wgrad<3, 1, 1, 64, 8>(a, r.stream);
-  if (k == 5 && stride == 1 && F == 16 && T > 64 && T <= 128) return launch_plane_wgrad<5, 1, 2, 64, 16>(a, r.stream);
-  if (k == 5 && stride == 2 && F == 8 && T > 32 && T <= 64) return launch_plane_wgrad<5, 2, 2, 32, 8>(a, r.stream);
-  if (k == 3 && stride == 2 && F == 16 && T > 64 && T <= 128) return launch_plane_wgrad<3, 2, 2, 64, 16>(a, r.stream);
-  if (k == 5 && stride == 1 && F == 4 && T <= 32) return launch_plane_wgrad<5, 1, 1, 32, 4>(a, r.stream);
+  switch (p.inst) {                                        // plane_wgrad_inst
+    case 0: return launch_plane_wgrad<3, 1, 1, 64, 8>(a, p, r.stream);
+    case 1: return launch_plane_wgrad<5, 1, 2, 64, 16>(a, p, r.stream);
+    case 2: return launch_plane_wgrad<5, 2, 2, 32, 8>(a, p, r.stream);
+    case 3: return launch_plane_wgrad<3, 2, 2, 64, 16>(a, p, r.stream);
+    case 4: return launch_plane_wgrad<5, 1, 1, 32, 4>(a, p, r.stream);
+  }
   return 1;
 }
 
@@ -1515,11 +1563,8 @@ int dw_bwd_try(const DwBwdReq& r) {
   const DwGeom& d = r.dim;
   const int k = d.k, stride = d.stride, F = d.F, T = d.T, Fo = d.Fo, To = d.To;
   const DwBnBwd* bn = r.bn;
-  if ((long long)d.B * d.C > 0x3fffffffLL || (long long)F * T >= (1 << 28)) return 1;
-  // Measured (MI355X, B = 256): the merged kernel wins on the LARGE planes (64x500 -> 32x250: 1.03 vs 1.47 ms, 32x250:
-  // 0.35 vs 0.53 ms) and loses on the small late-layer planes, where the whole-plane kernels pack one or two planes per
-  // wave with every lane busy (4x32 planes: 0.69 vs 0.35 ms; a wave of this kernel would use 18 of its 64 lanes)
-  if (!bn && T <= 128) return 1;                       // (with the BatchNorm backward on load the small planes gain: fewer passes)
+  DwBwdPlan pl;
+  if (dw_bwd_plan(d, bn != nullptr, &pl) != 0) return 1;
   DwBwdArgs a{static_cast<const float*>(r.dz), static_cast<const float*>(r.x), static_cast<float*>(r.g), r.dw, r.gpart,
               d.B, d.C, F, T, Fo, To, 0, 0, 0, 1, r.tf,
               DzBn{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, 0, 0}, r.res, r.gzpart, r.store};
@@ -1527,14 +1572,13 @@ int dw_bwd_try(const DwBwdReq& r) {
   if (ppw && !bn) return 1;
   if (bn) a.bn = DzBn{static_cast<const float*>(bn->z), bn->a, bn->b, bn->mean, bn->invstd, bn->gscale, bn->gadd, bn->sums,
                       (double)d.B * Fo * To, bn->act, bn->frozen};
-  if (stride == 1 && (Fo != F || To != T)) return 1;
-  // 5x5 on planes of <= 4 (output) rows, the last stage of the network: tiles of 4 rows (half the multiply work of RO = 8)
-  if (bn && k == 5 && stride == 1 && F <= 4 && T <= 64) return launch_dw_bwd<5, 1, 4>(a, r.w, r.h_inner, r.stream, ppw);
-  if (bn && k == 5 && stride == 2 && Fo <= 4 && T <= 64) return launch_dw_bwd<5, 2, 4>(a, r.w, r.h_inner, r.stream, ppw);
-  if (k == 3 && stride == 1) return launch_dw_bwd<3, 1, 8>(a, r.w, r.h_inner, r.stream, ppw);      // (RO = 16 needs 246 VGPRs)
-  if (k == 5 && stride == 1) return launch_dw_bwd<5, 1, 8>(a, r.w, r.h_inner, r.stream, ppw);
-  if (k == 3 && stride == 2) return launch_dw_bwd<3, 2, 8>(a, r.w, r.h_inner, r.stream, ppw);
-  if (k == 5 && stride == 2) return launch_dw_bwd<5, 2, 8>(a, r.w, r.h_inner, r.stream, ppw);
+  // the instance of the plan's rows per tile (pl.ro: 4 on the 5x5 planes of <= 4 rows, else 8)
+  if (k == 5 && stride == 1 && pl.ro == 4) return launch_dw_bwd<5, 1, 4>(a, pl, r.w, r.h_inner, r.stream, ppw);
+  if (k == 5 && stride == 2 && pl.ro == 4) return launch_dw_bwd<5, 2, 4>(a, pl, r.w, r.h_inner, r.stream, ppw);
+  if (k == 3 && stride == 1) return launch_dw_bwd<3, 1, 8>(a, pl, r.w, r.h_inner, r.stream, ppw);
+  if (k == 5 && stride == 1) return launch_dw_bwd<5, 1, 8>(a, pl, r.w, r.h_inner, r.stream, ppw);
+  if (k == 3 && stride == 2) return launch_dw_bwd<3, 2, 8>(a, pl, r.w, r.h_inner, r.stream, ppw);
+  if (k == 5 && stride == 2) return launch_dw_bwd<5, 2, 8>(a, pl, r.w, r.h_inner, r.stream, ppw);
   return 1;
 }
 
@@ -1557,6 +1601,19 @@ extern "C" int eat_dw_bwd_partials_inner(int F, int T, int Fo, int To, int k, in
   const int n_cols = stride == 1 ? T : To, n_rows = stride == 1 ? F : Fo;
   const int ro = 8;
   return ((n_cols + wmax - 1) / wmax) * ((n_rows + ro - 1) / ro);
+}
+
+// The merged kernel's split of a geometry, as dw_bwd_try launches it (eat::dw_bwd_plan); 1: not on this kernel
+extern "C" int eat_dw_bwd_split(int B, int C, int F, int T, int Fo, int To, int k, int stride, int bn, int* lane_group,
+                                int* whole_rows, int* tile_rows, int* G, int* inner) {
+  eat::DwBwdPlan pl;
+  if (eat::dw_bwd_plan(eat::DwGeom{B, C, F, T, Fo, To, k, stride}, bn != 0, &pl) != 0) return 1;
+  if (lane_group) *lane_group = pl.lpp;
+  if (whole_rows) *whole_rows = pl.wr;
+  if (tile_rows) *tile_rows = pl.ro;
+  if (G) *G = pl.G;
+  if (inner) *inner = pl.n_rc * pl.n_cs;
+  return 0;
 }
 
 // Upper bound of the partial slots per plane the training epilogues write (the host sizes its buffers with it):

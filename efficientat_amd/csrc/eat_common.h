@@ -103,7 +103,20 @@ struct DwFwdReq {
 };
 int dw_plane_try(const DwFwdReq& r);
 struct DwWgradReq { DwGeom dim; const float* dz; const float* x; float* dw; int per_plane; InTf tf; hipStream_t stream; };
-int dw_plane_wgrad_try(const DwWgradReq& r);
+// Where the batch picks the decomposition of the weight-gradient kernels: which kernel runs and its split.  The launchers
+// take their split from these plans and eat_dw_wgrad_split (eat_hip.h) answers from them - one copy of the arithmetic.
+enum DwWgradKernel { kDwWgPlane = 0, kDwWgTile = 1, kDwWgColumn = 2, kDwWgStem = 3, kDwWgChannel = 4 };
+struct DwWgradPlan {
+  int kernel;                    // DwWgradKernel
+  int inst, npw;                 // whole-plane: which of the five instances, samples side by side in a wave (else npw = 1)
+  int n_rc, n_cs, WO;            // tile: row chunks, column strips and strip width of a plane
+  int G; long long waves;        // whole-plane, tile: samples a lane group walks, waves launched
+  int TX, ct;                    // column-walking: columns per block, column tiles
+  int bpb, slices;               // column-walking, per-channel: samples per block, batch slices
+  int rpb, chunks;               // stem: output rows per block, row chunks
+};
+int dw_plane_wgrad_plan(const DwGeom& d, bool per_plane, DwWgradPlan* p);     // 1: no register-resident instance
+int dw_plane_wgrad_run(const DwWgradReq& r, const DwWgradPlan& p);            // p: dw_plane_wgrad_plan's answer for r
 // merged depthwise backward: weight gradient + data gradient + activation-derivative epilogue in one pass
 // bn != NULL: dz is the gradient w.r.t. the activated BatchNorm output of this conv; the BatchNorm + activation backward is
 // evaluated on load from (dz, bn->z) with the channel sums of the reduce pass (sums[0..C) = sum g, [C..2C) = sum g xhat)
@@ -119,6 +132,11 @@ struct DwBwdReq {
   DwStore store; hipStream_t stream;
 };
 int dw_bwd_try(const DwBwdReq& r);
+// the merged kernel's split of a geometry (bn: the BatchNorm-on-load instances): lane-group width, whole rows or column
+// strips, rows per tile, tiles of a plane and G = the groups of 64 / lpp samples a wave walks.  dw_bwd_try launches what this
+// answers and eat_dw_bwd_split (eat_hip.h) reports it.  1: not on the merged kernel.
+struct DwBwdPlan { int lpp, wr, ro, n_rc, n_cs, WO, G; long long waves; };
+int dw_bwd_plan(const DwGeom& d, bool bn, DwBwdPlan* p);
 // stride-2 data gradient on tiles (dim.stride is 2; epi with gz: the training epilogue)
 struct DwDgrad2Req {
   DwGeom dim; const float* dz; const float* w; const float* res; float* dx; int per_plane_w; const DwEpi* epi; hipStream_t stream;

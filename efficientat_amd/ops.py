@@ -655,6 +655,33 @@ def dw_partials_inner(F, T, Fo, To, k, stride, dgrad):
     return int(_lib.lib().eat_dw_partials_inner(F, T, Fo, To, k, stride, 1 if dgrad else 0))
 
 
+def dw_bwd_split(B, C, F, T, Fo, To, k, stride, bn):
+    """How the merged depthwise backward cuts a shape (eat_dw_bwd_split: the launcher's own arithmetic; no device work):
+    None where the geometry is not on that kernel, else {lane_group: 16 / 32 / 64, whole_rows: bool, tile_rows: 4 / 8,
+    G: sample groups a wave walks, inner: tiles per plane}.  bn: the BatchNorm-on-load entry points."""
+    out = [_ct.c_int(0) for _ in range(5)]
+    if _lib.call_rc("eat_dw_bwd_split", B, C, F, T, Fo, To, k, stride, 1 if bn else 0, *[_ct.addressof(o) for o in out]):
+        return None
+    lane_group, whole_rows, tile_rows, G, inner = (o.value for o in out)
+    return {"lane_group": lane_group, "whole_rows": bool(whole_rows), "tile_rows": tile_rows, "G": G, "inner": inner}
+
+
+DW_WGRAD_KERNELS = ("plane", "tile", "column", "stem", "channel")
+
+
+def dw_wgrad_split(B, C, XC, F, T, Fo, To, k, stride, per_sample=False):
+    """Which kernel a depthwise weight-gradient call runs on and how it cuts the batch (eat_dw_wgrad_split; no device work):
+    {kernel: one of DW_WGRAD_KERNELS, split: G (plane, tile) / samples per block (column, channel) / rows per block (stem),
+    parts: sample groups / batch slices / row chunks, lane_samples: samples side by side in a wave}."""
+    out = [_ct.c_int(0) for _ in range(3)]
+    kind = int(_lib.lib().eat_dw_wgrad_split(B, C, XC, F, T, Fo, To, k, stride, 1 if per_sample else 0,
+                                             *[_ct.addressof(o) for o in out]))
+    if kind < 0:
+        raise _lib.EatHipError(f"eat_dw_wgrad_split: no weight-gradient kernel takes C={C} XC={XC} k={k} stride={stride}")
+    split, parts, lane_samples = (o.value for o in out)
+    return {"kernel": DW_WGRAD_KERNELS[kind], "split": split, "parts": parts, "lane_samples": lane_samples}
+
+
 def dw_conv_stats(x, w, k, stride, tf=None, out_b16=False):
     """Train-mode depthwise conv + the partial sums of its output for the BatchNorm that follows.
     tf = (in_a, in_b, in_act): the conv input is act(in_a[c] x + in_b[c]) evaluated on load.

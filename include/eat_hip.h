@@ -263,6 +263,28 @@ int eat_dw_conv_dgrad_g(const float* dz, const float* w, const float* gz, const 
 /* Partial slots per plane of eat_dw_conv_bwd_g's merged kernel (host helper). */
 int eat_dw_bwd_partials_inner(int F, int T, int Fo, int To, int k, int stride);
 
+/* Host helpers for tests and measurement tools: how the depthwise training launchers cut a shape - the batch picks the work
+ * decomposition.  Both answer from the functions the launchers themselves call (no device work; any out pointer may be NULL).
+ *
+ * eat_dw_bwd_split: the merged backward kernel (eat_dw_conv_bwd_g: bn = 0; eat_dw_conv_bwd_bn_g, its _b16 and _dyn forms:
+ * bn = 1).  Returns 1 where the geometry is not on this kernel, else 0 and
+ *   lane_group  lanes that own a plane's row: 16 or 32 (4 or 2 samples side by side in a wave) or 64
+ *   whole_rows  1: a lane group holds whole rows; 0: column strips with halo lanes
+ *   tile_rows   rows per tile, 4 or 8
+ *   G           groups of 64 / lane_group samples a wave walks before its weight-gradient reduction (8, halved while
+ *               the launch would have fewer than 8192 waves)
+ *   inner       tiles per plane = what the launch writes to *h_inner (<= eat_dw_bwd_partials_inner)
+ *
+ * eat_dw_wgrad_split: eat_dw_conv_wgrad / eat_dw_conv_wgrad_tf (per_sample = 0) and eat_dw_conv_dyn_wgrad (1).  Returns the
+ * kernel - 0 whole-plane, 1 tile, 2 column-walking, 3 stem (XC = 1), 4 per-channel fallback; -1: the call would be refused -
+ *   split         whole-plane, tile: G as above; column-walking, per-channel: samples per block; stem: output rows per block
+ *   parts         sample groups per channel (whole-plane, tile), batch slices (column-walking, per-channel), row chunks (stem)
+ *   lane_samples  samples side by side in a wave (whole-plane: 1 or 2; else 1) */
+int eat_dw_bwd_split(int B, int C, int F, int T, int Fo, int To, int k, int stride, int bn, int* lane_group, int* whole_rows,
+                     int* tile_rows, int* G, int* inner);
+int eat_dw_wgrad_split(int B, int C, int XC, int F, int T, int Fo, int To, int k, int stride, int per_sample, int* split,
+                       int* parts, int* lane_samples);
+
 /* Backward of the depthwise conv (autograd of models/mn/block_types.py:150-162) in ONE pass over dz (B,C,Fo,To) and the
  * pre-BN expand output x (B,C,F,T): dw (C,k,k) += weight gradient w.r.t. act(in_a x + in_b) [dw zeroed by the caller],
  * g = dgrad(dz) * act'(in_a x + in_b) and its per-tile sums gpart [B][C][inner] - i.e. eat_dw_conv_wgrad_tf +

@@ -51,7 +51,7 @@ def test_ctypes_signatures_are_parsed_from_the_header(libpath):
     P, I, F, D, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
     with open(os.path.join(ROOT, "include", "eat_hip.h")) as f:
         protos = _lib.parse_prototypes(f.read())
-    assert len(protos) == 137 and protos == _lib.PROTOTYPES
+    assert len(protos) == 139 and protos == _lib.PROTOTYPES
     assert _lib.SIGNATURES == {name: args for name, (_, args) in protos.items()}
     for name, (restype, args) in protos.items():
         assert set(args) <= _VOCABULARY and restype in (I, LL, ctypes.c_char_p), name
