@@ -9,6 +9,7 @@
 // are summed by a transposing butterfly (63 shuffles for 64 sums instead of 384) that leaves sum v in lane v.
 // (R = 4 at G = 8, 16 was measured first: 8 rows halve the LDS reads per bank byte and double the loads in flight)
 //
+// The score of a wavefront's rows (loads, multiply-adds, butterfly) is `scan_rows` of search_scan.h, which match.hip calls too.
 // Position independence: element d of a row always goes to lane (d / 4) % 64, the lane adds its elements in ascending d
 // with one fmaf each, and the butterfly adds lanes in one fixed tree whatever the slot (row r, query g) of the sum - fp32
 // addition commutes, so which partner keeps a pair's sum does not matter.  The 4-byte path (D % 4 != 0 or an unaligned
@@ -25,84 +26,21 @@
 #include <cstdint>
 
 #include "eat_common.h"
+#include "search_scan.h"
 #include "search_topk.h"
 #include "../../include/eat_search.h"
 
 namespace {
 
+using namespace eat;             // search_scan.h: the score of a row; search_topk.h: better, list_offer, search_merge_kernel, row_sumsq
+
 constexpr int kBlocks = 256;            // stage-1 grid, whatever N; also the threads of a stage-2 block (one per list)
 constexpr int kThreads = 512;           // stage 1
 constexpr int kWaves = kThreads / eat::kWave;
-constexpr int kChunk = 256;             // floats of a row that a wavefront takes per step: 64 lanes x 16 bytes
 constexpr int kMaxGroup = 16;           // queries resident per pass over the bank
 constexpr int kMaxK = 128, kMaxQ = 1024;
-constexpr long long kLdsBytes = 160 * 1024;
 
 constexpr int rows_per_wave(int G) { return 8; }                       // R: rows a wavefront multiplies at once
-
-using namespace eat;             // search_topk.h: better, list_insert, list_offer, search_merge_kernel, row_sumsq
-
-// elements d .. d + 3 of a row (zeros from D on).  VEC: one 16-byte load (D % 4 == 0, 16-byte aligned rows).
-// TAIL = false: the caller knows d + 3 < D.
-template <bool VEC, bool TAIL>
-__device__ __forceinline__ float4 load4(const float* __restrict__ row, unsigned d, unsigned D) {
-  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if constexpr (VEC) {
-    if (!TAIL || d < D) v = *reinterpret_cast<const float4*>(row + d);
-  } else {
-    if (!TAIL || d < D) v.x = row[d];
-    if (!TAIL || d + 1 < D) v.y = row[d + 1];
-    if (!TAIL || d + 2 < D) v.z = row[d + 2];
-    if (!TAIL || d + 3 < D) v.w = row[d + 3];
-  }
-  return v;
-}
-
-// sum (r, g) lives at acc[(r * G + g) / VH][(r * G + g) % VH]: halves of at most 64 sums, one transposing butterfly each
-// sum (r, g) += b[r] . q_g[d .. d + 3], one fmaf per element in ascending d
-template <int G, int R, int H, int VH, bool QLDS, bool TAIL>
-__device__ __forceinline__ void fma_chunk(float (&acc)[H][VH], const float4 (&b)[R], const float* q_lds, unsigned Dp,
-                                          const float* __restrict__ q_glb, unsigned d, unsigned D) {
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    float4 qv;
-    if constexpr (QLDS) qv = *reinterpret_cast<const float4*>(q_lds + (size_t)g * Dp + d);
-    else qv = load4<false, TAIL>(q_glb + (size_t)g * D, d, D);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float a = acc[(r * G + g) / VH][(r * G + g) % VH];
-      a = __builtin_fmaf(b[r].x, qv.x, a);
-      a = __builtin_fmaf(b[r].y, qv.y, a);
-      a = __builtin_fmaf(b[r].z, qv.z, a);
-      a = __builtin_fmaf(b[r].w, qv.w, a);
-      acc[(r * G + g) / VH][(r * G + g) % VH] = a;
-    }
-  }
-}
-
-// Sums over the 64 lanes of V values per lane (V a power of two <= 64): log2 V transposing steps, in each of which a lane
-// keeps one half of its values and receives its partner's copies of that half, then plain butterfly steps.  Every lane ends
-// with the complete sum of value v = lane / (64 / V); the tree of additions is the same for every v.
-template <int V, int O = 32>
-__device__ __forceinline__ float transpose_sum(const float (&a)[V], int lane) {
-  static_assert(V >= 1 && (V == 1 || V <= 2 * O) && (V & (V - 1)) == 0, "V must be a power of two up to 64");
-  if constexpr (V > 1) {
-    constexpr int H = V / 2;
-    const bool upper = (lane & O) != 0;
-    float half[H];                            // a fresh array per step: every index is a constant, all of it stays in registers
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-      const float lo = a[i], hi = a[i + H];
-      half[i] = (upper ? hi : lo) + __shfl_xor(upper ? lo : hi, O, 64);
-    }
-    return transpose_sum<H, O / 2>(half, lane);
-  } else {
-    float v = a[0];
-#pragma unroll
-    for (int o = O; o >= 1; o /= 2) v += __shfl_xor(v, o, 64);
-    return v;
-  }
-}
 
 // LDS of one stage-1 block: G x Dp floats of queries (QLDS), G x k (score, index), 2 x G x tile-rows scores, G x (lo, hi)
 __host__ __device__ constexpr long long scan_lds_bytes(int G, long long Dp, int k) {
@@ -115,12 +53,11 @@ __global__ __launch_bounds__(kThreads) void search_scan_kernel(const float* __re
                                                                const float* __restrict__ queries, int Qg, int k,
                                                                const int* __restrict__ skip, float* __restrict__ ws_s,
                                                                int* __restrict__ ws_i) {
-  constexpr int R = rows_per_wave(G), V = R * G, TR = kWaves * R;     // TR = 64 rows per tile
-  constexpr int VH = V < 64 ? V : 64, H = V / VH;                     // the V sums of a lane, in H halves of VH
+  constexpr int R = rows_per_wave(G), TR = kWaves * R;                 // TR = 64 rows per tile
   static_assert(TR <= 64, "one lane per row of the tile in the selection");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const unsigned D = (unsigned)D_;
-  const unsigned Dp = QLDS ? (D + kChunk - 1) / kChunk * kChunk : 0u;
+  const unsigned Dp = QLDS ? (unsigned)padded_dim(D) : 0u;
   float* const q_lds = smem;
   float* const list_s = smem + (size_t)G * Dp;
   int* const list_i = reinterpret_cast<int*>(list_s + G * k);
@@ -129,10 +66,7 @@ __global__ __launch_bounds__(kThreads) void search_scan_kernel(const float* __re
   int* const s_hi = s_lo + G;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
-  if constexpr (QLDS) {
-    for (int g = 0; g < G; ++g)
-      for (unsigned d = tid; d < Dp; d += kThreads) q_lds[(size_t)g * Dp + d] = (g < Qg && d < D) ? queries[(size_t)g * D + d] : 0.0f;
-  }
+  if constexpr (QLDS) stage_queries<G, kThreads>(q_lds, Dp, queries, Qg, D, tid);
   for (int i = tid; i < G * k; i += kThreads) {
     list_s[i] = -INFINITY;
     list_i[i] = -1;
@@ -149,39 +83,12 @@ __global__ __launch_bounds__(kThreads) void search_scan_kernel(const float* __re
   }
   __syncthreads();
 
-  const unsigned n_full = D / kChunk;
-  const bool tail = (D % kChunk) != 0;
   const long long n_tiles = (N + TR - 1) / TR;
   int buf = 0;
   for (long long t = blockIdx.x; t < n_tiles; t += gridDim.x, buf ^= 1) {
-    const long long n0 = t * TR + wave * R;
-    const float* rows[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) rows[r] = bank + min(n0 + r, N - 1) * (long long)D;      // a row past N: scored and dropped
-    float acc[H][VH];
-#pragma unroll
-    for (int v = 0; v < V; ++v) acc[v / VH][v % VH] = 0.0f;
-    float4 b[R];
-    for (unsigned c = 0; c < n_full; ++c) {
-      const unsigned d = c * kChunk + 4u * lane;
-#pragma unroll
-      for (int r = 0; r < R; ++r) b[r] = load4<VEC, false>(rows[r], d, D);
-      fma_chunk<G, R, H, VH, QLDS, false>(acc, b, q_lds, Dp, queries, d, D);
-    }
-    if (tail) {
-      const unsigned d = n_full * kChunk + 4u * lane;
-#pragma unroll
-      for (int r = 0; r < R; ++r) b[r] = load4<VEC, true>(rows[r], d, D);
-      fma_chunk<G, R, H, VH, QLDS, true>(acc, b, q_lds, Dp, queries, d, D);
-    }
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-      const float total = transpose_sum<VH>(acc[h], lane);
-      if (lane % (64 / VH) == 0) {
-        const int v = h * VH + lane / (64 / VH), r = v / G, g = v % G;
-        sc[(buf * G + g) * TR + wave * R + r] = total;
-      }
-    }
+    float* const sc_t = sc + buf * G * TR;
+    scan_rows<G, R, VEC, QLDS>(bank, N, D, t * TR + wave * R, q_lds, Dp, queries, lane,
+                            [&](int r, int g, float s) { sc_t[g * TR + wave * R + r] = s; });       // a row past N: dropped below
     __syncthreads();
     // the next tile writes the other half of sc, and a wavefront reaches the tile after that only past the next barrier,
     // which every wavefront passes after its selection here: one barrier per tile
@@ -234,7 +141,7 @@ struct ScanArgs {
 template <int G, bool VEC, bool QLDS>
 int launch_scan(const ScanArgs& a) {
   auto kern = search_scan_kernel<G, VEC, QLDS>;
-  const long long Dp = QLDS ? ((long long)a.D + kChunk - 1) / kChunk * kChunk : 0;
+  const long long Dp = QLDS ? padded_dim(a.D) : 0;
   const long long lds = scan_lds_bytes(G, Dp, a.k);
   if (lds > 64 * 1024) {          // per device, and cheap: asked for on every call
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -289,7 +196,7 @@ extern "C" int eat_embed_search(const float* bank, long long N, int D, const flo
                      Q, k, need);
 
   // the largest group whose queries and lists fit the LDS of a CU; not even one query: it is read from global memory
-  const long long Dp = ((long long)D + kChunk - 1) / kChunk * kChunk;
+  const long long Dp = padded_dim(D);
   int g_max = kMaxGroup;
   while (g_max > 1 && scan_lds_bytes(g_max, Dp, k) > kLdsBytes) g_max /= 2;
   const bool qlds = scan_lds_bytes(g_max, Dp, k) <= kLdsBytes;

@@ -2255,6 +2255,50 @@ def embed_search(bank, queries, k, skip=None):
     return score, index
 
 
+# ------------------------------------------------------------------ occurrence search (include/eat_match.h)
+MATCH_MAX_L, MATCH_MAX_SEP = 1024, 4096
+_MATCH_WS = {}               # (device, N, min(L, 16), k) -> workspace of eat_embed_match_ws_bytes(N, L, k) bytes
+
+
+def embed_match(bank, seg, queries, k, sep, min_score=float("-inf"), skip=None):
+    """Where in the files of `bank` (N, D) does the sequence `queries` (L, D) occur - both L2-normalised already
+    (`rows_normalize`), the queries in time order at the bank's hop -> (score (k,) fp32, index (k,) int32).
+    seg (F + 1,) int32 on the bank's device: file f is rows [seg[f], seg[f + 1]), strictly ascending from 0 to N (the
+    caller's promise: the table is not read back).  The match score of a start row whose window fits its file is the mean
+    over j of the `embed_search` score of query row j and bank row n + j; a start row is returned when no other start row
+    of its file within `sep` rows is better (larger score, equal scores by lower row) and its score is at least
+    `min_score`: local-maximum peak picking, not greedy suppression.  Descending score, equal scores by ascending row,
+    (-inf, -1) in the slots that no peak fills.  skip: None or (lo, hi) - start rows [lo, hi) are neither returned nor
+    suppress others.  1 <= L <= 1024, 1 <= k <= 128, 0 <= sep <= 4096."""
+    if bank.dim() != 2 or queries.dim() != 2 or bank.shape[1] != queries.shape[1] or bank.shape[1] < 1:
+        raise _lib.EatHipError(f"embed_match: bank (N, D) and queries (L, D) must share D >= 1 (got {tuple(bank.shape)}, "
+                               f"{tuple(queries.shape)})")
+    pb, pq = _dev(bank, "x"), _dev(queries, "queries")
+    if queries.device != bank.device or seg.device != bank.device:
+        raise _lib.EatHipError(f"embed_match: bank lives on {bank.device}, queries on {queries.device}, seg on {seg.device}")
+    if seg.dim() != 1 or seg.dtype != torch.int32 or seg.shape[0] < 2 or not seg.is_contiguous():
+        raise _lib.EatHipError(f"embed_match: seg must be a contiguous int32 vector of F + 1 >= 2 bounds (got {tuple(seg.shape)} "
+                               f"{seg.dtype})")
+    (N, D), L, k, sep, dev = bank.shape, queries.shape[0], int(k), int(sep), bank.device
+    min_score = float(min_score)
+    if not 1 <= k <= SEARCH_MAX_K or not 1 <= L <= MATCH_MAX_L or not 0 <= sep <= MATCH_MAX_SEP or N < 1:
+        raise _lib.EatHipError(f"embed_match: need 1 <= k <= {SEARCH_MAX_K}, 1 <= L <= {MATCH_MAX_L}, 0 <= sep <= {MATCH_MAX_SEP} "
+                               f"and N >= 1 (got k={k}, L={L}, sep={sep}, N={N})")
+    if min_score != min_score:
+        raise _lib.EatHipError("embed_match: min_score is NaN (-inf disables it)")
+    lo, hi = (0, 0) if skip is None else (int(v) for v in check_skip([list(skip)], 1)[0])
+    key = (dev, N, min(L, SEARCH_GROUP), k)
+    ws = _MATCH_WS.get(key)
+    if ws is None:
+        _MATCH_WS.clear()                 # one bank at a time: a workspace holds (1 + min(L, 16)) x N floats
+        ws = _MATCH_WS[key] = torch.empty(_lib.lib().eat_embed_match_ws_bytes(N, L, k), device=dev, dtype=torch.uint8)
+    score = torch.empty((k,), device=dev, dtype=torch.float32)
+    index = torch.empty((k,), device=dev, dtype=torch.int32)
+    _lib.call("eat_embed_match", pb, N, D, seg.data_ptr(), seg.shape[0] - 1, pq, L, k, sep, min_score, lo, hi, ws.data_ptr(),
+              ws.numel(), score.data_ptr(), index.data_ptr(), _stream())
+    return score, index
+
+
 # ------------------------------------------------------------------ the 8-bit search index (include/eat_search_q8.h)
 SEARCH_Q8_MAX_D = 131072
 # geometry of csrc/search_q8.hip (kBlocks, kMaxGroup, kTileRows = 16 rows per wavefront x 8 wavefronts)

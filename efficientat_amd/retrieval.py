@@ -78,6 +78,8 @@ class EmbeddingIndex:
         else:
             self._bank = torch.empty((0, self.D), dtype=torch.float32, device=self.device or "cpu")
         self._n = 0
+        self._seg = None                                         # `find`: (F + 1,) int32 file bounds on the device; None: rebuild
+        self._uniform = None                                     # `find`: every file's times step by hop_ms; None: not checked yet
 
     # -- bookkeeping -----------------------------------------------------------------------------------------------------
     def __len__(self):
@@ -157,6 +159,7 @@ class EmbeddingIndex:
         self.names.append(name)
         self._ranges[name] = (lo, hi)
         self._n = hi
+        self._seg = self._uniform = None
         return lo, hi
 
     def _add_fp32(self, emb, lo, hi):
@@ -241,10 +244,86 @@ class EmbeddingIndex:
                 return ops.embed_search_q8(self.codes, self.scales, self.D, qcodes, qscale, k, skip)
             return ops.embed_search(self.bank, ops.rows_normalize(queries), k, skip)
 
-    def hits(self, score, index):
+    # -- occurrences -----------------------------------------------------------------------------------------------------
+    def _check_times(self):
+        """ValueError unless every file's time_ms is an arithmetic progression of step meta["hop_ms"] (checked once, on the
+        host, until the next `add`): a sequence of query rows at that hop then lines up with consecutive rows of a file."""
+        if self._uniform is None:
+            hop = self.meta["hop_ms"]
+            if hop is None or not float(hop) > 0:
+                raise ValueError(f"EmbeddingIndex.find: the index records no hop_ms (meta hop_ms = {hop!r}): pass it in meta")
+            steps = np.diff(self._time)
+            inside = np.diff(self._file) == 0
+            self._uniform = bool((np.abs(steps[inside] - float(hop)) <= 1e-6 * float(hop)).all())
+        if not self._uniform:
+            raise ValueError(f"EmbeddingIndex.find: the times of a file do not step by hop_ms = {self.meta['hop_ms']}: rows of "
+                             f"a sequence match must be evenly spaced")
+
+    def find(self, query_rows, k, min_separation_rows=None, min_score=None, exclude=None, extractor=None):
+        """Where in the files of a timestamp index does the clip occur whose timestamp embeddings are query_rows (L, D), in
+        time order at the index's hop_ms -> (score (k,) fp32, row (k,) int32) on the device: distinct occurrences, best
+        first, (-inf, -1) where there are fewer than k.  The score of a start row is the mean cosine of the L query rows with
+        the L rows from it on, all within one file; a start row is an occurrence when no other start row of its file within
+        min_separation_rows (default max(L, ceil(width_ms / hop_ms)): occurrences do not overlap) scores higher - local-maximum
+        peak picking (`ops.embed_match`, include/eat_match.h).  min_score: occurrences below it are left out.  exclude:
+        None or the name of a file whose rows are no start rows.  An fp32 index of kind "timestamps" on a GPU only."""
+        if self.storage != "fp32":
+            raise ValueError(f"EmbeddingIndex.find: a sequence match needs the fp32 index (this one has storage '{self.storage}')")
+        if self.meta["kind"] != "timestamps":
+            raise ValueError(f"EmbeddingIndex.find: occurrences are found in an index of kind 'timestamps' (this one is "
+                             f"'{self.meta['kind']}'; see `search`)")
+        if self.device is None:
+            raise _lib.EatHipError("EmbeddingIndex.find needs the index on a GPU: efficientat_amd has no CPU path "
+                                   "(load it with device='cuda')")
+        if extractor is not None:
+            self.check_extractor(extractor)
+        if self._n < 1:
+            raise ValueError("EmbeddingIndex: the index is empty")
+        query_rows = torch.as_tensor(query_rows)
+        if query_rows.dim() == 1:
+            query_rows = query_rows.unsqueeze(0)
+        if query_rows.dim() != 2 or query_rows.shape[1] != self.D or query_rows.shape[0] < 1:
+            raise ValueError(f"EmbeddingIndex.find: query_rows must be (L >= 1, {self.D}) (got {tuple(query_rows.shape)})")
+        self._check_times()
+        L = query_rows.shape[0]
+        if min_separation_rows is None:
+            min_separation_rows = max(L, int(np.ceil(float(self.meta["width_ms"] or 0.0) / float(self.meta["hop_ms"]))))
+        if int(min_separation_rows) != min_separation_rows or min_separation_rows < 0:
+            raise ValueError(f"EmbeddingIndex.find: min_separation_rows must be an integer >= 0 (got {min_separation_rows!r})")
+        skip = None if exclude is None else self.row_range(exclude)
+        with torch.cuda.device(self.device):
+            if self._seg is None:
+                bounds = [0] + [self._ranges[name][1] for name in self.names]
+                self._seg = torch.tensor(bounds, dtype=torch.int32).to(self.device)
+            query_rows = query_rows.to(device=self.device, dtype=torch.float32).contiguous()
+            return ops.embed_match(self.bank, self._seg, ops.rows_normalize(query_rows), k, int(min_separation_rows),
+                                   float("-inf") if min_score is None else min_score, skip)
+
+    def find_recordings(self, extractor, waves, k, min_separation_rows=None, min_score=None, exclude=None):
+        """`find` for each query clip of `waves` (what `EmbeddingExtractor.timestamp_embeddings` takes), embedded at the
+        index's hop_ms and width_ms -> per clip (score (k,), row (k,), L): L, the clip's rows, is what `hits` needs.
+        exclude: None, or per clip None or a file name."""
+        self.check_extractor(extractor)
+        if self.meta["hop_ms"] is None or self.meta["width_ms"] is None:
+            raise ValueError("EmbeddingIndex.find_recordings: the index records no hop_ms / width_ms to embed the queries at")
+        clips = extractor.timestamp_embeddings(waves, hop_ms=self.meta["hop_ms"], width_ms=self.meta["width_ms"])
+        exclude = [None] * len(clips) if exclude is None else list(exclude)
+        if len(exclude) != len(clips):
+            raise ValueError(f"EmbeddingIndex.find_recordings: exclude must hold one name or None per clip ({len(clips)}), "
+                             f"got {len(exclude)}")
+        return [self.find(emb, k, min_separation_rows, min_score, name) + (emb.shape[0],) for (emb, _), name in zip(clips, exclude)]
+
+    def hits(self, score, index, query_rows=None):
         """(score, index) of `search` -> per query a host list of {"name", "time_ms" (None for a scene row), "row", "score"},
-        best first, without the -1 slots."""
+        best first, without the -1 slots.  query_rows = L: (score, index) are the (k,) outputs of `find` for a clip of L rows;
+        the result is that clip's one list, and each place gains "end_ms" = time_ms + L hop_ms."""
         score, index = torch.as_tensor(score).cpu().numpy(), torch.as_tensor(index).cpu().numpy()
+        if query_rows is not None:
+            if score.ndim != 1:
+                raise ValueError(f"EmbeddingIndex.hits: with query_rows, score and index are the (k,) outputs of `find` (got {score.shape})")
+            span = int(query_rows) * float(self.meta["hop_ms"])
+            (found,) = self.hits(score[None], index[None])
+            return [dict(h, end_ms=h["time_ms"] + span) for h in found]
         if score.shape != index.shape or score.ndim != 2:
             raise ValueError(f"EmbeddingIndex.hits: score and index must share one (Q, k) shape (got {score.shape}, {index.shape})")
         if bool(((index < -1) | (index >= self._n)).any()):

@@ -4,8 +4,10 @@
                                            [--storage {fp32,q8}]
     python -m efficientat_amd.search query --index idx/ --audio_path q.wav ... [--k 10] [--exclude_self] [--json]
     python -m efficientat_amd.search convert --index idx/ --out idx_q8/ --storage q8
+    python -m efficientat_amd.search find --index idx/ --audio_path q.wav ... [--k 10] [--min_separation_ms X] [--min_score S]
+                                          [--exclude_self] [--query {sequence,scene}] [--json]
 
-Both take the model arguments of `python -m efficientat_amd.embed` (--model_name | --checkpoint [--width], --clip_seconds,
+`index`, `query` and `find` take the model arguments of `python -m efficientat_amd.embed` (--model_name | --checkpoint [--width], --clip_seconds,
 --batch_windows) plus --layers (feature-map indices, default all); `query` refuses an index built with other layers,
 another clip length or another embedding size.
 
@@ -21,6 +23,13 @@ table.
 --storage q8 keeps each row as int8 codes and one scale, a quarter of the bytes on disk and in GPU memory, and searches
 them with integer matrix instructions; scores are those of the quantised vectors.  `query` reads the storage from the
 index.  `convert` writes the q8 index of an existing fp32 index's rows without touching the audio again.
+
+`find` answers "where in these recordings does something like this clip occur" against an fp32 timestamp index of ANY
+width_ms: the query's timestamp embeddings, in order and at the index's hop, are laid over every position of every file;
+the score of a place is the mean cosine of the sequence, and the places returned are local maxima at least
+--min_separation_ms apart within a file (default: the query's length), so k hits are k distinct occurrences, not one
+place k times.  --query scene matches the one scene embedding instead, with the same peak picking.  --json prints one line
+per query: {"audio_path", "query", "rows", "hits": [{"name", "time_ms", "end_ms", "score"}, ...]}.
 """
 import argparse
 import contextlib
@@ -55,6 +64,17 @@ def parser():
     pq.add_argument("--k", type=int, default=10, help="hits per query (1 to 128)")
     pq.add_argument("--exclude_self", action="store_true", help="leave out the index file with the query's own path")
     pq.add_argument("--json", action="store_true", help="one JSON line per query")
+    pf = sub.add_parser("find", help="find where in a timestamp index something like the given WAV files occurs")
+    _model_arguments(pf)
+    pf.add_argument("--index", type=str, required=True, help="directory that `index --timestamps` wrote (fp32)")
+    pf.add_argument("--k", type=int, default=10, help="occurrences per query (1 to 128)")
+    pf.add_argument("--min_separation_ms", type=float, default=None,
+                    help="two occurrences in one file start at least this far apart (default: the query's length)")
+    pf.add_argument("--min_score", type=float, default=None, help="leave out occurrences of a lower mean cosine")
+    pf.add_argument("--exclude_self", action="store_true", help="leave out the index file with the query's own path")
+    pf.add_argument("--query", choices=("sequence", "scene"), default="sequence",
+                    help="sequence: the query's timestamp embeddings in order; scene: its one scene embedding")
+    pf.add_argument("--json", action="store_true", help="one JSON line per query")
     pc = sub.add_parser("convert", help="write the q8 index of an fp32 index's rows")
     pc.add_argument("--index", type=str, required=True, help="directory that `index` wrote (fp32)")
     pc.add_argument("--out", type=str, required=True, help="directory to write")
@@ -69,8 +89,12 @@ def parse(argv=None):
         return args
     if len(set(args.audio_path)) != len(args.audio_path) and args.command == "index":
         p.error("--audio_path names a file twice: a name is in an index once")
-    if args.command == "query" and not 1 <= args.k <= 128:
+    if args.command in ("query", "find") and not 1 <= args.k <= 128:
         p.error(f"--k must lie in [1, 128] (got {args.k})")
+    if args.command == "find" and args.min_separation_ms is not None and not args.min_separation_ms >= 0:
+        p.error(f"--min_separation_ms must be >= 0 (got {args.min_separation_ms})")
+    if args.command == "find" and args.min_score is not None and args.min_score != args.min_score:
+        p.error("--min_score must be a number")
     if args.command == "index" and (args.hop_ms <= 0 or args.width_ms <= 0):
         p.error(f"--hop_ms and --width_ms must be positive (got {args.hop_ms}, {args.width_ms})")
     if args.clip_seconds <= 0:
@@ -93,6 +117,32 @@ def _extractor(args):
         model.load_state_dict(sd)
         return EmbeddingExtractor(model=model.eval(), **kwargs)
     return EmbeddingExtractor(model_name=args.model_name, **kwargs)
+
+
+def _find(args, extractor, index, waves, exclude):
+    """The `find` command past loading: one `EmbeddingIndex.find` per query file, printed."""
+    if index.meta["kind"] != "timestamps" or index.storage != "fp32":
+        print(f"{args.index}: find needs an fp32 index built with --timestamps (this one: {index.meta['kind']}, {index.storage})",
+              file=sys.stderr)
+        return 2
+    sep = None
+    if args.min_separation_ms is not None:
+        sep = int(-(-args.min_separation_ms // index.meta["hop_ms"]))                # rows, rounded up
+    if args.query == "scene":
+        queries = [row.unsqueeze(0) for row in extractor.scene_embeddings(waves)]
+    else:
+        queries = [emb for emb, _ in extractor.timestamp_embeddings(waves, hop_ms=index.meta["hop_ms"], width_ms=index.meta["width_ms"])]
+    for path, rows, name in zip(args.audio_path, queries, exclude):
+        score, start = index.find(rows, args.k, min_separation_rows=sep, min_score=args.min_score, exclude=name)
+        found = index.hits(score, start, query_rows=rows.shape[0])
+        if args.json:
+            print(json.dumps({"audio_path": path, "query": args.query, "rows": int(rows.shape[0]),
+                              "hits": [{"name": h["name"], "time_ms": h["time_ms"], "end_ms": h["end_ms"], "score": h["score"]} for h in found]}))
+        else:
+            print(path)
+            for rank, h in enumerate(found):
+                print(f"  {rank + 1:3d}  {h['score']:8.5f}  {h['time_ms'] / 1000.0:9.3f} s - {h['end_ms'] / 1000.0:9.3f} s  {h['name']}")
+    return 0
 
 
 def main(argv=None):
@@ -122,6 +172,8 @@ def main(argv=None):
     exclude = None
     if args.exclude_self:
         exclude = [path if path in index.names else None for path in args.audio_path]
+    if args.command == "find":
+        return _find(args, extractor, index, waves, exclude or [None] * len(waves))
     score, rows = index.search(extractor.scene_embeddings(waves), args.k, exclude=exclude)
     for path, found in zip(args.audio_path, index.hits(score, rows)):
         if args.json:
