@@ -1,6 +1,6 @@
 """ctypes binding of libeat_hip.so (the C ABI declared in include/eat_hip.h, include/eat_tag.h, include/eat_embed.h,
 include/eat_attn.h, include/eat_detect.h, include/eat_sed.h, include/eat_event_score.h, include/eat_psds.h,
-include/eat_weak_sed.h, include/eat_median_bank.h, include/eat_search.h, include/eat_search_q8.h and include/eat_match.h).
+include/eat_weak_sed.h, include/eat_median_bank.h, include/eat_search.h, include/eat_search_q8.h, include/eat_match.h and include/eat_match_q8.h).
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, an
 exception is raised.  Build it with ``python -m efficientat_amd.build`` (or
@@ -43,6 +43,8 @@ SEARCH_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_search.h")
 SEARCH_Q8_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_search_q8.h")
 # occurrence search's entry points (efficientat_amd/retrieval.py: EmbeddingIndex.find): likewise
 MATCH_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_match.h")
+# occurrence search over the 8-bit index (efficientat_amd/retrieval.py: EmbeddingIndex.find(allow_q8=True)): likewise
+MATCH_Q8_HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "eat_match_q8.h")
 
 
 class EatHipError(RuntimeError):
@@ -111,6 +113,8 @@ with open(SEARCH_Q8_HEADER_PATH) as _f:
     SEARCH_Q8_PROTOTYPES = parse_prototypes(_f.read())                 # likewise
 with open(MATCH_HEADER_PATH) as _f:
     MATCH_PROTOTYPES = parse_prototypes(_f.read())                     # likewise
+with open(MATCH_Q8_HEADER_PATH) as _f:
+    MATCH_Q8_PROTOTYPES = parse_prototypes(_f.read())                  # likewise
 
 _lib = None
 
@@ -129,7 +133,8 @@ def lib():
                                           + list(SED_PROTOTYPES.items()) + list(EVENT_SCORE_PROTOTYPES.items())
                                           + list(PSDS_PROTOTYPES.items()) + list(WEAK_SED_PROTOTYPES.items())
                                           + list(MEDIAN_BANK_PROTOTYPES.items()) + list(SEARCH_PROTOTYPES.items())
-                                          + list(SEARCH_Q8_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items())):
+                                          + list(SEARCH_Q8_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items())
+                                          + list(MATCH_Q8_PROTOTYPES.items())):
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -7,7 +7,7 @@
 // 64, lane l loads 16 bytes of row l & 15 at byte 64 step + 16 (l >> 4) - the B operand of v_mfma_i32_16x16x64_i8 - and
 // per 16 queries reads 16 bytes of query l & 15 at the same k from LDS - the A operand.  Both operands take their bytes
 // from the same k, so the order of k inside the instruction does not matter; D[i][j] = sum_k A[i][k] B[k][j] has the
-// query on its row, 4 (lane >> 4) + reg, and the bank row on its column, lane & 15.  The loads of kAhead = 8 k-steps are
+// query on its row, 4 (lane >> 4) + reg, and the bank row on its column, lane & 15.  The loads of kQ8Ahead = 8 k-steps are
 // issued before the first MFMA of the batch (8 KB in flight per wavefront, 64 KB per CU); the tail of a row is one more
 // batch with lanes and steps past D predicated off.  The arithmetic is far from the limit: 4 MFMAs and 4 KB of LDS
 // reads per KB of bank at G = 64, against the ~10 bytes per clock that a CU's share of HBM delivers.
@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "eat_common.h"
+#include "search_q8_scan.h"
 #include "search_topk.h"
 #include "../../include/eat_search_q8.h"
 
@@ -36,19 +37,9 @@ constexpr int kBlocks = 256;            // stage-1 grid, whatever N; also the th
 constexpr int kThreads = 512;           // stage 1
 constexpr int kWaves = kThreads / eat::kWave;
 constexpr int kTileRows = 16 * kWaves;  // bank rows of a block per step: one 16-row MFMA tile per wavefront
-constexpr int kAhead = 8;               // k-steps whose bank loads are issued before the first MFMA
 constexpr int kMaxGroup = 64;           // queries resident per pass over the bank
 constexpr int kMaxK = 128, kMaxQ = 1024, kMaxD = 131072;
 constexpr long long kLdsBytes = 160 * 1024;
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// bytes between two queries in LDS: D rounded up to 16, and an odd number of 16-byte pieces, so that the 16 queries of
-// an A operand start in different banks
-__host__ __device__ constexpr long long q_pitch(long long D) {
-  const long long p = (D + 15) / 16;
-  return 16 * (p % 2 ? p : p + 1);
-}
 
 // LDS of one stage-1 block: G queries, G x k (score, index), 2 x 16 x kTileRows staged scores, (lo, hi, scale) per query slot
 __host__ __device__ constexpr long long scan_lds_bytes(int G, long long D, int k) {
@@ -78,16 +69,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
   float* const s_sq = reinterpret_cast<float*>(s_hi + GP);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
-  const unsigned wpr = pitch / 4;                                    // 32-bit words per query
-  for (unsigned i = tid; i < (unsigned)G * wpr; i += kThreads) {
-    const unsigned g = i / wpr, d = 4u * (i - g * wpr);
-    unsigned v = 0;
-    if ((int)g < Qg && d < D) {                                      // d + 3 < qld: qld >= D is a multiple of 16
-      v = *reinterpret_cast<const unsigned*>(qcodes + (long long)g * qld + d);
-      if (d + 4u > D) v &= (1u << (8u * (D - d))) - 1u;              // the bytes from D on: zero, whatever the caller left there
-    }
-    reinterpret_cast<unsigned*>(q_lds)[i] = v;
-  }
+  q8_stage_queries<G, kThreads>(q_lds, pitch, qcodes, qld, Qg, D, tid);
   for (int i = tid; i < G * k; i += kThreads) {
     list_s[i] = -INFINITY;
     list_i[i] = -1;
@@ -106,7 +88,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
   __syncthreads();
 
   const int col = lane & 15, quad = lane >> 4;
-  const unsigned n_steps = (Dr + 63u) / 64u, n_full = Dr / 64u;
   const long long n_tiles = (N + kTileRows - 1) / kTileRows;
   const unsigned char* a_row[QT];
 #pragma unroll
@@ -116,52 +97,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     const long long n = min(t * kTileRows + wave * 16 + col, N - 1);   // a row past N: scored and dropped
     const int8_t* const b_row = codes + n * ld + 16 * quad;
     v4i acc[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) acc[qt] = v4i{0, 0, 0, 0};
-    unsigned step = 0;
-    for (; step + kAhead <= n_full; step += kAhead) {
-      v4i b[kAhead];
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u) b[u] = *reinterpret_cast<const v4i*>(b_row + 64u * (step + u));
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u)
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-          const v4i a = *reinterpret_cast<const v4i*>(a_row[qt] + 64u * (step + u));
-          acc[qt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[u], acc[qt], 0, 0, 0);
-        }
-      // the order of issue, which the compiler otherwise picks for the fewest registers (two bank loads in flight, every
-      // MFMA waiting for its own LDS read): all bank loads of the batch, then the A operands of step u + 1 ahead of the
-      // MFMAs of step u
-      __builtin_amdgcn_sched_group_barrier(0x020, kAhead, 0);          // VMEM reads
-      __builtin_amdgcn_sched_group_barrier(0x100, QT, 0);              // DS reads
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u) {
-        if (u + 1 < kAhead) __builtin_amdgcn_sched_group_barrier(0x100, QT, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, QT, 0);            // MFMAs
-      }
-    }
-    if (step < n_steps) {                                            // the rest of the row: fewer steps, the last one ragged
-      v4i b[kAhead];
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u) {
-        const unsigned off = 64u * (step + u) + 16u * quad;          // off < Dr <= ld: inside the row
-        b[u] = v4i{0, 0, 0, 0};
-        if (off < Dr) b[u] = *reinterpret_cast<const v4i*>(b_row + 64u * (step + u));
-      }
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u) {
-        if (step + u < n_steps) {                                    // wave-uniform
-          const unsigned off = 64u * (step + u) + 16u * quad;
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt) {
-            v4i a = v4i{0, 0, 0, 0};
-            if (off < Dr) a = *reinterpret_cast<const v4i*>(a_row[qt] + 64u * (step + u));
-            acc[qt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[u], acc[qt], 0, 0, 0);
-          }
-        }
-      }
-    }
+    q8_dot_rows<QT>(acc, a_row, b_row, Dr, quad);
 
     const float sn = scale_n[n];
 #pragma unroll
@@ -277,14 +213,6 @@ int launch_scan_g(const ScanArgs& a, int G) {
     case 2: return launch_scan<2>(a);
     default: return launch_scan<1>(a);
   }
-}
-
-// the checks that the quantiser and the search share on one q8 matrix
-int check_q8(const char* who, const char* name, const void* p, long long ld, int D) {
-  if (ld < D) return eat::fail(EAT_EINVAL, "%s: %s=%lld is below D=%d", who, name, ld, D);
-  if (ld % 16 != 0) return eat::fail(EAT_EINVAL, "%s: %s=%lld is no multiple of 16", who, name, ld);
-  if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return eat::fail(EAT_EINVAL, "%s: the codes behind %s are not 16-byte aligned", who, name);
-  return EAT_OK;
 }
 
 }  // namespace

@@ -2380,6 +2380,51 @@ def embed_search_q8(codes, scale, D, qcodes, qscale, k, skip=None):
     return score, index
 
 
+# ------------------------------------------------------------------ occurrence search over the 8-bit index (include/eat_match_q8.h)
+MATCH_Q8_GROUP = 64          # kMaxGroup of csrc/match_q8.hip: query rows resident per pass over the bank
+_MATCH_Q8_WS = {}            # (device, N, min(L, 64), k) -> workspace of eat_embed_match_q8_ws_bytes(N, L, k) bytes
+
+
+def embed_match_q8(codes, scale, D, seg, qcodes, qscale, k, sep, min_score=float("-inf"), skip=None):
+    """`embed_match` over a q8 bank: codes (N, ld) int8 and scale (N,), the clip's rows qcodes (L, qld) and qscale (L,) in
+    time order, both of D values (`rows_quantize_q8`) -> (score (k,) fp32, index (k,) int32).  The score of a start row is
+    the mean over j of the `embed_search_q8` score of query row j and bank row n + j - a mean of q8 scores, on the scale
+    of `embed_search_q8` - and everything else (seg, the window inside one file, local-maximum peak picking within `sep`
+    rows, `min_score`, skip = None or (lo, hi), the order, the (-inf, -1) padding) is `embed_match`.  The bank is read once
+    per group of up to 64 query rows.  1 <= L <= 1024, 1 <= k <= 128, 0 <= sep <= 4096."""
+    D, k, sep = int(D), int(k), int(sep)
+    if not 1 <= D <= SEARCH_Q8_MAX_D:
+        raise _lib.EatHipError(f"embed_match_q8: need 1 <= D <= {SEARCH_Q8_MAX_D} (got {D})")
+    pb, ld = _dev_q8("embed_match_q8", codes, scale, D, "bank")
+    pq, qld = _dev_q8("embed_match_q8", qcodes, qscale, D, "query")
+    if qcodes.device != codes.device or seg.device != codes.device:
+        raise _lib.EatHipError(f"embed_match_q8: bank lives on {codes.device}, queries on {qcodes.device}, seg on {seg.device}")
+    if codes.device.index != torch.cuda.current_device():
+        raise _lib.EatHipError(f"embed_match_q8: the bank lives on {codes.device} but the current device is "
+                               f"cuda:{torch.cuda.current_device()}")
+    if seg.dim() != 1 or seg.dtype != torch.int32 or seg.shape[0] < 2 or not seg.is_contiguous():
+        raise _lib.EatHipError(f"embed_match_q8: seg must be a contiguous int32 vector of F + 1 >= 2 bounds (got {tuple(seg.shape)} "
+                               f"{seg.dtype})")
+    N, L, dev = codes.shape[0], qcodes.shape[0], codes.device
+    min_score = float(min_score)
+    if not 1 <= k <= SEARCH_MAX_K or not 1 <= L <= MATCH_MAX_L or not 0 <= sep <= MATCH_MAX_SEP or N < 1:
+        raise _lib.EatHipError(f"embed_match_q8: need 1 <= k <= {SEARCH_MAX_K}, 1 <= L <= {MATCH_MAX_L}, 0 <= sep <= {MATCH_MAX_SEP} "
+                               f"and N >= 1 (got k={k}, L={L}, sep={sep}, N={N})")
+    if min_score != min_score:
+        raise _lib.EatHipError("embed_match_q8: min_score is NaN (-inf disables it)")
+    lo, hi = (0, 0) if skip is None else (int(v) for v in check_skip([list(skip)], 1)[0])
+    key = (dev, N, min(L, MATCH_Q8_GROUP), k)
+    ws = _MATCH_Q8_WS.get(key)
+    if ws is None:
+        _MATCH_Q8_WS.clear()              # one bank at a time: a workspace holds (1 + min(L, 64)) x N floats
+        ws = _MATCH_Q8_WS[key] = torch.empty(_lib.lib().eat_embed_match_q8_ws_bytes(N, L, k), device=dev, dtype=torch.uint8)
+    score = torch.empty((k,), device=dev, dtype=torch.float32)
+    index = torch.empty((k,), device=dev, dtype=torch.int32)
+    _lib.call("eat_embed_match_q8", pb, ld, scale.data_ptr(), N, D, seg.data_ptr(), seg.shape[0] - 1, pq, qld, qscale.data_ptr(), L, k,
+              sep, min_score, lo, hi, ws.data_ptr(), ws.numel(), score.data_ptr(), index.data_ptr(), _stream())
+    return score, index
+
+
 # ------------------------------------------------------------------ attention-pooling head (models/mn/attention_pooling.py:9-56)
 def pitch4(T):
     """Row pitch of the head's (B, rows, T) tensors: T rounded up to a multiple of 4 (16-byte row pieces of the 1x1 kernels)."""

@@ -259,16 +259,21 @@ class EmbeddingIndex:
             raise ValueError(f"EmbeddingIndex.find: the times of a file do not step by hop_ms = {self.meta['hop_ms']}: rows of "
                              f"a sequence match must be evenly spaced")
 
-    def find(self, query_rows, k, min_separation_rows=None, min_score=None, exclude=None, extractor=None):
+    def find(self, query_rows, k, min_separation_rows=None, min_score=None, exclude=None, extractor=None, allow_q8=False):
         """Where in the files of a timestamp index does the clip occur whose timestamp embeddings are query_rows (L, D), in
         time order at the index's hop_ms -> (score (k,) fp32, row (k,) int32) on the device: distinct occurrences, best
         first, (-inf, -1) where there are fewer than k.  The score of a start row is the mean cosine of the L query rows with
         the L rows from it on, all within one file; a start row is an occurrence when no other start row of its file within
         min_separation_rows (default max(L, ceil(width_ms / hop_ms)): occurrences do not overlap) scores higher - local-maximum
         peak picking (`ops.embed_match`, include/eat_match.h).  min_score: occurrences below it are left out.  exclude:
-        None or the name of a file whose rows are no start rows.  An fp32 index of kind "timestamps" on a GPU only."""
-        if self.storage != "fp32":
-            raise ValueError(f"EmbeddingIndex.find: a sequence match needs the fp32 index (this one has storage '{self.storage}')")
+        None or the name of a file whose rows are no start rows.  An index of kind "timestamps" on a GPU only, and an fp32
+        one unless allow_q8: then a q8 index quantises the query rows as it quantised its own (`ops.rows_quantize_q8`) and
+        matches the codes (`ops.embed_match_q8`, include/eat_match_q8.h).  The scores are then those of the codes: a mean of
+        q8 scores, on the scale of the `search` scores of the same index, not the fp32 cosines.  On an fp32 index allow_q8
+        changes nothing."""
+        if self.storage != "fp32" and not allow_q8:
+            raise ValueError(f"EmbeddingIndex.find: a sequence match needs the fp32 index (this one has storage '{self.storage}'; "
+                             f"allow_q8=True matches the codes instead)")
         if self.meta["kind"] != "timestamps":
             raise ValueError(f"EmbeddingIndex.find: occurrences are found in an index of kind 'timestamps' (this one is "
                              f"'{self.meta['kind']}'; see `search`)")
@@ -296,13 +301,17 @@ class EmbeddingIndex:
                 bounds = [0] + [self._ranges[name][1] for name in self.names]
                 self._seg = torch.tensor(bounds, dtype=torch.int32).to(self.device)
             query_rows = query_rows.to(device=self.device, dtype=torch.float32).contiguous()
-            return ops.embed_match(self.bank, self._seg, ops.rows_normalize(query_rows), k, int(min_separation_rows),
-                                   float("-inf") if min_score is None else min_score, skip)
+            min_score = float("-inf") if min_score is None else min_score
+            if self.storage == "q8":
+                qcodes, qscale = ops.rows_quantize_q8(query_rows, normalize=True)
+                return ops.embed_match_q8(self.codes, self.scales, self.D, self._seg, qcodes, qscale, k, int(min_separation_rows),
+                                          min_score, skip)
+            return ops.embed_match(self.bank, self._seg, ops.rows_normalize(query_rows), k, int(min_separation_rows), min_score, skip)
 
-    def find_recordings(self, extractor, waves, k, min_separation_rows=None, min_score=None, exclude=None):
+    def find_recordings(self, extractor, waves, k, min_separation_rows=None, min_score=None, exclude=None, allow_q8=False):
         """`find` for each query clip of `waves` (what `EmbeddingExtractor.timestamp_embeddings` takes), embedded at the
         index's hop_ms and width_ms -> per clip (score (k,), row (k,), L): L, the clip's rows, is what `hits` needs.
-        exclude: None, or per clip None or a file name."""
+        exclude: None, or per clip None or a file name.  allow_q8: as in `find`."""
         self.check_extractor(extractor)
         if self.meta["hop_ms"] is None or self.meta["width_ms"] is None:
             raise ValueError("EmbeddingIndex.find_recordings: the index records no hop_ms / width_ms to embed the queries at")
@@ -311,7 +320,8 @@ class EmbeddingIndex:
         if len(exclude) != len(clips):
             raise ValueError(f"EmbeddingIndex.find_recordings: exclude must hold one name or None per clip ({len(clips)}), "
                              f"got {len(exclude)}")
-        return [self.find(emb, k, min_separation_rows, min_score, name) + (emb.shape[0],) for (emb, _), name in zip(clips, exclude)]
+        return [self.find(emb, k, min_separation_rows, min_score, name, allow_q8=allow_q8) + (emb.shape[0],)
+                for (emb, _), name in zip(clips, exclude)]
 
     def hits(self, score, index, query_rows=None):
         """(score, index) of `search` -> per query a host list of {"name", "time_ms" (None for a scene row), "row", "score"},

@@ -24,12 +24,12 @@ table.
 them with integer matrix instructions; scores are those of the quantised vectors.  `query` reads the storage from the
 index.  `convert` writes the q8 index of an existing fp32 index's rows without touching the audio again.
 
-`find` answers "where in these recordings does something like this clip occur" against an fp32 timestamp index of ANY
-width_ms: the query's timestamp embeddings, in order and at the index's hop, are laid over every position of every file;
+`find` answers "where in these recordings does something like this clip occur" against a timestamp index of ANY
+width_ms, fp32 or q8 (a q8 index matches its codes; the scores are then means of q8 scores): the query's timestamp embeddings, in order and at the index's hop, are laid over every position of every file;
 the score of a place is the mean cosine of the sequence, and the places returned are local maxima at least
 --min_separation_ms apart within a file (default: the query's length), so k hits are k distinct occurrences, not one
 place k times.  --query scene matches the one scene embedding instead, with the same peak picking.  --json prints one line
-per query: {"audio_path", "query", "rows", "hits": [{"name", "time_ms", "end_ms", "score"}, ...]}.
+per query: {"audio_path", "storage", "query", "rows", "hits": [{"name", "time_ms", "end_ms", "score"}, ...]}.
 """
 import argparse
 import contextlib
@@ -66,7 +66,7 @@ def parser():
     pq.add_argument("--json", action="store_true", help="one JSON line per query")
     pf = sub.add_parser("find", help="find where in a timestamp index something like the given WAV files occurs")
     _model_arguments(pf)
-    pf.add_argument("--index", type=str, required=True, help="directory that `index --timestamps` wrote (fp32)")
+    pf.add_argument("--index", type=str, required=True, help="directory that `index --timestamps` wrote (fp32 or q8)")
     pf.add_argument("--k", type=int, default=10, help="occurrences per query (1 to 128)")
     pf.add_argument("--min_separation_ms", type=float, default=None,
                     help="two occurrences in one file start at least this far apart (default: the query's length)")
@@ -121,8 +121,8 @@ def _extractor(args):
 
 def _find(args, extractor, index, waves, exclude):
     """The `find` command past loading: one `EmbeddingIndex.find` per query file, printed."""
-    if index.meta["kind"] != "timestamps" or index.storage != "fp32":
-        print(f"{args.index}: find needs an fp32 index built with --timestamps (this one: {index.meta['kind']}, {index.storage})",
+    if index.meta["kind"] != "timestamps":
+        print(f"{args.index}: find needs an index built with --timestamps (this one: {index.meta['kind']}, {index.storage})",
               file=sys.stderr)
         return 2
     sep = None
@@ -133,10 +133,11 @@ def _find(args, extractor, index, waves, exclude):
     else:
         queries = [emb for emb, _ in extractor.timestamp_embeddings(waves, hop_ms=index.meta["hop_ms"], width_ms=index.meta["width_ms"])]
     for path, rows, name in zip(args.audio_path, queries, exclude):
-        score, start = index.find(rows, args.k, min_separation_rows=sep, min_score=args.min_score, exclude=name)
+        score, start = index.find(rows, args.k, min_separation_rows=sep, min_score=args.min_score, exclude=name,
+                                  allow_q8=index.storage == "q8")
         found = index.hits(score, start, query_rows=rows.shape[0])
         if args.json:
-            print(json.dumps({"audio_path": path, "query": args.query, "rows": int(rows.shape[0]),
+            print(json.dumps({"audio_path": path, "storage": index.storage, "query": args.query, "rows": int(rows.shape[0]),
                               "hits": [{"name": h["name"], "time_ms": h["time_ms"], "end_ms": h["end_ms"], "score": h["score"]} for h in found]}))
         else:
             print(path)
